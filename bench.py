@@ -8,15 +8,29 @@ vbnmf_update iteration (reference src/vbnmf_update.cpp:33-90, evidence included)
 device-resident state, with lkh and the four hyper statistics delivered to the host for every
 iteration, as the reference's caller needs them (reference R/bayesian.R:345-347).
 
-The K timed steps are measured on two loops, each as the MEDIAN of 5 back-to-back repeats of the K-step region (every
-repeat bracketed by a barrier + device synchronise; all five times are reported):
-  * driven by the device (vbnmf_engine_run: the loop of vb_iterate with hyper_update and the stopping rule on the GPU,
-    steps queued ahead, the per-step history -- lkh + 4 statistics of EVERY step -- written by the control kernel
-    straight into pinned host memory) -> `value`; this is the path ccfindr_amd.vb_factorize runs by default;
+A plain run (no --full) does only what the headline needs: set-up, the W warm-up steps and the settle steps below, ONE
+timed region of exactly K steps driven by the device (vbnmf_engine_run: the loop of vb_iterate with hyper_update and the
+stopping rule on the GPU, steps queued ahead, the per-step history -- lkh + 4 statistics of EVERY step -- written by the
+control kernel straight into pinned host memory; the path ccfindr_amd.vb_factorize runs by default) -> `value` and
+`ms_per_step`, then the outputs (--dump-outputs) and the JSON line.  (--mode cells at N > 1 times the host-stepped loop.)
+After the W warm-up steps the engine runs untimed settle steps (to ~0.3 s of load in all, `config.settle_steps`) so that
+a short K measures the chip at its loaded clocks, not on its way up from idle; a K longer than the settle run is preceded
+by a run of a step or two that sizes the engine's history buffer for K rows (`config.history_presize_steps`), so that
+the timed region allocates nothing.  `warmup_effective` = W + those steps;
+`setup` = seconds of untimed set-up (ingestion of X, engine creation = the two tiled layouts + their upload, initial
+state + priming sweep; with --full also a second engine on the same matrix).
+
+--dump-outputs DIR writes what the timed path computed, as a caller of it receives it, after its last step: the state
+vb_run_rank reads back (lw, lh, ew, eh, dw, dh), the last evidence `lkh` and the tail of the per-step `history`, each as
+DIR/<name>.npy in float64 (64 MB at most in all: a larger array is replaced by a fixed, seeded sample of its elements,
+with the sampled flat indices in DIR/<name>_sample_index.npy).  The inputs depend on the arguments alone.
+
+Everything else is measured only with --full (the bench line as it was before that option existed).  The K timed steps
+are then measured on two loops, each as the MEDIAN of 5 back-to-back repeats of the K-step region (every repeat
+bracketed by a barrier + device synchronise; all five times are reported):
+  * driven by the device, as above -> `value`;
   * stepped from the host (vbnmf_engine_step: one call and one read-back of lkh + statistics per iteration, SURVEY.md
     section 8(d)'s literal metric) -> `value_host_stepped` (top level) and the `host_stepped` block.
-`warmup_effective` = W + the settle steps below; `setup` = seconds of untimed set-up (ingestion of X, engine creation =
-the two tiled layouts + their upload, initial state + priming sweep, a second engine on the same matrix).
 The roofline figures of k_sweep come from HIP events around its launches, on the engine's stream, in the host-stepped
 pass (mean per repeat, median over the five repeats, all five in `kernel_ms_repeats`).  `roofline.traffic` is measured in the
 same run at N = 1: rank 0 starts two short CHILD runs of this file under `rocprofv3 --pmc` (FETCH_SIZE, then WRITE_SIZE; each
@@ -28,12 +42,9 @@ OpenMP on the box's cores (kind "port"); `cpu_reference_literal` = the oracle's 
 src/vbnmf_update.cpp (dense, same operation order, ONE thread -- the reference builds without OpenMP, src/Makevars:1-2)
 at a stated down-scale of the same matrix, with ns per matrix element and the extrapolation to the full size.
 
-After the W warm-up steps the engine runs untimed settle steps (to ~0.3 s of load in all, `config.settle_steps`) so that
-a short K measures the chip at its loaded clocks, not on its way up from idle.
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--mode restarts|cells] [--small] [--dump-outputs DIR] [--full]
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--mode restarts|cells] [--small]
-
-Beside the headline, at every N: `rank_sweep` = BASELINE config C4 (ranks 2..20 on the same matrix through
+With --full, beside the headline, at every N: `rank_sweep` = BASELINE config C4 (ranks 2..20 on the same matrix through
 vb_factorize_sharded, reference defaults: wall seconds of the call as the library runs it -- four units in flight per
 process --, per-rank iterations, and from a second call with ONE unit at a time the stepping / setup split per process;
 that second call finds the sweep's layouts already cut); at N > 1
@@ -455,7 +466,7 @@ def measure_sweep_traffic(timeout_s=300.0):
         env = {k: v for k, v in os.environ.items() if not k.startswith(prof) and k != "LD_PRELOAD"}
         env.update(BENCH_NO_SWEEP="1", BENCH_NO_TRAFFIC="1", BENCH_NO_SMALL="1", TMPDIR="/tmp")      # (the headline's sweeps only)
         cmd = [tool, "--pmc", counter, "--output-format", "csv", "-d", out, "-o", "pmc", "--", sys.executable,
-               os.path.abspath(__file__), "--steps", "24", "--warmup", "2", "--no-cpu", "--no-ml"]
+               os.path.abspath(__file__), "--steps", "24", "--warmup", "2", "--no-cpu", "--no-ml", "--full"]
         try:
             proc = subprocess.Popen(cmd, env=env, cwd="/tmp", stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, start_new_session=True)
             try:
@@ -481,6 +492,40 @@ def measure_sweep_traffic(timeout_s=300.0):
     f, w = means["FETCH_SIZE"][0], means["WRITE_SIZE"][0]
     return (2.0 * f + w) * 1024.0, {"FETCH_SIZE_KB_per_launch": f, "WRITE_SIZE_KB_per_launch": w,
                                     "dispatches": means["FETCH_SIZE"][1], "seconds": time.perf_counter() - t_all}
+
+
+DUMP_BUDGET = 60 * 10 ** 6      # bytes of --dump-outputs in all (values + sample indices), under 64 MB
+HISTORY_TAIL = 4096             # rows of the per-step history kept by --dump-outputs (the last ones)
+
+
+def last_step_outputs(eng, res=None, host_last=None):
+    """What the timed path hands its caller after its last step, as float64 arrays: the state that
+    bayesian.vb_run_rank reads back after the loop, and the loop's result -- the evidence `lkh` and the tail of the
+    per-step `history` (device-driven loop) or the statistics of the last step (host-stepped loop).  A cell-partitioned
+    engine's get_state all-gathers: every rank calls this."""
+    out = dict(eng.get_state())
+    if res is not None:
+        out["lkh"] = np.array([res["lkh"]])
+        out["history"] = np.asarray(res["history"])[-HISTORY_TAIL:]
+    else:
+        out["lkh"] = np.array([host_last["lkh"]])
+        out["stats"] = np.array(host_last["stats"])
+    return out
+
+
+def write_outputs(path, arrays, budget=DUMP_BUDGET):
+    """arrays -> path/<name>.npy in float64.  If they exceed `budget` in all, every array above an equal share of it is
+    replaced by a fixed, seeded sample of its flattened elements (sorted indices in path/<name>_sample_index.npy)."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    share = budget // max(1, len(arrays))
+    over = sum(a.nbytes for a in arrays.values()) > budget
+    for name, a in arrays.items():
+        if over and a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // 16, replace=False))
+            np.save(os.path.join(path, f"{name}_sample_index.npy"), idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, f"{name}.npy"), a)
 
 
 def timed_repeats(fn, barrier, repeats=5, after=None):
@@ -523,6 +568,11 @@ def main():
     ap.add_argument("--no-ml", action="store_true", help="skip the ML-NMF side measurement")
     ap.add_argument("--no-traffic", action="store_true", help="skip the in-run rocprofv3 --pmc passes behind roofline.traffic")
     ap.add_argument("--rank", type=int, default=0, help="diagnostic: another rank on the same matrix (the metric is rank 10)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="every side measurement and check beside the headline (repeats, host-stepped loop, roofline, traffic, "
+                         "hyper updates on, ML-NMF, CPU references, C4 / C5, small matrix); a plain run times the headline only")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -594,9 +644,10 @@ def main():
         t_s = time.perf_counter()
         eng.set_state(wh0["lw"], wh0["lh"], wh0["eh"])
         setup["set_state_s"] = time.perf_counter() - t_s              # state upload + the priming sweep
-        t_s = time.perf_counter()
-        C.VBEngine(M, r, device=local_rank).close()
-        setup["engine_create_cached_s"] = time.perf_counter() - t_s   # a second engine on the same matrix and geometry
+        if args.full:
+            t_s = time.perf_counter()
+            C.VBEngine(M, r, device=local_rank).close()
+            setup["engine_create_cached_s"] = time.perf_counter() - t_s   # a second engine on the same matrix and geometry
         step = lambda: eng.step(HYPER)
         units_per_step = world
         scaling = "weak"
@@ -612,28 +663,42 @@ def main():
     # of milliseconds of load to leave its idle clocks (k_sweep reads 215 us in the first 5 ms after start-up and 179 us
     # 25 ms later).  After the W warm-up steps, untimed steps are added until ~0.3 s of stepping lie behind the engine.
     settle = max(0, 1200 - args.warmup)
-    if hasattr(eng, "run") and getattr(eng, "native", True):
-        eng.run(HYPER, Itmax=settle, Tol=0.0, n0=10, dn=1, flags=(False,) * 4)
+    device_loop = hasattr(eng, "run") and getattr(eng, "native", True)
+    presize = 0
+    if device_loop:
+        # The timed run records its history into the engine's pinned buffer, which the library sizes by the run's step
+        # count and grows on demand.  The settle run below records history too, so the buffer holds `settle` rows before
+        # the timed region; a longer K gets its rows here: a run asked for K steps with an unbounded tolerance stops at its
+        # first convergence test (step 2 once the evidence rises), after the buffer has been sized for K.
+        if args.steps > settle:
+            presize = eng.run(HYPER, Itmax=args.steps, Tol=float("inf"), n0=1, dn=1, flags=(False,) * 4, history=True)["it"]
+        eng.run(HYPER, Itmax=settle, Tol=0.0, n0=10, dn=1, flags=(False,) * 4, history=True)
     else:
         for _ in range(settle):
             step()
 
     base_eng = getattr(eng, "engine", eng)
-    REPEATS = 5
+    REPEATS = 5 if args.full else 1              # a plain run times ONE region of exactly K steps
     last = {}
 
     def host_pass():
         for _ in range(args.steps):
-            last["lkh"], _ = step()
+            last["lkh"], last["stats"] = step()
 
-    base_eng.timing_enable(True)
-    sweep_repeats = []                           # mean k_sweep time (HIP events on the engine's stream) of every repeat
-    host_times = timed_repeats(host_pass, barrier, REPEATS, after=lambda: sweep_repeats.append(base_eng.timing_get()))
-    dt = float(np.median(host_times))
-    lkh = last["lkh"]
-    per_repeat_ms = [ms / cnt for ms, cnt in sweep_repeats if cnt]
-    sweep_cnt = sum(cnt for _, cnt in sweep_repeats)
-    sweep_ms = (float(np.median(per_repeat_ms)) * sweep_cnt) if per_repeat_ms else 0.0      # median repeat, as for `value`
+    # The host-stepped loop: measured with --full, and the timed path of a plain run only where the device cannot drive
+    # the loop (a cell-partitioned engine without the library's collective).
+    host_times, dt, lkh = None, None, None
+    per_repeat_ms, sweep_cnt, sweep_ms = [], 0, 0.0
+    if args.full or not device_loop:
+        base_eng.timing_enable(args.full)
+        sweep_repeats = []                       # mean k_sweep time (HIP events on the engine's stream) of every repeat
+        host_times = timed_repeats(host_pass, barrier, REPEATS,
+                                   after=(lambda: sweep_repeats.append(base_eng.timing_get())) if args.full else None)
+        dt = float(np.median(host_times))
+        lkh = last["lkh"]
+        per_repeat_ms = [ms / cnt for ms, cnt in sweep_repeats if cnt]
+        sweep_cnt = sum(cnt for _, cnt in sweep_repeats)
+        sweep_ms = (float(np.median(per_repeat_ms)) * sweep_cnt) if per_repeat_ms else 0.0      # median repeat, as for `value`
 
     # The same K steps with the loop driven by the device (vbnmf_engine_run: the product's default path,
     # ccfindr_amd/bayesian.py::vb_run_rank): hyper_update and the stopping rule of vb_iterate evaluated on the GPU,
@@ -641,7 +706,8 @@ def main():
     # This is `value`; the host-stepped rate of the loop above is reported beside it.
     dt_dev = None
     dev_times = None
-    if hasattr(eng, "run") and getattr(eng, "native", True):
+    hyper_on = None
+    if device_loop:
         base_eng.timing_enable(False)
 
         def dev_pass():
@@ -652,23 +718,30 @@ def main():
         dev_times = timed_repeats(dev_pass, barrier, REPEATS)
         dt_dev = float(np.median(dev_times))
         lkh_dev = last["res"]["lkh"]
+
+    # what the timed path computed in its last step, read back before anything else runs on the engine
+    if args.dump_outputs:
+        outputs = last_step_outputs(eng, res=last["res"] if device_loop else None, host_last=last)
+        if rank == 0:
+            write_outputs(args.dump_outputs, outputs)
+        del outputs
+
+    if device_loop and args.full and world == 1:
         # one more pass with the reference's default hyper.update = TRUE (n0 = 10, dn = 1), to
         # show what the Newton updates of aw, ah on the device cost per step (reported, not `value`)
-        hyper_on = None
-        if world == 1:
-            torch.cuda.synchronize()
-            t1 = time.perf_counter()
-            res_h = eng.run(HYPER, Itmax=args.steps, Tol=0.0, n0=10, dn=1, flags=(True,) * 4)
-            torch.cuda.synchronize()
-            dt_h = time.perf_counter() - t1
-            hyper_on = {"value": res_h["it"] / dt_h, "unit": "iterations/s", "ms_per_step": 1e3 * dt_h / max(res_h["it"], 1),
-                        "steps": res_h["it"], "hyper_last": res_h["hyper"]}
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        res_h = eng.run(HYPER, Itmax=args.steps, Tol=0.0, n0=10, dn=1, flags=(True,) * 4)
+        torch.cuda.synchronize()
+        dt_h = time.perf_counter() - t1
+        hyper_on = {"value": res_h["it"] / dt_h, "unit": "iterations/s", "ms_per_step": 1e3 * dt_h / max(res_h["it"], 1),
+                    "steps": res_h["it"], "hyper_last": res_h["hyper"]}
 
     # The maximum-likelihood NMF step of factorize() (reference R/factorize.R:2-27 + :40-49)
     # on the same matrix and rank: K steps host-stepped (sweep timing) and K device-driven, reported beside the headline
     # (never part of `value`).
     ml = None
-    if world == 1 and hasattr(eng, "ml_step") and not args.no_ml:
+    if args.full and world == 1 and hasattr(eng, "ml_step") and not args.no_ml:
         rng = np.random.default_rng(2003)
         w_ml, h_ml = rng.uniform(size=(n, r)), rng.uniform(size=(r, m))
         eng.ml_set_state(w_ml, h_ml)
@@ -717,23 +790,45 @@ def main():
 
     if world > 1:
         # MAX over ranks of every repeat, then the median of those
-        t = torch.tensor([host_times, dev_times if dev_times is not None else [0.0] * REPEATS], dtype=torch.float64,
+        t = torch.tensor([host_times if host_times is not None else [0.0] * REPEATS,
+                          dev_times if dev_times is not None else [0.0] * REPEATS], dtype=torch.float64,
                          device="cuda" if backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        host_times = [float(v) for v in t[0].tolist()]
-        dt = float(np.median(host_times))
+        if host_times is not None:
+            host_times = [float(v) for v in t[0].tolist()]
+            dt = float(np.median(host_times))
         if dev_times is not None:
             dev_times = [float(v) for v in t[1].tolist()]
             dt_dev = float(np.median(dev_times))
 
     if rank == 0:
         bytes_iter, bytes_sweep = algorithmic_bytes(n, m, r, nnz)
-        host_value = units_per_step * args.steps / dt
-        host_ms = 1e3 * dt / args.steps
+        if host_times is not None:
+            host_value = units_per_step * args.steps / dt
+            host_ms = 1e3 * dt / args.steps
         if dt_dev is not None:
             value, ms_step, loop = units_per_step * args.steps / dt_dev, 1e3 * dt_dev / args.steps, "device-driven (vbnmf_engine_run)"
         else:
             value, ms_step, loop = host_value, host_ms, "host-stepped (vbnmf_engine_step)"
+        out = {
+            "metric": "VB-NMF update iterations/sec (20k x 50k sparse counts, rank 10)",
+            "value": value, "unit": "iterations/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": ms_step, "higher_is_better": True, "scaling": scaling,
+            "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "warmup_effective": args.warmup + presize + settle,
+            "setup": dict(setup, note="seconds, outside every timed region: ingestion of X, this process's first use of the device, engine creation (tiled layouts "
+                                      "cut on the host + upload), initial state + priming sweep"),
+            "config": {"workload": name, "n_genes": n, "n_cells": m, "nnz": nnz, "rank": r,
+                       "mode": args.mode if world > 1 else "single", "hyper": "fixed aw=bw=ah=bh=1",
+                       "loop": loop, "lkh_last": lkh_dev if dt_dev is not None else lkh,
+                       "timing": (f"median of {REPEATS} repeats of the {args.steps}-step region" if args.full
+                                  else f"one timed region of {args.steps} steps"),
+                       "settle_steps": settle, "history_presize_steps": presize},
+            "iteration_roofline": {"bytes_iter": bytes_iter, "achieved_GBs": bytes_iter * (value / units_per_step) / 1e9,
+                                   "frac": bytes_iter * (value / units_per_step) / 1e9 / HBM_PEAK_GBS},
+        }
+        out["repeats_ms_per_step"] = [1e3 * t / args.steps for t in (dev_times if dev_times is not None else host_times)]
+    if rank == 0 and args.full:
         sweep_s = (sweep_ms / max(sweep_cnt, 1)) * 1e-3
         achieved = bytes_sweep / sweep_s / 1e9 if sweep_cnt else None
         info = base_eng.layout_info()
@@ -754,34 +849,18 @@ def main():
                     break
                 except Exception:
                     traffic = None
-        out = {
-            "metric": "VB-NMF update iterations/sec (20k x 50k sparse counts, rank 10)",
-            "value": value, "unit": "iterations/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": ms_step, "higher_is_better": True, "scaling": scaling,
-            "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "value_host_stepped": host_value, "warmup_effective": args.warmup + settle,
-            "setup": dict(setup, note="seconds, outside every timed region: ingestion of X, this process's first use of the device, engine creation (tiled layouts "
-                                      "cut on the host + upload), initial state + priming sweep"),
-            "config": {"workload": name, "n_genes": n, "n_cells": m, "nnz": nnz, "rank": r,
-                       "mode": args.mode if world > 1 else "single", "hyper": "fixed aw=bw=ah=bh=1",
-                       "loop": loop, "lkh_last": lkh_dev if dt_dev is not None else lkh,
-                       "timing": f"median of {REPEATS} repeats of the {args.steps}-step region",
-                       "settle_steps": settle},
-            "roofline": {"bound": "hbm", "kernel": "k_sweep", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": (achieved / HBM_PEAK_GBS) if achieved else None, "traffic": traffic,
-                         "traffic_source": traffic_source,
-                         "traffic_counters": traffic_detail if isinstance(traffic_detail, dict) else None,
-                         "algorithmic_bytes_per_launch": bytes_sweep, "kernel_ms": sweep_s * 1e3,
-                         "kernel_ms_repeats": per_repeat_ms,
-                         "streamed_bytes_per_launch": info["stream_bytes_per_step"]},
-            # SURVEY.md section 8(d) asks for both fractions: algorithmic flops = 10 r per stored entry
-            "roofline_fp64": {"bound": "fp64-valu", "kernel": "k_sweep", "flops_per_launch": 10 * r * nnz,
-                              "achieved": (10 * r * nnz / sweep_s / 1e12) if sweep_cnt else None, "peak": FP64_PEAK_TFLOPS,
-                              "unit": "TFLOP/s", "frac": (10 * r * nnz / sweep_s / 1e12 / FP64_PEAK_TFLOPS) if sweep_cnt else None},
-            "iteration_roofline": {"bytes_iter": bytes_iter, "achieved_GBs": bytes_iter * (value / units_per_step) / 1e9,
-                                   "frac": bytes_iter * (value / units_per_step) / 1e9 / HBM_PEAK_GBS},
-        }
-        out["repeats_ms_per_step"] = [1e3 * t / args.steps for t in (dev_times if dev_times is not None else host_times)]
+        out["value_host_stepped"] = host_value
+        out["roofline"] = {"bound": "hbm", "kernel": "k_sweep", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                           "frac": (achieved / HBM_PEAK_GBS) if achieved else None, "traffic": traffic,
+                           "traffic_source": traffic_source,
+                           "traffic_counters": traffic_detail if isinstance(traffic_detail, dict) else None,
+                           "algorithmic_bytes_per_launch": bytes_sweep, "kernel_ms": sweep_s * 1e3,
+                           "kernel_ms_repeats": per_repeat_ms,
+                           "streamed_bytes_per_launch": info["stream_bytes_per_step"]}
+        # SURVEY.md section 8(d) asks for both fractions: algorithmic flops = 10 r per stored entry
+        out["roofline_fp64"] = {"bound": "fp64-valu", "kernel": "k_sweep", "flops_per_launch": 10 * r * nnz,
+                                "achieved": (10 * r * nnz / sweep_s / 1e12) if sweep_cnt else None, "peak": FP64_PEAK_TFLOPS,
+                                "unit": "TFLOP/s", "frac": (10 * r * nnz / sweep_s / 1e12 / FP64_PEAK_TFLOPS) if sweep_cnt else None}
         out["host_stepped"] = {"value": host_value, "unit": "iterations/s", "ms_per_step": host_ms, "steps": args.steps,
                                "lkh_last": lkh, "repeats_ms_per_step": [1e3 * t / args.steps for t in host_times]}
         if dt_dev is not None and hyper_on:
@@ -796,11 +875,11 @@ def main():
             k = min(len(cpu_lk), len(gpu_lk))
             if k:
                 out["elbo_rel_err_first_steps"] = max(abs(g / c - 1) for g, c in zip(gpu_lk[:k], cpu_lk[:k]))
-    # Everything below is a side measurement.  At N > 1 it involves collectives (tiny ones in the sweep's control plane, the
+    # Everything below is a side measurement (--full only).  At N > 1 it involves collectives (tiny ones in the sweep's control plane, the
     # library's all-reduce in the partitioned sample): it can only hang where a peer or the fabric does, so the headline
     # (measured above, without any collective) is safe behind a watchdog that prints it, records the hang and leaves.
     dog = None
-    if world > 1:
+    if world > 1 and args.full:
         import threading
 
         def give_up():
@@ -815,7 +894,7 @@ def main():
         dog.start()
     # Config C4 beside the headline, at every N: the rank sweep through vb_factorize_sharded (no collective on its data path).
     rank_sweep = None
-    if args.mode == "restarts" and args.rank == 0 and not os.environ.get("BENCH_NO_SWEEP"):
+    if args.full and args.mode == "restarts" and args.rank == 0 and not os.environ.get("BENCH_NO_SWEEP"):
         try:
             eng.close()
             rank_sweep = rank_sweep_sample(M, world, rank, local_rank, barrier, small=args.small)
@@ -823,7 +902,7 @@ def main():
             rank_sweep = {"error": f"{type(exc).__name__}: {exc}"}
         if rank == 0:
             out["rank_sweep"] = rank_sweep
-    if world == 1 and args.mode == "restarts" and args.rank == 0 and not args.small and not os.environ.get("BENCH_NO_SMALL"):
+    if args.full and world == 1 and args.mode == "restarts" and args.rank == 0 and not args.small and not os.environ.get("BENCH_NO_SMALL"):
         try:
             out["restarts_small_matrix"] = small_matrix_restarts_sample()
         except Exception as exc:                                   # noqa: BLE001 -- the headline must still be printed
@@ -831,7 +910,7 @@ def main():
     # N > 1, default mode: after the headline (independent restarts, no collective) one C5-shaped cell-partitioned
     # factorisation is run on the same N GPUs, so that the RCCL path of the library is measured on hardware too.  It can
     # only hang where the fabric does, so the headline line is safe behind a watchdog that prints it and leaves.
-    if world > 1 and args.mode == "restarts" and not os.environ.get("BENCH_NO_CELLS"):
+    if args.full and world > 1 and args.mode == "restarts" and not os.environ.get("BENCH_NO_CELLS"):
         try:
             eng.close()
             cp, times = cells_partitioned_sample(world, rank, local_rank, barrier, max(50, min(args.steps, 300)) if not args.small else 20,

@@ -10,7 +10,7 @@ OUT=$REPO/gpurun_out
 mkdir -p $OUT
 export TMPDIR=/tmp
 cd /tmp
-B20="$REPO/bench.py --rank 20 --no-cpu --no-ml"
+B20="$REPO/bench.py --full --rank 20 --no-cpu --no-ml"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_rank20_stats -o stats -- python3 $B20 --steps 200 --warmup 10 > $OUT/${TAG}_rank20_bench.json 2> $OUT/${TAG}_rank20_stats.err
 echo "rank20 stats done"
 for pass in FETCH_SIZE WRITE_SIZE; do

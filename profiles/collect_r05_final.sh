@@ -18,7 +18,7 @@ if [ "$PART" = 1 ]; then
 elif [ "$PART" = 2 ]; then
   export TMPDIR=/tmp
   R=$PWD
-  B20="$R/bench.py --rank 20 --no-cpu --no-ml"
+  B20="$R/bench.py --full --rank 20 --no-cpu --no-ml"
   (cd /tmp && BENCH_NO_SWEEP=1 BENCH_NO_TRAFFIC=1 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$OUT/r05_rank20_stats -o stats -- python3 $B20 --steps 200 --warmup 10 > $R/$OUT/r05_rank20_bench.json 2> $R/$OUT/r05_rank20_stats.err)
   for pass in FETCH_SIZE WRITE_SIZE; do
     name=$(echo $pass | tr 'A-Z' 'a-z')

@@ -4,7 +4,7 @@ export TMPDIR=/tmp
 R=$PWD
 for lib in "$@"; do
   rm -rf /tmp/abprof_$lib
-  (cd /tmp && VBNMF_LIB=$R/gpurun_build/libs/$lib rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/abprof_$lib -o st -- python3 $R/bench.py --steps 300 --warmup 10 --no-cpu --no-ml > /dev/null 2>&1)
+  (cd /tmp && VBNMF_LIB=$R/profiles/ubench/libs/$lib rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/abprof_$lib -o st -- python3 $R/bench.py --full --steps 300 --warmup 10 --no-cpu --no-ml > /dev/null 2>&1)
   python3 - <<EOF
 import csv,glob
 f=glob.glob("/tmp/abprof_$lib/**/*kernel_stats.csv",recursive=True)

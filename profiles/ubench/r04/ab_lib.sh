@@ -9,7 +9,7 @@ for rep in 1 2 3; do
   for r in $RANKS; do
     for v in new old; do
       if [ $v = new ]; then unset VBNMF_LIB; else export VBNMF_LIB=$LIB; fi
-      out=$(python3 $R/bench.py --rank $r --steps 600 --no-cpu --no-ml 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('%.1f it/s step %.1f us sweep %.1f us' % (d['value'], 1e3*d['ms_per_step'], 1e3*d['roofline']['kernel_ms']))")
+      out=$(python3 $R/bench.py --full --rank $r --steps 600 --no-cpu --no-ml 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('%.1f it/s step %.1f us sweep %.1f us' % (d['value'], 1e3*d['ms_per_step'], 1e3*d['roofline']['kernel_ms']))")
       echo "rank $r $v rep $rep: $out"
     done
   done
@@ -18,6 +18,6 @@ cd /tmp
 for v in new old; do
   if [ $v = new ]; then unset VBNMF_LIB; else export VBNMF_LIB=$LIB; fi
   rm -rf /tmp/abl_$v
-  rocprofv3 --kernel-trace --output-format csv -d /tmp/abl_$v -o t -- python3 $R/bench.py --steps 100 --warmup 5 --no-cpu --no-ml > /dev/null 2>&1
+  rocprofv3 --kernel-trace --output-format csv -d /tmp/abl_$v -o t -- python3 $R/bench.py --full --steps 100 --warmup 5 --no-cpu --no-ml > /dev/null 2>&1
   echo "rank 10 $v"; python3 $R/profiles/ubench/r04/update_split.py /tmp/abl_$v | grep k_update
 done

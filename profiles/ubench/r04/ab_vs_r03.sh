@@ -8,6 +8,6 @@ for rep in 1 2 3; do
   for r in 10 16 20; do
     if [ $r = 10 ]; then a=""; else a="--rank $r"; fi
     echo "rank $r rep $rep r03: $(cd $R/build/r03_tree && python3 bench.py $a --no-cpu --no-ml 2>/dev/null | line)"
-    echo "rank $r rep $rep r04: $(cd $R && python3 bench.py $a --no-cpu --no-ml 2>/dev/null | line)"
+    echo "rank $r rep $rep r04: $(cd $R && python3 bench.py --full $a --no-cpu --no-ml 2>/dev/null | line)"
   done
 done

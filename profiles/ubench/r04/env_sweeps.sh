@@ -6,7 +6,7 @@ export BENCH_NO_SWEEP=1
 REPO=$PWD
 one() {  # label, env assignments...
   label=$1; shift
-  out=$(env "$@" python3 $REPO/bench.py --steps 600 --no-cpu --no-ml 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('%.1f it/s step %.1f us sweep %.1f us' % (d['value'], 1e3*d['ms_per_step'], 1e3*d['roofline']['kernel_ms']))")
+  out=$(env "$@" python3 $REPO/bench.py --full --steps 600 --no-cpu --no-ml 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('%.1f it/s step %.1f us sweep %.1f us' % (d['value'], 1e3*d['ms_per_step'], 1e3*d['roofline']['kernel_ms']))")
   echo "headline $label: $out"
 }
 for rep in 1 2; do

@@ -9,7 +9,7 @@ for r in 10 20; do
   for lib in default lib_r04_NOGATHER.so lib_r04_NOSPECIAL.so lib_r04_NOWRITE.so; do
     if [ $lib = default ]; then unset VBNMF_LIB; else export VBNMF_LIB=$R/profiles/ubench/libs/$lib; fi
     rm -rf /tmp/abl
-    rocprofv3 --kernel-trace --output-format csv -d /tmp/abl -o t -- python3 $R/bench.py --rank $r --steps 100 --warmup 5 --no-cpu --no-ml > /dev/null 2>&1
+    rocprofv3 --kernel-trace --output-format csv -d /tmp/abl -o t -- python3 $R/bench.py --full --rank $r --steps 100 --warmup 5 --no-cpu --no-ml > /dev/null 2>&1
     echo "== rank $r $lib"; python3 $R/profiles/ubench/r04/update_split.py /tmp/abl | grep k_update
   done
 done
