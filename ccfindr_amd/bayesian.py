@@ -396,8 +396,18 @@ def vb_run_units_batch(units, bundle):
                           initializer=bundle["initializer"], rng=rng, device=bundle.get("device", 0))
             eng.set_state(wh0["lw"], wh0["lh"], wh0["eh"])
         engines.append(eng); hypers.append(hyper)
-    outs = run_batch(engines, hypers, Itmax=bundle["Itmax"], Tol=bundle["Tol"], n0=bundle["hyper_update_n0"],
-                     dn=bundle["hyper_update_dn"], flags=bundle["hyper_update"], fudge=bundle["fudge"])
+    loop = dict(Itmax=bundle["Itmax"], Tol=bundle["Tol"], n0=bundle["hyper_update_n0"], dn=bundle["hyper_update_dn"],
+                flags=bundle["hyper_update"], fudge=bundle["fudge"])
+    try:
+        outs = run_batch(engines, hypers, **loop)
+    except N.VBNMFError as exc:
+        # Engines whose update table does not fit one block's LDS row (a wide, very sparse matrix on a batch's narrow grid:
+        # engine.hip build_update_table) keep the two-launch update, which the batch kernels do not serve; vbnmf_batch_run
+        # refuses them (VBNMF_ERR_STATE) before any step.  The engines here are one grid and width with their states set, so
+        # that is the only refusal possible: every unit then runs its own loop, as batch = 1 does on the same engines.
+        if exc.code != N.ERR_STATE:
+            raise
+        outs = [eng.run(hyper, **loop) for eng, hyper in zip(engines, hypers)]
     if any(o["reason"] == 3 for o in outs):
         raise RuntimeError("Hyper-parameter update failed to converge")          # reference R/bayesian.R:43
     recs = []

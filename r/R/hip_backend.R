@@ -44,8 +44,18 @@ vb_restarts_rank_hip <- function(gpu_mat, rank, whs, hyper, bundle, geometry_ran
   engs <- tryCatch(lapply(whs, function(wh) vbnmf_engine_geom(gpu_mat, rank, geometry_rank, wh, device)),
                    finally = vbnmf_set_grid(0, 0))
   hy <- matrix(rep(unlist(hyper[c("aw", "bw", "ah", "bh")]), each = B), nrow = B)
-  out <- vbnmf_run_batch(engs, hy, bundle$fudge, bundle$Itmax, bundle$Tol, bundle$hyper.update.n0,
-                         bundle$hyper.update.dn, bundle$hyper.update)
+  # Engines whose update table does not fit one block's LDS row (a wide, very sparse matrix on a batch's narrow grid) keep the
+  # two-launch update, which the batch kernels do not serve: vbnmf_batch_run refuses them before any step, and every restart
+  # then runs its own loop on its engine (vbnmf_run), as one restart at a time would.
+  out <- tryCatch(vbnmf_run_batch(engs, hy, bundle$fudge, bundle$Itmax, bundle$Tol, bundle$hyper.update.n0,
+                                  bundle$hyper.update.dn, bundle$hyper.update),
+                  error = function(e) if (grepl("one-launch update form", conditionMessage(e), fixed = TRUE)) NULL else stop(e))
+  if (is.null(out)) {
+    one <- lapply(engs, function(eng) vbnmf_run(eng, unlist(hyper), bundle$fudge, bundle$Itmax, bundle$Tol,
+                                                bundle$hyper.update.n0, bundle$hyper.update.dn, bundle$hyper.update))
+    return(lapply(seq_len(B), function(b) list(wh = vbnmf_state(engs[[b]]), hyper = as.list(one[[b]]$hyper),
+                                               lk0 = one[[b]]$lk0, it = one[[b]]$it)))
+  }
   lapply(seq_len(B), function(b) list(wh = vbnmf_state(engs[[b]]), hyper = as.list(out$hyper[b, ]), lk0 = out$lk0[b],
                                       it = out$it[b]))
 }
