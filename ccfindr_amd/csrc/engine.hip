@@ -506,6 +506,14 @@ int launch_sweep(vbnmf_engine *e)
     return VBNMF_OK;
 }
 
+// Whether an update of `grid` blocks stages the inverse index of side S in LDS: it pays from a few hundred task ids per block
+// on (on tiny matrices its two leading round trips are all there is to the kernel -- 200 x 500 at rank 3: 30.7 -> 31.3 us per
+// step with it).  `dense`: the partitioned gene side, whose statistics are already summed into `red` -- no index to stage.
+int stage_ids(const DeviceSide &S, unsigned grid, bool dense = false)
+{
+    return !dense && S.n_tasks >= (int64_t)256 * grid ? 1 : 0;
+}
+
 // ctl != nullptr: device-driven loop, the hyper-parameters are read from the control block on the device
 int launch_update(vbnmf_engine *e, bool gene_side, double a, double b, double fudge, const LoopCtl *ctl = nullptr,
                   const ControlFold *foldp = nullptr)
@@ -528,12 +536,9 @@ int launch_update(vbnmf_engine *e, bool gene_side, double a, double b, double fu
     double *l = gene_side ? e->lw : e->lh, *ll = gene_side ? e->llw : e->llh;
     double *ev = gene_side ? e->ew : e->eh, *d = gene_side ? e->dw : e->dh;
     double *bp = gene_side ? e->bpW : e->bpH;
-    static const int stage_allowed = [] { const char *v = getenv("VBNMF_NO_STAGE_IDS"); return (v && v[0] == '1') ? 0 : 1; }();   // A/B switch
-    // (staging the inverse index in LDS pays from a few hundred task ids per block on: on tiny matrices its two leading
-    // round trips are all there is to the kernel -- 200 x 500 at rank 3: 30.7 -> 31.3 us per step with it)
-    const int stage_ids = stage_allowed && !dense && S.n_tasks >= (int64_t)256 * grid ? 1 : 0;
+    const int stage = stage_ids(S, grid, dense);
     switch (e->R) {
-#define X(RR) case RR: hipLaunchKernelGGL((k_update<RR>), dim3(grid), dim3(kUpdateThreads), 0, e->stream, acc, inv_ptr, inv_task, nmaj, e->r, other, other_bp, other_nb, a, b, lga, fudge, l, ll, ev, d, bp, ctl, side, fold, stage_ids); break;
+#define X(RR) case RR: hipLaunchKernelGGL((k_update<RR>), dim3(grid), dim3(kUpdateThreads), 0, e->stream, acc, inv_ptr, inv_task, nmaj, e->r, other, other_bp, other_nb, a, b, lga, fudge, l, ll, ev, d, bp, ctl, side, fold, stage); break;
         VBNMF_FOR_EACH_R(X)
 #undef X
         default: return fail(VBNMF_ERR_BAD_ARG, "unsupported padded rank %d", e->R);
@@ -776,10 +781,8 @@ int launch_ml_update(vbnmf_engine *e, bool gene_side, int prior, double ga, doub
     MlFold fold{};
     if (foldp) fold = *foldp;
     const unsigned grid = fold.control_only ? 1 : (unsigned)e->ub;
-    static const int stage_allowed = [] { const char *v = getenv("VBNMF_NO_STAGE_IDS"); return (v && v[0] == '1') ? 0 : 1; }();
-    const int stage_ids = stage_allowed && S.n_tasks >= (int64_t)256 * grid ? 1 : 0;      // (as launch_update)
     switch (e->R) {
-#define X(RR) case RR: hipLaunchKernelGGL((k_ml_update<RR>), dim3(grid), dim3(kUpdateThreads), 0, e->stream, S.part, S.inv_ptr, S.inv_task, nmaj, e->r, other_bp, e->ub, prior, ga, gb, eps, f, bp, stop, fold, stage_ids); break;
+#define X(RR) case RR: hipLaunchKernelGGL((k_ml_update<RR>), dim3(grid), dim3(kUpdateThreads), 0, e->stream, S.part, S.inv_ptr, S.inv_task, nmaj, e->r, other_bp, e->ub, prior, ga, gb, eps, f, bp, stop, fold, stage_ids(S, grid)); break;
         VBNMF_FOR_EACH_R(X)
 #undef X
         default: return fail(VBNMF_ERR_BAD_ARG, "unsupported padded rank %d", e->R);
@@ -1610,10 +1613,38 @@ int group_tables(vbnmf_comm *c)
     return VBNMF_OK;
 }
 
+// The fold of step t (1-based) of an unpartitioned engine's run: the control step of the previous sweep, folded into this
+// step's gene-side update (kernels.h: ControlFold).  Step t + 1's fold, with bpW_prev and control_only set, is the control
+// step alone behind the last step.
+ControlFold vb_fold(const vbnmf_engine *e, int t, bool hist)
+{
+    ControlFold f{};
+    f.prev = e->ctl2 + ((t - 1) & 1); f.next = e->ctl2 + (t & 1);
+    f.epart = e->epart; f.nepart = 2 * (int64_t)e->n_wg;
+    f.lgx = e->lgx; f.n = (double)e->n; f.m_global = (double)e->m_global;
+    f.history = hist ? e->h_hist_dev : nullptr; f.out_host = e->h_out_dev;
+    f.do_control = t > 1 ? 1 : 0;
+    return f;
+}
+
+// The same for the ML loop: the control step of the previous cell-side sweep, folded into step t's H update (mlnmf.h: MlFold);
+// bpH_prev is the table of H-side partials the previous step wrote.
+MlFold ml_fold(const vbnmf_engine *e, int t, bool hist, const double *bpH_prev)
+{
+    MlFold f{};
+    f.prev = e->ctl2 + ((t - 1) & 1); f.next = e->ctl2 + (t & 1);
+    f.bpH_prev = bpH_prev;
+    f.epart = e->epart + e->n_wg; f.nepart = (int64_t)e->n_wg;
+    f.xlx = e->xlx; f.n = (double)e->n; f.m = (double)e->m;
+    f.history = hist ? e->h_hist_dev : nullptr; f.out_host = e->h_out_dev;
+    f.do_control = t > 1 ? 1 : 0;
+    return f;
+}
+
 // One step of the device-driven VB loop, queued on every engine of the group.
 //   unpartitioned : k_update(W, + the control step of the previous sweep) k_update(H) k_sweep(both sides)
 //   partitioned   : k_update(W <- reduced statistics, + the control step of the previous sweeps) k_update(H) | gene-side sweep
-//                   | k_pack_tail (main stream for an RCCL rank, comm stream for a local group) | event
+//                   | k_pack_tail | event
 //                   -> comm stream: all-reduce [swsum | rowSum(eh) | 2 scalars]     (RCCL, or k_group_sum)
 //                   || main stream: cell-side sweep
 //                   -> main stream: all-reduce [evidence slots | sum lgamma(x+1)]   (behind an event after the first one)
@@ -1628,12 +1659,7 @@ int queue_vb_step(const LoopGroup &G, double fudge, bool hist, int max_it)
         // the run, the control step alone (kernels.h: ControlFold)
         vbnmf_engine *e = G.e[0];
         const int t = ++e->fold_step;                               // 1-based step of this run
-        ControlFold f{};
-        f.prev = e->ctl2 + ((t - 1) & 1); f.next = e->ctl2 + (t & 1);
-        f.epart = e->epart; f.nepart = 2 * (int64_t)e->n_wg;
-        f.lgx = e->lgx; f.n = (double)e->n; f.m_global = (double)e->m_global;
-        f.history = hist ? e->h_hist_dev : nullptr; f.out_host = e->h_out_dev;
-        f.do_control = t > 1 ? 1 : 0;
+        ControlFold f = vb_fold(e, t, hist);
         int rc;
         if (e->pair) {
             // k_update2(W and H, with the control step of the previous sweep folded in)  k_sweep : two launches per step
@@ -1648,10 +1674,8 @@ int queue_vb_step(const LoopGroup &G, double fudge, bool hist, int max_it)
         }
         if (!rc) rc = launch_sweep(e);
         if (!rc && t == max_it) {
-            ControlFold g = f;
-            g.prev = f.next; g.next = e->ctl2 + ((t + 1) & 1);
-            g.bpW_prev = e->bpW;
-            g.do_control = 1; g.control_only = 1;
+            ControlFold g = vb_fold(e, t + 1, hist);
+            g.bpW_prev = e->bpW; g.control_only = 1;
             rc = launch_update(e, true, 0, 0, fudge, nullptr, &g);
         }
         return rc;
@@ -1673,7 +1697,6 @@ int queue_vb_step(const LoopGroup &G, double fudge, bool hist, int max_it)
     vbnmf_engine *L = G.e[0];                                  // leader: owner of the comm stream used by a local group
     const int64_t nbig = L->n * L->R + L->R + 2;
     const bool fold = L->fold;
-    static const bool small_on_comm = [] { const char *v = getenv("VBNMF_SMALL_ON_COMM"); return v && v[0] == '1'; }();   // (see the second exchange below)
     hipEvent_t evA[64], evB[64];
     ControlFold last{};                                        // (fold) the control-only launch behind step max_it
     for (int p = 0; p < P; p++) {
@@ -1713,25 +1736,18 @@ int queue_vb_step(const LoopGroup &G, double fudge, bool hist, int max_it)
         // with the chip to itself, + the cell side's column sums) on the MAIN stream, between the two sweeps: the all-reduce
         // of n * R doubles must travel WHILE the cell-side sweep runs, and a pack queued beside that sweep on the comm
         // stream is starved by its persistent workgroups (profiles/r04_c5_step_timeline.txt: 168 us, ending after the
-        // sweep -- the collective would start when the sweep is over).  VBNMF_PACK_ON_MAIN=0 puts it on the comm stream
-        // (A/B switch: round 4's first half ran it there; on the final build it is slower for a local group of eight as
-        // well, 0.373-0.376 against 0.370-0.371 ms per partition step on the same box).
-        static const bool pack_on_main = [] { const char *v = getenv("VBNMF_PACK_ON_MAIN"); return !(v && v[0] == '0'); }();
-        hipStream_t ps = pack_on_main ? e->stream : e->cstream;
-        if (!pack_on_main) {
-            hipEvent_t evS = next_event(e);
-            HIPCHECK(hipEventRecord(evS, e->stream));
-            HIPCHECK(hipStreamWaitEvent(e->cstream, evS, 0));
-        }
+        // sweep -- the collective would start when the sweep is over).  Round 4's first half ran it on the comm stream; on
+        // the final build that is slower for a local group of eight as well, 0.373-0.376 against 0.370-0.371 ms per
+        // partition step on the same box.
         const int64_t cnt = e->n * e->R;
-        hipLaunchKernelGGL(k_pack_tail, dim3((unsigned)((cnt + 255) / 256) + 1), dim3(256), 0, ps, e->A.part, e->A.inv_ptr, e->A.inv_task, e->n, e->R, e->red,
+        hipLaunchKernelGGL(k_pack_tail, dim3((unsigned)((cnt + 255) / 256) + 1), dim3(256), 0, e->stream, e->A.part, e->A.inv_ptr, e->A.inv_task, e->n, e->R, e->red,
                            e->bpH, e->ub, stop);
         HIPCHECK(hipGetLastError());
         evA[p] = next_event(e);
-        HIPCHECK(hipEventRecord(evA[p], ps));
+        HIPCHECK(hipEventRecord(evA[p], e->stream));
     }
     if (c->kind == 0) {
-        HIPCHECK(hipStreamWaitEvent(L->cstream, evA[0], 0));   // (a no-op when k_pack / k_tail_h ran on the comm stream themselves)
+        HIPCHECK(hipStreamWaitEvent(L->cstream, evA[0], 0));
         if (int rc = rccl_check(rccl_api().AllReduce(L->red, L->red_g, (size_t)nbig, ncclDouble, ncclSum, c->nc, L->cstream), "ncclAllReduce")) return rc;
     } else {
         for (int p = 0; p < P; p++) HIPCHECK(hipStreamWaitEvent(L->cstream, evA[p], 0));
@@ -1745,7 +1761,7 @@ int queue_vb_step(const LoopGroup &G, double fudge, bool hist, int max_it)
             hipLaunchKernelGGL(k_tail_data, dim3(1), dim3(1024), 0, e->stream, e->epart, 2 * (int64_t)e->n_wg, e->lgx, e->red + nbig, &e->ctl->stop);
             HIPCHECK(hipGetLastError());
         }
-        if (small_on_comm || p > 0) {                            // (an event costs the stream a barrier packet: only where another stream waits on it)
+        if (p > 0) {                                           // (an event costs the stream a barrier packet: only where another stream waits on it)
             evB[p] = next_event(e);
             HIPCHECK(hipEventRecord(evB[p], e->stream));
         }
@@ -1754,29 +1770,24 @@ int queue_vb_step(const LoopGroup &G, double fudge, bool hist, int max_it)
     // issued on the leader's MAIN stream: no hand-over to the comm stream and back (two cross-queue waits, microseconds
     // each, for a collective of a few KB).  It follows the first exchange through an event recorded behind it on the comm
     // stream -- long satisfied by then -- so the two collectives of a step never overlap and every rank issues them in the
-    // same order.  VBNMF_SMALL_ON_COMM=1 puts it back on the comm stream (A/B switch).
-    hipStream_t ss = small_on_comm ? L->cstream : L->stream;
-    if (!small_on_comm) {
-        hipEvent_t evBig = next_event(L);
-        HIPCHECK(hipEventRecord(evBig, L->cstream));
-        HIPCHECK(hipStreamWaitEvent(L->stream, evBig, 0));
-    }
-    const bool need_evD = small_on_comm || P > 1;
-    hipEvent_t evD = need_evD ? next_event(L) : nullptr;
+    // same order.
+    hipEvent_t evBig = next_event(L);
+    HIPCHECK(hipEventRecord(evBig, L->cstream));
+    HIPCHECK(hipStreamWaitEvent(L->stream, evBig, 0));
+    hipEvent_t evD = P > 1 ? next_event(L) : nullptr;
+    const int64_t nsmall = fold ? kEvSlots + 1 : 2;
     if (c->kind == 0) {
-        if (small_on_comm) HIPCHECK(hipStreamWaitEvent(L->cstream, evB[0], 0));
-        const int64_t off = fold ? L->red_count : nbig, cnt = fold ? kEvSlots + 1 : 2;
-        if (int rc = rccl_check(rccl_api().AllReduce(L->red + off, L->red_g + off, (size_t)cnt, ncclDouble, ncclSum, c->nc, ss), "ncclAllReduce")) return rc;
+        const int64_t off = fold ? L->red_count : nbig;
+        if (int rc = rccl_check(rccl_api().AllReduce(L->red + off, L->red_g + off, (size_t)nsmall, ncclDouble, ncclSum, c->nc, L->stream), "ncclAllReduce")) return rc;
     } else {
-        for (int p = small_on_comm ? 0 : 1; p < P; p++) HIPCHECK(hipStreamWaitEvent(ss, evB[p], 0));
-        const int64_t cnt = fold ? kEvSlots + 1 : 2;
-        hipLaunchKernelGGL(k_group_sum, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, ss, c->d_send_small, c->d_recv_small, P, cnt);
+        for (int p = 1; p < P; p++) HIPCHECK(hipStreamWaitEvent(L->stream, evB[p], 0));
+        hipLaunchKernelGGL(k_group_sum, dim3((unsigned)((nsmall + 255) / 256)), dim3(256), 0, L->stream, c->d_send_small, c->d_recv_small, P, nsmall);
         HIPCHECK(hipGetLastError());
     }
-    if (need_evD) HIPCHECK(hipEventRecord(evD, ss));
+    if (evD) HIPCHECK(hipEventRecord(evD, L->stream));
     for (int p = 0; p < P; p++) {
         vbnmf_engine *e = G.e[p];
-        if (need_evD && e->stream != ss) HIPCHECK(hipStreamWaitEvent(e->stream, evD, 0));
+        if (evD && e->stream != L->stream) HIPCHECK(hipStreamWaitEvent(e->stream, evD, 0));
         if (!fold) { if (int rc = launch_control(e, hist && p == 0 ? e->h_hist_dev : nullptr, true)) return rc; }
         else if (last.control_only) {                           // behind the last step of the run: the control step alone
             ControlFold g = last;
@@ -1791,31 +1802,49 @@ int queue_vb_step(const LoopGroup &G, double fudge, bool hist, int max_it)
     return VBNMF_OK;
 }
 
-// Host side of a device-driven loop.  Steps are queued in batches of eight, two batches ahead of the device, and batch
-// b + 2 is queued exactly when the loop has not stopped at or before the last step of batch b -- a function of the
-// device's (replicated) decisions alone, never of when this host happened to look.  Every process of a partitioned run
-// therefore queues the same number of steps, i.e. the same sequence of collectives.  The host reads the pinned result
-// block of engine 0: [5] = steps done, [6] = reason (raised after [5]), [7] = steps done (raised last).
+// Host side of every device-driven loop: a single engine, a local group, a batch.  Steps are queued in batches of eight, two
+// batches ahead of the device, by queue_step(t) (t: the 1-based step); the host polls the pinned result blocks of `polled`
+// engines (engine 0 for a single engine or a group, every engine for a batch): [5] = steps done, [6] = reason (raised after
+// [5]), [7] = steps done (raised last).  Batch b + 2 is queued
+//   replicated  (single engine, group): unless the loop stopped at or before the last step of batch b -- a function of the
+//               device's (replicated) decisions alone, never of when this host happened to look, so every process of a
+//               partitioned run queues the same number of steps, i.e. the same sequence of collectives;
+//   !replicated (batch): unless every engine has stopped.
+// `fold`: the control step is folded into the NEXT step's update (ControlFold / MlFold).  A timed-out wait sets poisoned on
+// engine 0 (RunScope::end passes it on to the run's other engines).
 template <class QueueStep>
-int drive_loop(vbnmf_engine *e0, int max_it, bool fold, QueueStep &&queue_step)
+int drive_loop(vbnmf_engine *const *engs, int polled, bool replicated, int max_it, bool fold, QueueStep &&queue_step)
 {
-    volatile double *ho = e0->h_out;
+    vbnmf_engine *e0 = engs[0];
     const int B = 8;
     int queued = 0;
     auto queue_batch = [&]() -> int {
         for (int q = 0; q < B && queued < max_it; q++, queued++)
-            if (int rc = queue_step()) return rc;
+            if (int rc = queue_step(queued + 1)) return rc;
         return VBNMF_OK;
     };
-    // "The stream is idle, no stop was raised, and fewer steps are reported than a drained stream must show": something
-    // was lost on the device.  With the control step folded into the NEXT step's update (ControlFold / MlFold) step t is
-    // only reported by step t + 1's launch, so a fully drained, healthy stream shows queued - 1 until the closing
-    // control-only launch behind step max_it has been queued.
-    auto idle_check = [&]() -> int {
+    // every polled engine has stopped or reported `target` steps; all_stopped: every one has stopped
+    auto reached = [&](int target, bool &all_stopped) {
+        bool ok = true;
+        all_stopped = true;
+        for (int p = 0; p < polled; p++) {
+            volatile double *ho = engs[p]->h_out;
+            const bool stopped = ho[6] != 0.0;
+            all_stopped = all_stopped && stopped;
+            ok = ok && (stopped || (int)ho[7] >= target);
+        }
+        return ok;
+    };
+    // "The stream is idle and an engine that raised no stop reports fewer steps than a drained stream must show": something
+    // was lost on the device.  With the fold, step t is only reported by step t + 1's launch, so a fully drained, healthy
+    // stream shows queued - 1 until the closing control-only launch behind step max_it has been queued.
+    auto idle_check = [&](int target) -> int {
         hipError_t q = hipStreamQuery(e0->stream);
-        if (q != hipSuccess && q != hipErrorNotReady) return fail(VBNMF_ERR_HIP, "the loop failed on the device: %s", hipGetErrorString(q));
+        if (q != hipSuccess && q != hipErrorNotReady) return fail(VBNMF_ERR_HIP, "the device-driven loop failed on the device: %s", hipGetErrorString(q));
         const int expect = queued - ((fold && queued < max_it) ? 1 : 0);
-        if (q == hipSuccess && ho[6] == 0.0 && (int)ho[7] < expect) return fail(VBNMF_ERR_HIP, "the device went idle before the queued steps finished");
+        bool all_stopped;
+        if (q == hipSuccess && !reached(std::min(target, expect), all_stopped))
+            return fail(VBNMF_ERR_HIP, "the device went idle before the queued steps of the device-driven loop finished");
         return VBNMF_OK;
     };
     // test hook (tests/test_gpu_control_fold.py): drain the stream before every look, i.e. the host thread stalled between
@@ -1830,24 +1859,119 @@ int drive_loop(vbnmf_engine *e0, int max_it, bool fold, QueueStep &&queue_step)
         const auto t0 = std::chrono::steady_clock::now();          // the bound is per batch of B steps
         if (drain_first) {
             (void)hipStreamSynchronize(e0->stream);
-            if (int rc = idle_check()) return rc;
+            if (int rc = idle_check(target)) return rc;
         }
-        for (long spins = 1; ho[6] == 0.0 && (int)ho[7] < target; spins++) {
+        bool all_stopped = false;
+        for (long spins = 1; !reached(target, all_stopped); spins++) {
             if ((spins & 0xFFFF) == 0) {
                 const double waited = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
                 if (waited > limit) {
                     e0->poisoned = true;
                     return fail(VBNMF_ERR_HIP, "timed out after %.1f s (VBNMF_WAIT_TIMEOUT_S) waiting for step %d of the device-driven loop; "
-                                "the last completed step is %d (%d queued)", waited, target, (int)ho[7], queued);
+                                "the last completed step is %d (%d queued)", waited, target, (int)e0->h_out[7], queued);
                 }
-                if (int rc = idle_check()) return rc;
+                if (int rc = idle_check(target)) return rc;
             }
         }
-        if (ho[6] != 0.0 && (int)ho[5] <= target) break;        // stopped inside a batch that is complete
+        volatile double *ho = e0->h_out;
+        if (replicated ? ho[6] != 0.0 && (int)ho[5] <= target : all_stopped) break;
         if (target >= max_it) break;
         if (int rc = queue_batch()) return rc;
     }
     return VBNMF_OK;
+}
+
+// What a device-driven run changes on its engines: begin() saves it and loads every engine's control block, end() waits for
+// the streams and puts it back.  shared: the stream every launch of a batch goes on (null: each engine its own).
+struct RunScope {
+    vbnmf_engine *const *e;
+    int count;
+    hipStream_t shared = nullptr;
+    std::vector<hipStream_t> own;
+    std::vector<char> timing;
+
+    // ctl(p): the control block engine p's loop starts from
+    template <class CtlOf>
+    int begin(CtlOf &&ctl)
+    {
+        own.resize(count); timing.resize(count);
+        for (int p = 0; p < count; p++) {
+            vbnmf_engine *x = e[p];
+            own[p] = x->stream; timing[p] = x->timing;
+            x->timing = false;                                     // event pairs cannot follow launches queued ahead
+            x->ev_recorded = false; x->ev2_recorded = false;
+            if (shared) x->stream = shared;
+            hipLaunchKernelGGL(k_ctl_init, dim3(1), dim3(1), 0, x->stream, x->fold ? x->ctl2 : x->ctl, ctl(p));
+            x->fold_step = 0;
+            volatile double *ho = x->h_out;
+            ho[5] = 0.0; ho[6] = 0.0; ho[7] = 0.0;
+            x->run_active = true;
+        }
+        hipError_t he = hipGetLastError();
+        if (he != hipSuccess) return end(fail(VBNMF_ERR_HIP, "loading the loop control block failed: %s", hipGetErrorString(he)));
+        return VBNMF_OK;
+    }
+
+    // After a timeout (engine 0 poisoned) the streams may never drain: every engine is poisoned and gets its own stream back,
+    // nothing is waited for.  Otherwise a failed synchronise becomes the result of a run that had succeeded.
+    int end(int rc)
+    {
+        if (e[0]->poisoned) {
+            for (int p = 0; p < count; p++) { e[p]->poisoned = true; e[p]->stream = own[p]; }
+            return rc;
+        }
+        for (int p = 0; p < (shared ? 1 : count); p++) {
+            vbnmf_engine *x = e[p];
+            hipError_t he = hipStreamSynchronize(x->stream);
+            if (he == hipSuccess && x->cstream) he = hipStreamSynchronize(x->cstream);
+            if (he != hipSuccess && !rc) rc = fail(VBNMF_ERR_HIP, "hipStreamSynchronize failed: %s", hipGetErrorString(he));
+        }
+        for (int p = 0; p < count; p++) {
+            vbnmf_engine *x = e[p];
+            x->stream = own[p];
+            x->run_active = false; x->timing = timing[p];
+            x->stop_ptr = nullptr;
+            x->seq = 0.0; x->h_out[7] = 0.0;                       // the step path's sequence flag restarts
+        }
+        return rc;
+    }
+};
+
+// The results the last live control step of each of `count` engines left in its h_out: [5] steps, [6] reason, [0] the last
+// likelihood (lk: lkh of the VB loop, lk of the ML loop -- [0] itself stays, ml_likelihood() keeps answering for the pair
+// held now), [12] lk0 and [8..11] the hyper-parameters (VB); history: `rows` rows of `width` doubles per engine.
+void read_out(vbnmf_engine *const *engs, int count, int32_t *it_out, double *lk0_out, double *lk_out, int32_t *reason_out,
+              double *hyper, double *history, int64_t rows, int width)
+{
+    for (int b = 0; b < count; b++) {
+        const double *ho = engs[b]->h_out;
+        const int it = (int)ho[5];
+        if (hyper) for (int q = 0; q < 4; q++) hyper[(size_t)b * 4 + q] = ho[8 + q];
+        if (it_out) it_out[b] = it;
+        if (lk0_out) lk0_out[b] = ho[12];
+        if (lk_out) lk_out[b] = ho[0];
+        if (reason_out) reason_out[b] = (int)ho[6];
+        if (history && it > 0) std::memcpy(history + (size_t)b * rows * width, engs[b]->h_hist, (size_t)it * width * sizeof(double));
+    }
+}
+
+// The control block of a VB loop: hyper[0..3] and flags[0..3] as hyper.update
+LoopCtl vb_ctl(const double *hyper, const int32_t *flags, double tol, int32_t max_it, int32_t n0, int32_t dn)
+{
+    LoopCtl c{};
+    for (int q = 0; q < 4; q++) { c.hyper[q] = hyper[q]; c.flags[q] = flags[q] ? 1 : 0; }
+    c.lk0 = 0.0;                                                   // :336
+    c.tol = tol; c.max_it = max_it; c.n0 = n0; c.dn = dn;
+    return c;
+}
+
+// ... of an ML loop
+LoopCtl ml_ctl(double tol, int32_t max_it)
+{
+    LoopCtl c{};
+    c.lk0 = -INFINITY;                                             // lkold <- -Inf (R/factorize.R:193)
+    c.tol = tol; c.max_it = max_it;
+    return c;
 }
 
 int run_group(const LoopGroup &G, double *hyper, double fudge, int32_t max_it, double tol, int32_t n0, int32_t dn,
@@ -1867,65 +1991,26 @@ int run_group(const LoopGroup &G, double *hyper, double fudge, int32_t max_it, d
     if (int rc = use_device(e0)) return rc;
     if (history) { if (int rc = ensure_history(e0, (size_t)max_it * 9)) return rc; }
 
-    LoopCtl c{};
-    for (int q = 0; q < 4; q++) { c.hyper[q] = hyper[q]; c.flags[q] = flags[q] ? 1 : 0; }
-    c.lk0 = 0.0;                                                   // :336
-    c.tol = tol; c.max_it = max_it; c.n0 = n0; c.dn = dn;
-    std::vector<bool> timing(G.count);
-    for (int p = 0; p < G.count; p++) {
-        vbnmf_engine *e = G.e[p];
-        timing[p] = e->timing;
-        e->timing = false;                                         // event pairs cannot follow launches queued ahead
-        e->ev_recorded = false; e->ev2_recorded = false;
-        hipLaunchKernelGGL(k_ctl_init, dim3(1), dim3(1), 0, e->stream, e->fold ? e->ctl2 : e->ctl, c);
-        e->fold_step = 0;
-        if (G.comm) {                                              // the reduced statistics of the loaded state
+    const LoopCtl c = vb_ctl(hyper, flags, tol, max_it, n0, dn);
+    RunScope S{G.e, G.count};
+    if (int rc = S.begin([&](int) { return c; })) return rc;
+    if (G.comm)                                                    // the reduced statistics of the loaded state
+        for (int p = 0; p < G.count; p++) {
+            vbnmf_engine *e = G.e[p];
             e->red_in = e->red_g;
             (void)hipMemcpyAsync(e->red_g, e->red, (size_t)e->red_count * sizeof(double), hipMemcpyDeviceToDevice, e->stream);
         }
-        volatile double *ho = e->h_out;
-        ho[5] = 0.0; ho[6] = 0.0; ho[7] = 0.0;
-        e->run_active = true;
-    }
-    auto cleanup = [&](int rc) {
-        if (e0->poisoned) {                                        // timed out: the streams may never drain -- leave at once
-            std::string msg = last_error_cstr();
-            for (int p = 0; p < G.count; p++) G.e[p]->poisoned = true;
-            return fail(rc, "%s", msg.c_str());
-        }
+    int rc = drive_loop(G.e, 1, true, max_it, e0->fold, [&](int) { return queue_vb_step(G, fudge, history != nullptr, max_it); });
+    rc = S.end(rc);
+    if (G.comm && !e0->poisoned)                                   // host-stepped calls read the reduced statistics from `red`
         for (int p = 0; p < G.count; p++) {
             vbnmf_engine *e = G.e[p];
-            (void)hipStreamSynchronize(e->stream);
-            if (e->cstream) (void)hipStreamSynchronize(e->cstream);
-            if (G.comm) {                                          // host-stepped calls read the reduced statistics from `red`
-                (void)hipMemcpy(e->red, e->red_g, (size_t)e->red_count * sizeof(double), hipMemcpyDeviceToDevice);
-                e->red_in = nullptr;
-            }
-            e->run_active = false; e->timing = timing[p];
-            e->stop_ptr = nullptr;
-            e->seq = 0.0; e->h_out[7] = 0.0;                       // the step path's sequence flag restarts
+            (void)hipMemcpy(e->red, e->red_g, (size_t)e->red_count * sizeof(double), hipMemcpyDeviceToDevice);
+            e->red_in = nullptr;
         }
-        return rc;
-    };
-    hipError_t he = hipGetLastError();
-    if (he != hipSuccess) return cleanup(fail(VBNMF_ERR_HIP, "loading the loop control block failed: %s", hipGetErrorString(he)));
-
-    int rc = drive_loop(e0, max_it, e0->fold, [&]() { return queue_vb_step(G, fudge, history != nullptr, max_it); });
-    if (rc) return cleanup(rc);
-    for (int p = 0; p < G.count; p++) {
-        he = hipStreamSynchronize(G.e[p]->stream);
-        if (he == hipSuccess && G.e[p]->cstream) he = hipStreamSynchronize(G.e[p]->cstream);
-        if (he != hipSuccess) return cleanup(fail(VBNMF_ERR_HIP, "hipStreamSynchronize failed: %s", hipGetErrorString(he)));
-    }
-    const double *ho = e0->h_out;                                  // written by the last live k_control
-    const int it = (int)ho[5];
-    for (int q = 0; q < 4; q++) hyper[q] = ho[8 + q];
-    if (it_out) *it_out = it;
-    if (lk0_out) *lk0_out = ho[12];
-    if (lkh_out) *lkh_out = ho[0];
-    if (reason_out) *reason_out = (int)ho[6];
-    if (history && it > 0) std::memcpy(history, e0->h_hist, (size_t)it * 9 * sizeof(double));
-    return cleanup(VBNMF_OK);
+    if (rc) return rc;
+    read_out(G.e, 1, it_out, lk0_out, lkh_out, reason_out, hyper, history, history_rows, 9);
+    return VBNMF_OK;
 }
 
 }  // namespace
@@ -1999,62 +2084,35 @@ int launch_update2_batch(vbnmf_engine *e, const Upd2Job *jobs, int B)
     return VBNMF_OK;
 }
 
-// Host side of a batch's device-driven loops (drive_loop's rule over all engines): steps queued in batches of eight, two batches
-// ahead of the device; batch b + 2 is queued when some engine has neither stopped nor fallen short of the last step of batch b.
-// `queue_batch` queues up to eight more steps and counts them in `queued`.  Every engine's result block is polled: [5] = steps done,
-// [6] = reason (raised after [5]), [7] = steps done (raised last).  Returns with e0->poisoned set when the wait timed out.
-template <class QueueBatch>
-int drive_batch_loop(vbnmf_engine **engs, int B, hipStream_t S, int max_it, const int &queued, QueueBatch &&queue_batch, const char *what)
+// The engines a batch run takes (vb: vbnmf_batch_run, else vbnmf_batch_ml_run): no null or repeated handle; unpartitioned, the
+// control step folded in (VB: the one-launch update form; ML: both tables of H-side partials), padded rank <= 16; one row width
+// on one matrix; a state set.  Their history buffers are made to hold `hist_doubles` (0: no history), the streams of all but
+// the first are idle on return.
+int batch_admit(vbnmf_engine **engs, int B, bool vb, size_t hist_doubles)
 {
     vbnmf_engine *e0 = engs[0];
-    if (int rc = queue_batch()) return rc;
-    if (int rc = queue_batch()) return rc;
-    const double limit = wait_timeout_s();
-    for (int bt = 0;; bt++) {
-        const int target = (int)std::min<int64_t>((int64_t)(bt + 1) * 8, max_it);
-        const auto t0 = std::chrono::steady_clock::now();
-        bool all_stopped = false;
-        for (long spins = 1;; spins++) {
-            bool reached = true;
-            all_stopped = true;
-            for (int b = 0; b < B; b++) {
-                volatile double *ho = engs[b]->h_out;
-                const bool stopped = ho[6] != 0.0;
-                all_stopped = all_stopped && stopped;
-                reached = reached && (stopped || (int)ho[7] >= target);
-            }
-            if (reached) break;
-            if ((spins & 0xFFFF) == 0) {
-                const double waited = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-                if (waited > limit) {
-                    e0->poisoned = true;
-                    return fail(VBNMF_ERR_HIP, "timed out after %.1f s (VBNMF_WAIT_TIMEOUT_S) waiting for step %d of %s (%d queued)", waited, target, what, queued);
-                }
-                hipError_t q = hipStreamQuery(S);
-                if (q != hipSuccess && q != hipErrorNotReady) return fail(VBNMF_ERR_HIP, "%s failed on the device: %s", what, hipGetErrorString(q));
-                if (q == hipSuccess) {                            // idle: everything queued has run; one more look, then a step is lost
-                    bool ok = true;
-                    const int expect = queued - (queued < max_it ? 1 : 0);      // (step t is reported by step t + 1's launch, the last by the closing ones)
-                    for (int b = 0; b < B; b++) { volatile double *ho = engs[b]->h_out; ok = ok && (ho[6] != 0.0 || (int)ho[7] >= std::min(target, expect)); }
-                    if (!ok) return fail(VBNMF_ERR_HIP, "the device went idle before the queued steps of %s finished", what);
-                }
-            }
-        }
-        if (all_stopped || target >= max_it) return VBNMF_OK;
-        if (int rc = queue_batch()) return rc;
+    if (!e0) return fail(VBNMF_ERR_BAD_ARG, "engine handle is NULL");
+    for (int b = 0; b < B; b++) {
+        vbnmf_engine *e = engs[b];
+        if (!e) return fail(VBNMF_ERR_BAD_ARG, "engine handle is NULL");
+        for (int q = 0; q < b; q++) if (engs[q] == e) return fail(VBNMF_ERR_BAD_ARG, "the same engine twice in a batch");
+        if (int rc = use_device(e)) return rc;
+        if (e->partitioned || e->comm || !e->fold || !(vb ? e->pair : e->bpH_alt != nullptr) || e->R > kBatchMaxPaddedRank)
+            return fail(VBNMF_ERR_STATE, "a batch takes unpartitioned engines %s and padded rank <= %d",
+                        vb ? "of the one-launch update form" : "with the control step folded in", kBatchMaxPaddedRank);
+        if (e->device != e0->device || e->n != e0->n || e->m != e0->m || e->R != e0->R || e->n_wg != e0->n_wg || e->ub != e0->ub ||
+            e->NT != e0->NT || e->wide != e0->wide || e->lds_bytes != e0->lds_bytes || e->A.n_slices != e0->A.n_slices ||
+            e->B.n_slices != e0->B.n_slices ||
+            (vb && (e->upd_stride4 != e0->upd_stride4 || e->upd_V != e0->upd_V || e->upd_ids_off != e0->upd_ids_off)))
+            return fail(VBNMF_ERR_STATE, "the engines of a batch must be of one row width on one matrix (same padded rank, layouts%s)",
+                        vb ? ", grids and update table" : " and grids");
+        if (vb && (!e->has_state || !e->stats_ready)) return fail(VBNMF_ERR_STATE, "batch run before set_state");
+        if (vb && e->step_pending) return fail(VBNMF_ERR_STATE, "batch run between step_local and step_finish");
+        if (!vb && !e->ml_ready) return fail(VBNMF_ERR_STATE, "batch ML run before ml_set_state");
+        if (hist_doubles) { if (int rc = ensure_history(e, hist_doubles)) return rc; }
     }
-}
-
-// the fold of step t (1-based) of engine e's run, as queue_vb_step builds it
-ControlFold batch_fold(const vbnmf_engine *e, int t, bool hist)
-{
-    ControlFold f{};
-    f.prev = e->ctl2 + ((t - 1) & 1); f.next = e->ctl2 + (t & 1);
-    f.epart = e->epart; f.nepart = 2 * (int64_t)e->n_wg;
-    f.lgx = e->lgx; f.n = (double)e->n; f.m_global = (double)e->m_global;
-    f.history = hist ? e->h_hist_dev : nullptr; f.out_host = e->h_out_dev;
-    f.do_control = t > 1 ? 1 : 0;
-    return f;
+    for (int b = 1; b < B; b++) HIPCHECK(hipStreamSynchronize(engs[b]->stream));      // (idle already: set_state ends with a synchronise)
+    return VBNMF_OK;
 }
 
 }  // namespace
@@ -2099,37 +2157,16 @@ int vbnmf_batch_run(vbnmf_engine **engs, int32_t count, double *hyper, double fu
     if (count < 1 || count > kBatchMax) return fail(VBNMF_ERR_BAD_ARG, "a batch holds 1 to %d engines", kBatchMax);
     if (max_it < 1 || dn < 1) return fail(VBNMF_ERR_BAD_ARG, "max_it and dn must be >= 1");
     if (history && history_rows < max_it) return fail(VBNMF_ERR_BAD_ARG, "history needs max_it rows of 9 doubles per engine");
-    vbnmf_engine *e0 = engs[0];
-    if (!e0) return fail(VBNMF_ERR_BAD_ARG, "engine handle is NULL");
     const int B = count;
-    for (int b = 0; b < B; b++) {
-        vbnmf_engine *e = engs[b];
-        if (!e) return fail(VBNMF_ERR_BAD_ARG, "engine handle is NULL");
-        for (int q = 0; q < b; q++) if (engs[q] == e) return fail(VBNMF_ERR_BAD_ARG, "the same engine twice in a batch");
-        if (int rc = use_device(e)) return rc;
-        if (e->partitioned || e->comm || !e->pair || !e->fold || e->R > kBatchMaxPaddedRank)
-            return fail(VBNMF_ERR_STATE, "a batch takes unpartitioned engines of the one-launch update form and padded rank <= %d", kBatchMaxPaddedRank);
-        if (e->device != e0->device || e->n != e0->n || e->m != e0->m || e->R != e0->R || e->n_wg != e0->n_wg || e->ub != e0->ub ||
-            e->NT != e0->NT || e->wide != e0->wide || e->lds_bytes != e0->lds_bytes || e->upd_stride4 != e0->upd_stride4 || e->upd_V != e0->upd_V ||
-            e->upd_ids_off != e0->upd_ids_off || e->A.n_slices != e0->A.n_slices || e->B.n_slices != e0->B.n_slices)
-            return fail(VBNMF_ERR_STATE, "the engines of a batch must be of one row width on one matrix (same padded rank, layouts, grids and update table)");
-        if (!e->has_state || !e->stats_ready) return fail(VBNMF_ERR_STATE, "batch run before set_state");
-        if (e->step_pending) return fail(VBNMF_ERR_STATE, "batch run between step_local and step_finish");
-        if (history) { if (int rc = ensure_history(e, (size_t)max_it * 9)) return rc; }
-    }
-    hipStream_t S = e0->stream;
-    for (int b = 1; b < B; b++) HIPCHECK(hipStreamSynchronize(engs[b]->stream));      // (idle already: set_state ends with a synchronise)
+    if (int rc = batch_admit(engs, B, true, history ? (size_t)max_it * 9 : 0)) return rc;
+    vbnmf_engine *e0 = engs[0];
 
     // ---- the jobs: the update's of step 1 (nothing to evaluate yet), of the odd and of the even steps; the sweep's by parity
     const bool hist = history != nullptr;
     std::vector<Upd2Job> ju((size_t)3 * B);
     std::vector<SweepSide> js((size_t)2 * 2 * B);
-    std::vector<hipStream_t> own(B);
-    std::vector<bool> timing(B);
     for (int b = 0; b < B; b++) {
         vbnmf_engine *e = engs[b];
-        own[b] = e->stream; timing[b] = e->timing;
-        e->timing = false; e->ev_recorded = false; e->ev2_recorded = false;
         double *Wt[2] = {e->bpW, e->bpW_alt}, *Ht[2] = {e->bpH, e->bpH_alt};          // [0]: the latest tables as the run starts
         for (int v = 0; v < 3; v++) {
             const int t = v == 0 ? 1 : (v == 1 ? 3 : 2);
@@ -2140,54 +2177,27 @@ int vbnmf_batch_run(vbnmf_engine **engs, int32_t count, double *hyper, double fu
             J.H.bp_prev = Ht[(t - 1) & 1]; J.H.bp = Ht[t & 1];
             J.T = UpdTable{e->upd_tab, e->upd_stride4, e->upd_V, e->upd_ids_off};
             J.r = e->r; J.nb = e->ub; J.ncs = e->n_wg; J.csum = e->csum; J.fudge = fudge;
-            J.fold = batch_fold(e, t, hist);
+            J.fold = vb_fold(e, t, hist);
         }
-        e->run_active = true;
         for (int par = 0; par < 2; par++) {                       // the sweep of step t reads the stop flag that step's update left
-            e->stop_ptr = &(e->ctl2 + par)->stop;
-            js[((size_t)par * B + b) * 2] = sweep_side_args(e, e->A, true, e->epart);
-            js[((size_t)par * B + b) * 2 + 1] = sweep_side_args(e, e->B, false, e->epart + e->n_wg);
+            SweepSide *s = &js[((size_t)par * B + b) * 2];
+            s[0] = sweep_side_args(e, e->A, true, e->epart);
+            s[1] = sweep_side_args(e, e->B, false, e->epart + e->n_wg);
+            s[0].stop = s[1].stop = &(e->ctl2 + par)->stop;
         }
-        e->stop_ptr = nullptr;
     }
     Upd2Job *d_ju = nullptr;
     SweepSide *d_js = nullptr;
-    auto restore = [&](int rc) {
-        for (int b = 0; b < B; b++) {
-            vbnmf_engine *e = engs[b];
-            e->stream = own[b];
-            e->run_active = false; e->timing = timing[b]; e->stop_ptr = nullptr;
-            e->seq = 0.0; e->h_out[7] = 0.0;
-        }
-        dev_free(d_ju); dev_free(d_js);
-        return rc;
-    };
-    if (int rc = dev_upload(&d_ju, ju)) return restore(rc);
-    if (int rc = dev_upload(&d_js, js)) return restore(rc);
-    for (int b = 0; b < B; b++) {
-        vbnmf_engine *e = engs[b];
-        LoopCtl c{};
-        for (int q = 0; q < 4; q++) { c.hyper[q] = hyper[(size_t)b * 4 + q]; c.flags[q] = flags[q] ? 1 : 0; }
-        c.lk0 = 0.0;
-        c.tol = tol; c.max_it = max_it; c.n0 = n0; c.dn = dn;
-        hipLaunchKernelGGL(k_ctl_init, dim3(1), dim3(1), 0, S, e->ctl2, c);
-        e->fold_step = 0;
-        volatile double *ho = e->h_out;
-        ho[5] = 0.0; ho[6] = 0.0; ho[7] = 0.0;
-        e->stream = S;                                           // every launch of the run goes on the first engine's stream
-    }
-    {
-        hipError_t he = hipGetLastError();
-        if (he != hipSuccess) { (void)hipStreamSynchronize(S); return restore(fail(VBNMF_ERR_HIP, "loading the loop control blocks failed: %s", hipGetErrorString(he))); }
-    }
+    int rc = dev_upload(&d_ju, ju);
+    if (!rc) rc = dev_upload(&d_js, js);
+    if (rc) { dev_free(d_ju); dev_free(d_js); return rc; }
 
-    // ---- the loop: steps queued in batches of eight, two batches ahead of the device (drive_loop's rule, over all engines)
-    int queued = 0;
-    auto queue_step = [&]() -> int {
-        const int t = queued + 1;
+    RunScope S{engs, B, e0->stream};                              // every launch of the run goes on the first engine's stream
+    rc = S.begin([&](int b) { return vb_ctl(hyper + (size_t)b * 4, flags, tol, max_it, n0, dn); });
+    if (!rc) rc = drive_loop(engs, B, false, max_it, true, [&](int t) -> int {
         const int v = t == 1 ? 0 : ((t & 1) ? 1 : 2);
-        if (int rc = launch_update2_batch(e0, d_ju + (size_t)v * B, B)) return rc;
-        if (int rc = launch_sweep_batch(e0, d_js + (size_t)(t & 1) * B * 2, B)) return rc;
+        if (int q = launch_update2_batch(e0, d_ju + (size_t)v * B, B)) return q;
+        if (int q = launch_sweep_batch(e0, d_js + (size_t)(t & 1) * B * 2, B)) return q;
         for (int b = 0; b < B; b++) {
             vbnmf_engine *e = engs[b];
             std::swap(e->bpW, e->bpW_alt); std::swap(e->bpH, e->bpH_alt);      // (e->bpW / e->bpH name the latest tables, as launch_update2 keeps them)
@@ -2196,42 +2206,19 @@ int vbnmf_batch_run(vbnmf_engine **engs, int32_t count, double *hyper, double fu
         if (t == max_it) {                                       // behind the last step: every engine's control step alone
             for (int b = 0; b < B; b++) {
                 vbnmf_engine *e = engs[b];
-                ControlFold g = batch_fold(e, t + 1, hist);
-                g.bpW_prev = e->bpW;
-                g.do_control = 1; g.control_only = 1;
-                if (int rc = launch_update(e, true, 0, 0, fudge, nullptr, &g)) return rc;
+                ControlFold g = vb_fold(e, t + 1, hist);
+                g.bpW_prev = e->bpW; g.control_only = 1;
+                if (int q = launch_update(e, true, 0, 0, fudge, nullptr, &g)) return q;
             }
         }
-        queued++;
         return VBNMF_OK;
-    };
-    auto queue_batch = [&]() -> int {
-        for (int q = 0; q < 8 && queued < max_it; q++) if (int rc = queue_step()) return rc;
-        return VBNMF_OK;
-    };
-    auto fail_out = [&](int rc) {
-        std::string msg = last_error_cstr();
-        if (e0->poisoned) { for (int b = 0; b < B; b++) { engs[b]->poisoned = true; engs[b]->stream = own[b]; } return fail(rc, "%s", msg.c_str()); }
-        (void)hipStreamSynchronize(S);
-        restore(rc);
-        return fail(rc, "%s", msg.c_str());
-    };
-    if (int rc = drive_batch_loop(engs, B, S, max_it, queued, queue_batch, "a batch's device-driven loops")) return fail_out(rc);
-    {
-        hipError_t he = hipStreamSynchronize(S);
-        if (he != hipSuccess) return restore(fail(VBNMF_ERR_HIP, "hipStreamSynchronize failed: %s", hipGetErrorString(he)));
-    }
-    for (int b = 0; b < B; b++) {
-        const double *ho = engs[b]->h_out;
-        const int it = (int)ho[5];
-        for (int q = 0; q < 4; q++) hyper[(size_t)b * 4 + q] = ho[8 + q];
-        if (it_out) it_out[b] = it;
-        if (lk0_out) lk0_out[b] = ho[12];
-        if (lkh_out) lkh_out[b] = ho[0];
-        if (reason_out) reason_out[b] = (int)ho[6];
-        if (history && it > 0) std::memcpy(history + (size_t)b * (size_t)history_rows * 9, engs[b]->h_hist, (size_t)it * 9 * sizeof(double));
-    }
-    return restore(VBNMF_OK);
+    });
+    rc = S.end(rc);
+    if (e0->poisoned) return rc;                                   // (the jobs may still be read)
+    dev_free(d_ju); dev_free(d_js);
+    if (rc) return rc;
+    read_out(engs, B, it_out, lk0_out, lkh_out, reason_out, hyper, history, history_rows, 9);
+    return VBNMF_OK;
 }
 
 }  // extern "C"
@@ -2276,18 +2263,6 @@ int launch_ml_update_batch(vbnmf_engine *e, const MlUpdJob *jobs, int B)
     return VBNMF_OK;
 }
 
-MlFold batch_ml_fold(const vbnmf_engine *e, int t, bool hist, const double *bpH_prev)
-{
-    MlFold f{};
-    f.prev = e->ctl2 + ((t - 1) & 1); f.next = e->ctl2 + (t & 1);
-    f.bpH_prev = bpH_prev;
-    f.epart = e->epart + e->n_wg; f.nepart = (int64_t)e->n_wg;
-    f.xlx = e->xlx; f.n = (double)e->n; f.m = (double)e->m;
-    f.history = hist ? e->h_hist_dev : nullptr; f.out_host = e->h_out_dev;
-    f.do_control = t > 1 ? 1 : 0;
-    return f;
-}
-
 }  // namespace
 
 extern "C" {
@@ -2304,37 +2279,17 @@ int vbnmf_batch_ml_run(vbnmf_engine **engs, int32_t count, int32_t prior, double
     if (count < 1 || count > kBatchMax) return fail(VBNMF_ERR_BAD_ARG, "a batch holds 1 to %d engines", kBatchMax);
     if (max_it < 1) return fail(VBNMF_ERR_BAD_ARG, "max_it must be >= 1");
     if (history && history_rows < max_it) return fail(VBNMF_ERR_BAD_ARG, "history needs max_it doubles per engine");
-    vbnmf_engine *e0 = engs[0];
-    if (!e0) return fail(VBNMF_ERR_BAD_ARG, "engine handle is NULL");
     const int B = count;
+    if (int rc = batch_admit(engs, B, false, history ? (size_t)max_it : 0)) return rc;
+    vbnmf_engine *e0 = engs[0];
     const double eps = 2.220446049250313e-16;
-    for (int b = 0; b < B; b++) {
-        vbnmf_engine *e = engs[b];
-        if (!e) return fail(VBNMF_ERR_BAD_ARG, "engine handle is NULL");
-        for (int q = 0; q < b; q++) if (engs[q] == e) return fail(VBNMF_ERR_BAD_ARG, "the same engine twice in a batch");
-        if (int rc = use_device(e)) return rc;
-        if (e->partitioned || e->comm || !e->fold || !e->bpH_alt || e->R > kBatchMaxPaddedRank)
-            return fail(VBNMF_ERR_STATE, "a batch takes unpartitioned engines with the control step folded in and padded rank <= %d", kBatchMaxPaddedRank);
-        if (e->device != e0->device || e->n != e0->n || e->m != e0->m || e->R != e0->R || e->n_wg != e0->n_wg || e->ub != e0->ub ||
-            e->NT != e0->NT || e->wide != e0->wide || e->lds_bytes != e0->lds_bytes || e->A.n_slices != e0->A.n_slices || e->B.n_slices != e0->B.n_slices)
-            return fail(VBNMF_ERR_STATE, "the engines of a batch must be of one row width on one matrix (same padded rank, layouts and grids)");
-        if (!e->ml_ready) return fail(VBNMF_ERR_STATE, "batch ML run before ml_set_state");
-        if (history) { if (int rc = ensure_history(e, (size_t)max_it)) return rc; }
-    }
-    hipStream_t S = e0->stream;
-    for (int b = 1; b < B; b++) HIPCHECK(hipStreamSynchronize(engs[b]->stream));
 
     const bool hist = history != nullptr;
-    static const int stage_allowed = [] { const char *v = getenv("VBNMF_NO_STAGE_IDS"); return (v && v[0] == '1') ? 0 : 1; }();
     // jobs: the H update's of step 1, of the odd and of the even steps; the W update's and the two sweeps' by parity
     std::vector<MlUpdJob> jh((size_t)3 * B), jw((size_t)2 * B);
     std::vector<SweepSide> jg((size_t)2 * B), jc((size_t)2 * B);
-    std::vector<hipStream_t> own(B);
-    std::vector<bool> timing(B);
     for (int b = 0; b < B; b++) {
         vbnmf_engine *e = engs[b];
-        own[b] = e->stream; timing[b] = e->timing;
-        e->timing = false; e->ev_recorded = false; e->ev2_recorded = false;
         double *Ht[2] = {e->bpH, e->bpH_alt};                                    // [0]: the latest table as the run starts
         for (int v = 0; v < 3; v++) {
             const int t = v == 0 ? 1 : (v == 1 ? 3 : 2);
@@ -2343,10 +2298,9 @@ int vbnmf_batch_ml_run(vbnmf_engine **engs, int32_t count, int32_t prior, double
             J.other_bp = e->bpW; J.f = e->lh; J.bp = Ht[t & 1]; J.stop = nullptr;
             J.ga = gamma_a; J.gb = gamma_b; J.eps = eps;
             J.r = e->r; J.other_nb = e->ub; J.prior = prior;
-            J.stage_ids = stage_allowed && e->B.n_tasks >= (int64_t)256 * e->ub ? 1 : 0;
-            J.fold = batch_ml_fold(e, t, hist, Ht[(t - 1) & 1]);
+            J.stage_ids = stage_ids(e->B, e->ub);
+            J.fold = ml_fold(e, t, hist, Ht[(t - 1) & 1]);
         }
-        e->run_active = true;
         for (int par = 0; par < 2; par++) {                                      // step t of parity par = t & 1
             const int32_t *stop = &(e->ctl2 + par)->stop;                        // what that step's H update left
             MlUpdJob &J = jw[(size_t)par * B + b];
@@ -2354,97 +2308,50 @@ int vbnmf_batch_ml_run(vbnmf_engine **engs, int32_t count, int32_t prior, double
             J.other_bp = Ht[par]; J.f = e->lw; J.bp = e->bpW; J.stop = stop;
             J.ga = gamma_a; J.gb = gamma_b; J.eps = eps;
             J.r = e->r; J.other_nb = e->ub; J.prior = prior;
-            J.stage_ids = stage_allowed && e->A.n_tasks >= (int64_t)256 * e->ub ? 1 : 0;
+            J.stage_ids = stage_ids(e->A, e->ub);
             J.fold = MlFold{};
-            e->stop_ptr = stop;
             SweepSide g = sweep_side_args(e, e->A, true, e->epart);
             g.logterm = 0;
             SweepSide c = sweep_side_args(e, e->B, false, e->epart + e->n_wg);
             c.logterm = 1;
+            g.stop = c.stop = stop;
             jg[(size_t)par * B + b] = g; jc[(size_t)par * B + b] = c;
         }
-        e->stop_ptr = nullptr;
     }
     MlUpdJob *d_jh = nullptr, *d_jw = nullptr;
     SweepSide *d_jg = nullptr, *d_jc = nullptr;
-    auto restore = [&](int rc) {
-        for (int b = 0; b < B; b++) {
-            vbnmf_engine *e = engs[b];
-            e->stream = own[b];
-            e->run_active = false; e->timing = timing[b]; e->stop_ptr = nullptr;
-            e->seq = 0.0; e->h_out[7] = 0.0;
-        }
-        dev_free(d_jh); dev_free(d_jw); dev_free(d_jg); dev_free(d_jc);
-        return rc;
-    };
-    if (int rc = dev_upload(&d_jh, jh)) return restore(rc);
-    if (int rc = dev_upload(&d_jw, jw)) return restore(rc);
-    if (int rc = dev_upload(&d_jg, jg)) return restore(rc);
-    if (int rc = dev_upload(&d_jc, jc)) return restore(rc);
-    for (int b = 0; b < B; b++) {
-        vbnmf_engine *e = engs[b];
-        LoopCtl c{};
-        c.lk0 = -INFINITY;                                                        // lkold <- -Inf (R/factorize.R:193)
-        c.tol = tol; c.max_it = max_it;
-        hipLaunchKernelGGL(k_ctl_init, dim3(1), dim3(1), 0, S, e->ctl2, c);
-        e->fold_step = 0;
-        volatile double *ho = e->h_out;
-        ho[5] = 0.0; ho[6] = 0.0; ho[7] = 0.0;
-        e->stream = S;
-    }
-    {
-        hipError_t he = hipGetLastError();
-        if (he != hipSuccess) { (void)hipStreamSynchronize(S); return restore(fail(VBNMF_ERR_HIP, "loading the loop control blocks failed: %s", hipGetErrorString(he))); }
-    }
-    int queued = 0;
-    auto queue_step = [&]() -> int {
-        const int t = queued + 1;
+    auto free_jobs = [&] { dev_free(d_jh); dev_free(d_jw); dev_free(d_jg); dev_free(d_jc); };
+    int rc = dev_upload(&d_jh, jh);
+    if (!rc) rc = dev_upload(&d_jw, jw);
+    if (!rc) rc = dev_upload(&d_jg, jg);
+    if (!rc) rc = dev_upload(&d_jc, jc);
+    if (rc) { free_jobs(); return rc; }
+
+    RunScope S{engs, B, e0->stream};
+    rc = S.begin([&](int) { return ml_ctl(tol, max_it); });
+    if (!rc) rc = drive_loop(engs, B, false, max_it, true, [&](int t) -> int {
         const int v = t == 1 ? 0 : ((t & 1) ? 1 : 2), par = t & 1;
-        if (int rc = launch_ml_update_batch(e0, d_jh + (size_t)v * B, B)) return rc;           // H <- , the previous step's control folded in
+        if (int q = launch_ml_update_batch(e0, d_jh + (size_t)v * B, B)) return q;           // H <- , the previous step's control folded in
         for (int b = 0; b < B; b++) { vbnmf_engine *e = engs[b]; std::swap(e->bpH, e->bpH_alt); e->fold_step = t; }
-        if (int rc = launch_sweep1_batch(e0, d_jg + (size_t)par * B, B, false)) return rc;     // gene side on (w, h_new)
-        if (int rc = launch_ml_update_batch(e0, d_jw + (size_t)par * B, B)) return rc;         // W <-
-        if (int rc = launch_sweep1_batch(e0, d_jc + (size_t)par * B, B, true)) return rc;      // cell side on (h_new, w_new): next step's statistics + sum x log(wh)
+        if (int q = launch_sweep1_batch(e0, d_jg + (size_t)par * B, B, false)) return q;     // gene side on (w, h_new)
+        if (int q = launch_ml_update_batch(e0, d_jw + (size_t)par * B, B)) return q;         // W <-
+        if (int q = launch_sweep1_batch(e0, d_jc + (size_t)par * B, B, true)) return q;      // cell side on (h_new, w_new): next step's statistics + sum x log(wh)
         if (t == max_it) {
             for (int b = 0; b < B; b++) {
                 vbnmf_engine *e = engs[b];
-                MlFold g = batch_ml_fold(e, t + 1, hist, e->bpH);
-                g.do_control = 1; g.control_only = 1;
-                if (int rc = launch_ml_update(e, false, prior, gamma_a, gamma_b, eps, &g)) return rc;
+                MlFold g = ml_fold(e, t + 1, hist, e->bpH);
+                g.control_only = 1;
+                if (int q = launch_ml_update(e, false, prior, gamma_a, gamma_b, eps, &g)) return q;
             }
         }
-        queued++;
         return VBNMF_OK;
-    };
-    auto queue_batch = [&]() -> int {
-        for (int q = 0; q < 8 && queued < max_it; q++) if (int rc = queue_step()) return rc;
-        return VBNMF_OK;
-    };
-    auto fail_out = [&](int rc) {
-        std::string msg = last_error_cstr();
-        if (e0->poisoned) { for (int b = 0; b < B; b++) { engs[b]->poisoned = true; engs[b]->stream = own[b]; } return fail(rc, "%s", msg.c_str()); }
-        (void)hipStreamSynchronize(S);
-        restore(rc);
-        return fail(rc, "%s", msg.c_str());
-    };
-    if (int rc = drive_batch_loop(engs, B, S, max_it, queued, queue_batch, "a batch's ML loops")) return fail_out(rc);
-    {
-        hipError_t he = hipStreamSynchronize(S);
-        if (he != hipSuccess) return restore(fail(VBNMF_ERR_HIP, "hipStreamSynchronize failed: %s", hipGetErrorString(he)));
-    }
-    for (int b = 0; b < B; b++) {
-        vbnmf_engine *e = engs[b];
-        const int it = (int)e->h_out[5];
-        if (it_out) it_out[b] = it;
-        if (lk_out) lk_out[b] = e->h_out[0];
-        if (reason_out) reason_out[b] = (int)e->h_out[6];
-        if (history && it > 0) std::memcpy(history + (size_t)b * (size_t)history_rows, e->h_hist, (size_t)it * sizeof(double));
-    }
-    std::vector<double> lk_last(B);
-    for (int b = 0; b < B; b++) lk_last[b] = engs[b]->h_out[0];
-    const int rc = restore(VBNMF_OK);
-    for (int b = 0; b < B; b++) engs[b]->h_out[0] = lk_last[b];                   // ml_likelihood() keeps answering for the pair held now
-    return rc;
+    });
+    rc = S.end(rc);
+    if (e0->poisoned) return rc;                                   // (the jobs may still be read)
+    free_jobs();
+    if (rc) return rc;
+    read_out(engs, B, it_out, nullptr, lk_out, reason_out, nullptr, history, history_rows, 1);
+    return VBNMF_OK;
 }
 
 // ---------------------------------------------------------------- communicators (comm.h)
@@ -2752,53 +2659,26 @@ int vbnmf_engine_ml_run(vbnmf_engine *e, int32_t prior, double gamma_a, double g
     if (history && history_rows < max_it) return fail(VBNMF_ERR_BAD_ARG, "history needs max_it doubles");
     if (int rc = use_device(e)) return rc;
     const double eps = 2.220446049250313e-16;
-
-    LoopCtl c{};
-    c.lk0 = -INFINITY;                                             // lkold <- -Inf (:193)
-    c.tol = tol; c.max_it = max_it;
     if (history) { if (int rc = ensure_history(e, (size_t)max_it)) return rc; }
-    hipLaunchKernelGGL(k_ctl_init, dim3(1), dim3(1), 0, e->stream, e->fold ? e->ctl2 : e->ctl, c);
-    e->fold_step = 0;
-    hipError_t he = hipGetLastError();
-    if (he != hipSuccess) return fail(VBNMF_ERR_HIP, "loading the loop control block failed: %s", hipGetErrorString(he));
-    volatile double *ho = e->h_out;
-    ho[5] = 0.0; ho[6] = 0.0; ho[7] = 0.0;
-    e->run_active = true;
-    const bool timing = e->timing;
-    e->timing = false;                                             // event pairs cannot follow launches queued ahead
-    e->ev_recorded = false; e->ev2_recorded = false;
-    auto done_with = [&](int rc) {
-        if (e->poisoned) return rc;                                 // timed out: the stream may never drain
-        (void)hipStreamSynchronize(e->stream);
-        e->timing = timing; e->run_active = false;
-        e->stop_ptr = nullptr;
-        e->seq = 0.0; e->h_out[7] = 0.0;                            // the step path's sequence flag restarts
-        return rc;
-    };
-    double *hist_dev = history ? e->h_hist_dev : nullptr;
-    int rc = drive_loop(e, max_it, e->fold, [&]() -> int {
+
+    const bool hist = history != nullptr;
+    RunScope S{&e, 1};
+    int rc = S.begin([&](int) { return ml_ctl(tol, max_it); });
+    if (!rc) rc = drive_loop(&e, 1, true, max_it, e->fold, [&](int) -> int {
         if (e->fold) {
             // k_ml_update(H, with the control step of the PREVIOUS cell-side sweep folded in)  sweep  k_ml_update(W)  sweep ;
             // behind the last step of the run the control step alone (mlnmf.h: MlFold)
             const int t = ++e->fold_step;
-            MlFold f{};
-            f.prev = e->ctl2 + ((t - 1) & 1); f.next = e->ctl2 + (t & 1);
-            f.bpH_prev = e->bpH;
+            MlFold f = ml_fold(e, t, hist, e->bpH);
             std::swap(e->bpH, e->bpH_alt);                          // this step's H-side partials go to the other table
-            f.epart = e->epart + e->n_wg; f.nepart = (int64_t)e->n_wg;
-            f.xlx = e->xlx; f.n = (double)e->n; f.m = (double)e->m;
-            f.history = hist_dev; f.out_host = e->h_out_dev;
-            f.do_control = t > 1 ? 1 : 0;
             int q = launch_ml_update(e, false, prior, gamma_a, gamma_b, eps, &f);
             e->stop_ptr = &f.next->stop;
             if (!q) q = launch_sweep1(e, true);
             if (!q) q = launch_ml_update(e, true, prior, gamma_a, gamma_b, eps);
             if (!q) q = launch_sweep1(e, false);
             if (!q && t == max_it) {
-                MlFold g = f;
-                g.prev = f.next; g.next = e->ctl2 + ((t + 1) & 1);
-                g.bpH_prev = e->bpH;
-                g.do_control = 1; g.control_only = 1;
+                MlFold g = ml_fold(e, t + 1, hist, e->bpH);
+                g.control_only = 1;
                 q = launch_ml_update(e, false, prior, gamma_a, gamma_b, eps, &g);
             }
             return q;
@@ -2809,7 +2689,7 @@ int vbnmf_engine_ml_run(vbnmf_engine *e, int32_t prior, double gamma_a, double g
         if (!q) q = launch_sweep1(e, false);
         if (q) return q;
         switch (e->R) {
-#define X(RR) case RR: hipLaunchKernelGGL((k_ml_control<RR>), dim3(1), dim3(1024), 0, e->stream, e->bpW, e->bpH, e->ub, e->epart + e->n_wg, (int64_t)e->n_wg, e->xlx, e->r, (double)e->n, (double)e->m, e->ctl, hist_dev, e->h_out_dev); break;
+#define X(RR) case RR: hipLaunchKernelGGL((k_ml_control<RR>), dim3(1), dim3(1024), 0, e->stream, e->bpW, e->bpH, e->ub, e->epart + e->n_wg, (int64_t)e->n_wg, e->xlx, e->r, (double)e->n, (double)e->m, e->ctl, hist ? e->h_hist_dev : nullptr, e->h_out_dev); break;
             VBNMF_FOR_EACH_R(X)
 #undef X
             default: return fail(VBNMF_ERR_BAD_ARG, "unsupported padded rank %d", e->R);
@@ -2818,18 +2698,9 @@ int vbnmf_engine_ml_run(vbnmf_engine *e, int32_t prior, double gamma_a, double g
         if (le != hipSuccess) return fail(VBNMF_ERR_HIP, "k_ml_control launch failed: %s", hipGetErrorString(le));
         return VBNMF_OK;
     });
-    if (rc) return done_with(rc);
-    he = hipStreamSynchronize(e->stream);
-    if (he != hipSuccess) return done_with(fail(VBNMF_ERR_HIP, "hipStreamSynchronize failed: %s", hipGetErrorString(he)));
-    const int it = (int)e->h_out[5];
-    const double lk_last = e->h_out[0];
-    if (it_out) *it_out = it;
-    if (lk_out) *lk_out = lk_last;
-    if (reason_out) *reason_out = (int)e->h_out[6];
-    if (history && it > 0) std::memcpy(history, e->h_hist, (size_t)it * sizeof(double));
-    rc = done_with(VBNMF_OK);
-    e->h_out[0] = lk_last;                                          // ml_likelihood() keeps answering for the pair held now
-    return rc;
+    if ((rc = S.end(rc))) return rc;
+    read_out(&e, 1, it_out, nullptr, lk_out, reason_out, nullptr, history, history_rows, 1);
+    return VBNMF_OK;
 }
 
 int vbnmf_engine_ml_get_state(vbnmf_engine *e, double *w, double *h)

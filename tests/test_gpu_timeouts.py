@@ -63,16 +63,28 @@ def test_host_stepped_wait_times_out_with_the_last_completed_step(short_limit):
 
 
 def test_device_driven_loop_times_out_instead_of_spinning(short_limit):
+    """The single engine's loop and a one-engine batch (vbnmf_batch_run) share the poll loop and its timeout path; after
+    the batch's timeout the engine refuses every further call at once."""
+    import ccfindr_amd as C
     from ccfindr_amd import _native as N
-    M, eng = _engine(4)
-    N.check(N.load().vbnmf_test_stream_sleep(eng._h, 3.0))
-    t0 = time.perf_counter()
-    with pytest.raises(N.VBNMFError) as ei:
-        eng.run(HY, Itmax=40, Tol=0.0, flags=(False,) * 4)
-    waited = time.perf_counter() - t0
-    assert ei.value.code == N.ERR_HIP
-    assert "timed out" in str(ei.value) and "device-driven loop" in str(ei.value)
-    assert 0.9 < waited < 2.5, waited
-    time.sleep(3.0)
-    eng.close()
-    M.close()
+    for loop in ("run", "run_batch"):
+        M, eng = _engine(4)
+        N.check(N.load().vbnmf_test_stream_sleep(eng._h, 3.0))
+        t0 = time.perf_counter()
+        with pytest.raises(N.VBNMFError) as ei:
+            if loop == "run":
+                eng.run(HY, Itmax=40, Tol=0.0, flags=(False,) * 4)
+            else:
+                C.run_batch([eng], [HY], Itmax=40, Tol=0.0, flags=(False,) * 4)
+        waited = time.perf_counter() - t0
+        assert ei.value.code == N.ERR_HIP
+        assert "timed out" in str(ei.value) and "device-driven loop" in str(ei.value)
+        assert 0.9 < waited < 2.5, waited
+        if loop == "run_batch":
+            for call in (lambda: C.run_batch([eng], [HY], Itmax=3), lambda: eng.run(HY, Itmax=3)):
+                with pytest.raises(N.VBNMFError) as e2:
+                    call()
+                assert e2.value.code == N.ERR_STATE and "timed out earlier" in str(e2.value)
+        time.sleep(3.0)
+        eng.close()
+        M.close()
