@@ -74,6 +74,7 @@ def reconstruct(view):
                 assert not val.any() and not idx.any()
                 lens.append(0)
                 ones.append(0)
+                ones12.append(0)
                 continue
             ntask += 1
             live = val != 0
@@ -91,16 +92,22 @@ def reconstruct(view):
             lens.append(n_live)
             if view["wide"]:
                 ones.append(0)
+                ones12.append(0)
             else:
-                is1 = val[:n_live] == 1.0                          # a task's ones come first, its other entries after them
-                n1 = int(is1.sum())
-                assert is1[:n1].all()
+                # a task's ones come first, then its twos, then its other entries
+                is1, is2 = val[:n_live] == 1.0, val[:n_live] == 2.0
+                n1, n2 = int(is1.sum()), int(is2.sum())
+                assert is1[:n1].all() and is2[n1:n1 + n2].all(), (s, lane, val[:n_live].tolist())
                 ones.append(n1)
+                ones12.append(n1 + n2)
         padded = [(q + 3) // 4 for q in lens]
         assert padded == sorted(padded, reverse=True)          # longest (padded) task first: width = first lane
         assert (w - lens[0]) < 4
         fast = int(view["slice_fast"][s])
         assert fast % 8 == 0 and 0 <= fast <= min(ones) and (view["wide"] == 0 or fast == 0)
+        # the stretch of ones or twos: whole 8-entry trips, at least the stretch of ones, within every lane's ones and twos
+        fast2 = int(view["slice_fast2"][s])
+        assert fast2 % 8 == 0 and fast <= fast2 <= min(ones12), (s, fast, fast2, min(ones12))
     assert ntask == view["n_tasks"]
     multi = nslot > 1
     assert (npart[multi] <= 1).all() and (not multi.any() or not view["wide"])      # no entry stored twice
