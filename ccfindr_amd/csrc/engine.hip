@@ -21,11 +21,15 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <exception>
 #include <memory>
 #include <new>
 #include <queue>
 #include <string>
+#include <system_error>
 #include <thread>
+#include <type_traits>
+#include <utility>
 
 #include "common.h"
 #include "comm.h"
@@ -404,17 +408,36 @@ int upload_side(const Layout &L, int R, int device, const vbnmf_matrix *X, Devic
     return VBNMF_OK;
 }
 
-SweepSide sweep_side_args(const vbnmf_engine *e, const DeviceSide &S, bool gene_side, double *epart)
+// One side of the factorisation as the launch functions see it: the gene side (W; lanes own genes) or the cell side (H).
+struct SideView {
+    const DeviceSide &S;
+    int64_t nmaj;                     // the side's majors: genes / this engine's cells
+    double *l, *ll, *e, *d;           // its state arrays
+    double *other_l;                  // the other side's factor (what its sweep gathers)
+    double *bp, *other_bp;            // block partials of its update and of the other side's
+    double *epart;                    // its half of the evidence partials
+    int idx;                          // 0: gene side, 1: cell side
+};
+
+SideView side_view(const vbnmf_engine *e, bool gene_side)
 {
+    if (gene_side) return {e->A, e->n, e->lw, e->llw, e->ew, e->dw, e->lh, e->bpW, e->bpH, e->epart, 0};
+    return {e->B, e->m, e->lh, e->llh, e->eh, e->dh, e->lw, e->bpH, e->bpW, e->epart + e->n_wg, 1};
+}
+
+SweepSide sweep_side_args(const vbnmf_engine *e, bool gene_side)
+{
+    const SideView v = side_view(e, gene_side);
+    const DeviceSide &S = v.S;
     SweepSide P;
     P.packed = S.packed; P.widx = S.widx; P.wval = S.wval;
     P.task_major = S.task_major; P.slice_width = S.slice_width; P.slice_off = S.slice_off; P.slice_fast = S.slice_fast;
     P.seg_block = S.seg_block; P.wg_seg0 = S.wg_seg0; P.seg_ptr = S.seg_ptr;
-    P.F = gene_side ? e->lw : e->lh;
-    P.llF = gene_side ? e->llw : e->llh;
-    P.G = gene_side ? e->lh : e->lw;
-    P.part = S.part; P.epart = epart;
-    P.csl = gene_side ? e->csl : nullptr; P.csum = gene_side ? e->csum : nullptr;
+    P.F = v.l;
+    P.llF = v.ll;
+    P.G = v.other_l;
+    P.part = S.part; P.epart = v.epart;
+    P.csl = gene_side ? e->csl : nullptr; P.csum = gene_side ? e->csum : nullptr;      // (the pair form's column sums: gene side only)
     P.n_minor = (int32_t)S.n_minor; P.block_start = S.block_start;
     P.row_slots = S.row_slots;
     {
@@ -431,7 +454,7 @@ SweepSide sweep_side_args(const vbnmf_engine *e, const DeviceSide &S, bool gene_
         const int third = (e->NT / 64) / 3;
         int k = gene_side ? (e->R >= 8 ? third : 0) : (e->R >= 16 ? third : 0);
         if (pe >= 0) k = pe;
-        if (pes[gene_side ? 0 : 1] >= 0) k = pes[gene_side ? 0 : 1];
+        if (pes[v.idx] >= 0) k = pes[v.idx];
         P.pull_ends = std::min(k, e->NT / 64);
     }
     P.logterm = gene_side ? 1 : 0;
@@ -439,7 +462,7 @@ SweepSide sweep_side_args(const vbnmf_engine *e, const DeviceSide &S, bool gene_
     P.n_wg = S.n_wg;
     P.logtab = e->logtab;
     P.stop = e->run_active ? (e->stop_ptr ? e->stop_ptr : &e->ctl->stop) : nullptr;
-    P.dbg = e->dbg ? e->dbg + (gene_side ? 0 : e->dbg_count / 2) : nullptr;
+    P.dbg = e->dbg ? e->dbg + v.idx * (e->dbg_count / 2) : nullptr;
     return P;
 }
 
@@ -455,52 +478,106 @@ int prepare_sweep_kernel(const void *fn)
     return VBNMF_OK;
 }
 
-// ---- dispatch over the padded rank (compile-time so factor rows live in registers) ----
-template <int R, bool WIDE, int NT, int SP>
-int launch_sweep_t(vbnmf_engine *e, const SweepSide &a, const SweepSide &b)
+// Launch of kernel K on the engine's stream, with the launch error turned into a status.
+template <auto K, class... Args>
+int launch_kernel(vbnmf_engine *e, dim3 grid, int threads, size_t lds, const Args &...args)
 {
-    static std::atomic<bool> attr_set[16];
-    const void *fn = (const void *)k_sweep<R, WIDE, NT, SP>;
-    if (e->device >= 16 || !attr_set[e->device].load(std::memory_order_acquire)) {
-        if (int rc = prepare_sweep_kernel(fn)) return rc;
-        if (e->device < 16) attr_set[e->device].store(true, std::memory_order_release);
-    }
-    const unsigned grid = (unsigned)e->n_wg;
-    hipLaunchKernelGGL((k_sweep<R, WIDE, NT, SP>), dim3(grid), dim3(NT), e->lds_bytes, e->stream, a, b);
+    hipLaunchKernelGGL(K, grid, dim3(threads), lds, e->stream, args...);
     HIPCHECK(hipGetLastError());
     return VBNMF_OK;
 }
 
-// RT: the padded rank; above 32 the sweep's lanes share it (SP lanes of R = RT / SP columns each, kernels.h)
-template <int RT>
-int launch_sweep_r(vbnmf_engine *e, const SweepSide &a, const SweepSide &b)
+// The kernels that stage the 160 KB LDS image (k_sweep, k_sweep1, k_spmm and the two batch sweeps): prepared once per
+// kernel instantiation and device (the flags live with the instantiation of this template; devices from 16 on prepare on
+// every launch).
+template <auto K, class... Args>
+int launch_lds_kernel(vbnmf_engine *e, dim3 grid, int threads, const Args &...args)
 {
-    constexpr int SP = rank_shares(RT), R = RT / SP, NT = sweep_threads(RT);
-    return e->wide ? launch_sweep_t<R, true, NT, SP>(e, a, b) : launch_sweep_t<R, false, NT, SP>(e, a, b);
+    static std::atomic<bool> attr_set[16];
+    if (e->device >= 16 || !attr_set[e->device].load(std::memory_order_acquire)) {
+        if (int rc = prepare_sweep_kernel((const void *)K)) return rc;
+        if (e->device < 16) attr_set[e->device].store(true, std::memory_order_release);
+    }
+    return launch_kernel<K>(e, grid, threads, e->lds_bytes, args...);
 }
 
+// ---- dispatch over the padded rank (compile-time so factor rows live in registers) ----
 #define VBNMF_FOR_EACH_R_UP_TO_64(X) \
     X(2) X(4) X(6) X(8) X(10) X(12) X(14) X(16) X(18) X(20) X(22) X(24) X(26) X(28) X(30) X(32) \
     X(40) X(48) X(56) X(64)
 // every padded rank: up to 32 by 2 (one lane per task), 40..64 by 8 (two lanes), 80..128 by 16 (four lanes)
 #ifdef VBNMF_DEV_FEW_RANKS              /* development builds only: a few ranks, for a compile check in a minute */
 #define VBNMF_FOR_EACH_R(X) X(4) X(6) X(8) X(10) X(20) X(48) X(80)
+#define VBNMF_FOR_EACH_R_BATCH(X) X(4) X(6) X(8) X(10)
 #else
 #define VBNMF_FOR_EACH_R(X) VBNMF_FOR_EACH_R_UP_TO_64(X) X(80) X(96) X(112) X(128)
+#define VBNMF_FOR_EACH_R_BATCH(X) X(2) X(4) X(6) X(8) X(10) X(12) X(14) X(16)
 #endif
+constexpr int kBatchMaxPaddedRank = 16;      // the small-matrix regime the batch is for (instantiations cost build time)
+static_assert(rank_shares(kBatchMaxPaddedRank) == 1, "the batch sweeps have no form that shares a rank among lanes");
+
+// f(std::integral_constant<int, R>{}) for the padded rank R of one of the lists above; returns f's status.  The lists are
+// expanded here and nowhere else: with_rank serves every rank, with_rank_up_to_64 the truncated SVD's dense kernels,
+// with_batch_rank the kernels that step a batch of engines.
+#define X(RR) case RR: return f(std::integral_constant<int, RR>{});
+template <class F>
+int with_rank(int R, F &&f)
+{
+    switch (R) {
+        VBNMF_FOR_EACH_R(X)
+        default: return fail(VBNMF_ERR_BAD_ARG, "unsupported padded rank %d", R);
+    }
+}
+
+template <class F>
+int with_rank_up_to_64(int R, F &&f)
+{
+    switch (R) {
+        VBNMF_FOR_EACH_R_UP_TO_64(X)
+        default: return fail(VBNMF_ERR_BAD_ARG, "unsupported padded rank %d", R);
+    }
+}
+
+template <class F>
+int with_batch_rank(int R, F &&f)
+{
+    switch (R) {
+        VBNMF_FOR_EACH_R_BATCH(X)
+        default: return fail(VBNMF_ERR_BAD_ARG, "a batch serves padded ranks up to %d (this engine: %d)", kBatchMaxPaddedRank, R);
+    }
+}
+#undef X
+
+// f(std::true_type{}) or f(std::false_type{}): a run-time switch as a template argument
+template <class F>
+int with_flag(bool on, F &&f)
+{
+    return on ? f(std::true_type{}) : f(std::false_type{});
+}
+
+// The template arguments the sweep family shares, for the padded rank RT and the engine's entry format: above 32 the
+// sweep's lanes share the rank (SP lanes of R = RT / SP columns each, kernels.h).  f(shape) reads them as shape.R, shape.WIDE,
+// shape.NT and shape.SP.
+template <int R_, bool WIDE_, int NT_, int SP_>
+struct SweepShape { static constexpr int R = R_, NT = NT_, SP = SP_; static constexpr bool WIDE = WIDE_; };
+
+template <int RT, class F>
+int with_sweep_shape(const vbnmf_engine *e, F &&f)
+{
+    constexpr int SP = rank_shares(RT), R = RT / SP, NT = sweep_threads(RT);
+    return e->wide ? f(SweepShape<R, true, NT, SP>{}) : f(SweepShape<R, false, NT, SP>{});
+}
 
 int launch_sweep(vbnmf_engine *e)
 {
-    SweepSide a = sweep_side_args(e, e->A, true, e->epart);
-    SweepSide b = sweep_side_args(e, e->B, false, e->epart + e->n_wg);
+    SweepSide a = sweep_side_args(e, true);
+    SweepSide b = sweep_side_args(e, false);
     if (e->timing) { HIPCHECK(hipEventRecord(e->ev0, e->stream)); }
-    int rc = VBNMF_ERR_BAD_ARG;
-    switch (e->R) {
-#define X(RR) case RR: rc = launch_sweep_r<RR>(e, a, b); break;
-        VBNMF_FOR_EACH_R(X)
-#undef X
-        default: return fail(VBNMF_ERR_BAD_ARG, "unsupported padded rank %d", e->R);
-    }
+    int rc = with_rank(e->R, [&](auto rt) {
+        return with_sweep_shape<rt()>(e, [&](auto s) {
+            return launch_lds_kernel<k_sweep<s.R, s.WIDE, s.NT, s.SP>>(e, dim3((unsigned)e->n_wg), s.NT, a, b);
+        });
+    });
     if (rc) return rc;
     if (e->timing) { HIPCHECK(hipEventRecord(e->ev1, e->stream)); e->ev_recorded = true; }
     return VBNMF_OK;
@@ -522,29 +599,21 @@ int launch_update(vbnmf_engine *e, bool gene_side, double a, double b, double fu
     if (foldp) fold = *foldp;
     const unsigned grid = fold.control_only ? 1 : e->ub;
     const double lga = (ctl || foldp) ? 0.0 : -std::lgamma(a) + a * std::log(a / b);     // reference :82 / :87
-    const int side = gene_side ? 0 : 1;
+    const SideView v = side_view(e, gene_side);
+    const DeviceSide &S = v.S;
     const bool dense = gene_side && e->partitioned;               // statistics already summed into `red`
-    const DeviceSide &S = gene_side ? e->A : e->B;
     const double *redin = e->red_in ? e->red_in : e->red;
     const double *acc = dense ? redin : S.part;
     const int32_t *inv_ptr = dense ? nullptr : S.inv_ptr;
     const uint32_t *inv_task = dense ? nullptr : S.inv_task;
-    const int64_t nmaj = gene_side ? e->n : e->m;
     const double *other = dense ? redin + (size_t)e->n * e->R : nullptr;
-    const double *other_bp = dense ? nullptr : (gene_side ? e->bpH : e->bpW);
+    const double *other_bp = dense ? nullptr : v.other_bp;
     const int other_nb = dense ? 0 : e->ub;
-    double *l = gene_side ? e->lw : e->lh, *ll = gene_side ? e->llw : e->llh;
-    double *ev = gene_side ? e->ew : e->eh, *d = gene_side ? e->dw : e->dh;
-    double *bp = gene_side ? e->bpW : e->bpH;
     const int stage = stage_ids(S, grid, dense);
-    switch (e->R) {
-#define X(RR) case RR: hipLaunchKernelGGL((k_update<RR>), dim3(grid), dim3(kUpdateThreads), 0, e->stream, acc, inv_ptr, inv_task, nmaj, e->r, other, other_bp, other_nb, a, b, lga, fudge, l, ll, ev, d, bp, ctl, side, fold, stage); break;
-        VBNMF_FOR_EACH_R(X)
-#undef X
-        default: return fail(VBNMF_ERR_BAD_ARG, "unsupported padded rank %d", e->R);
-    }
-    HIPCHECK(hipGetLastError());
-    return VBNMF_OK;
+    return with_rank(e->R, [&](auto rt) {
+        return launch_kernel<k_update<rt()>>(e, dim3(grid), kUpdateThreads, 0, acc, inv_ptr, inv_task, v.nmaj, e->r, other, other_bp,
+                                             other_nb, a, b, lga, fudge, v.l, v.ll, v.e, v.d, v.bp, ctl, v.idx, fold, stage);
+    });
 }
 
 // The work table of k_update2 (kernels.h): per block of the update, the visits of every thread row -- the block's genes
@@ -634,6 +703,13 @@ bool build_update_table(const Layout &LA, const Layout &LB, int ub, int R, std::
     return true;
 }
 
+// A side as k_update2 takes it; bp_prev / bp: the tables of block partials the launch reads and writes.
+UpdSide upd_side(const vbnmf_engine *e, bool gene_side, const double *bp_prev, double *bp)
+{
+    const SideView v = side_view(e, gene_side);
+    return UpdSide{v.S.part, v.nmaj, v.l, v.ll, v.e, v.d, bp, bp_prev};
+}
+
 // Both posterior updates in one launch (kernels.h: k_update2).  Both tables of block partials alternate: the launch reads
 // the previous ones and writes the others; e->bpW / e->bpH always name the latest.
 int launch_update2(vbnmf_engine *e, double aw, double bw, double ah, double bh, double fudge, const LoopCtl *ctl = nullptr,
@@ -642,40 +718,22 @@ int launch_update2(vbnmf_engine *e, double aw, double bw, double ah, double bh, 
     ControlFold fold{};
     if (foldp) fold = *foldp;
     const unsigned grid = (unsigned)e->ub;
-    UpdSide W{}, H{};
-    W.part = e->A.part; W.nmaj = e->n;
-    W.l = e->lw; W.ll = e->llw; W.e = e->ew; W.d = e->dw;
-    H.part = e->B.part; H.nmaj = e->m;
-    H.l = e->lh; H.ll = e->llh; H.e = e->eh; H.d = e->dh;
-    UpdTable T{e->upd_tab, e->upd_stride4, e->upd_V, e->upd_ids_off};
-    W.bp_prev = e->bpW; H.bp_prev = e->bpH;
+    const UpdSide W = upd_side(e, true, e->bpW, e->bpW_alt), H = upd_side(e, false, e->bpH, e->bpH_alt);
     std::swap(e->bpW, e->bpW_alt); std::swap(e->bpH, e->bpH_alt);
-    W.bp = e->bpW; H.bp = e->bpH;
-    switch (e->R) {
-#define X(RR) case RR: hipLaunchKernelGGL((k_update2<RR>), dim3(grid), dim3(kUpdateThreads), 0, e->stream, W, H, T, e->r, e->ub, (const double *)e->csum, e->n_wg, aw, bw, ah, bh, fudge, ctl, fold); break;
-        VBNMF_FOR_EACH_R(X)
-#undef X
-        default: return fail(VBNMF_ERR_BAD_ARG, "unsupported padded rank %d", e->R);
-    }
-    HIPCHECK(hipGetLastError());
-    return VBNMF_OK;
+    UpdTable T{e->upd_tab, e->upd_stride4, e->upd_V, e->upd_ids_off};
+    return with_rank(e->R, [&](auto rt) {
+        return launch_kernel<k_update2<rt()>>(e, dim3(grid), kUpdateThreads, 0, W, H, T, e->r, e->ub, (const double *)e->csum, e->n_wg,
+                                              aw, bw, ah, bh, fudge, ctl, fold);
+    });
 }
 
-int launch_prime(vbnmf_engine *e, bool gene_side)
+// ev: the array whose column sums go to the side's block partials (null: none)
+int launch_prime(vbnmf_engine *e, bool gene_side, const double *ev)
 {
-    const int64_t nmaj = gene_side ? e->n : e->m;
-    const double *l = gene_side ? e->lw : e->lh;
-    double *ll = gene_side ? e->llw : e->llh;
-    const double *ev = gene_side ? nullptr : e->eh;
-    double *bp = gene_side ? e->bpW : e->bpH;
-    switch (e->R) {
-#define X(RR) case RR: hipLaunchKernelGGL((k_prime<RR>), dim3(e->ub), dim3(kUpdateThreads), 0, e->stream, nmaj, e->r, l, ll, ev, bp); break;
-        VBNMF_FOR_EACH_R(X)
-#undef X
-        default: return fail(VBNMF_ERR_BAD_ARG, "unsupported padded rank %d", e->R);
-    }
-    HIPCHECK(hipGetLastError());
-    return VBNMF_OK;
+    const SideView v = side_view(e, gene_side);
+    return with_rank(e->R, [&](auto rt) {
+        return launch_kernel<k_prime<rt()>>(e, dim3(e->ub), kUpdateThreads, 0, v.nmaj, e->r, (const double *)v.l, v.ll, ev, v.bp);
+    });
 }
 
 int launch_final(vbnmf_engine *e)
@@ -683,14 +741,10 @@ int launch_final(vbnmf_engine *e)
     const double *tail = e->partitioned ? e->red + (size_t)e->n * e->R : nullptr;
     const int64_t nep = 2 * (int64_t)e->n_wg;
     e->seq += 1.0;
-    switch (e->R) {
-#define X(RR) case RR: hipLaunchKernelGGL((k_final<RR>), dim3(1), dim3(1024), 0, e->stream, e->bpW, e->ub, tail, e->bpH, e->ub, e->epart, nep, e->lgx, e->r, (double)e->n, (double)e->m_global, e->seq, e->d_out, e->h_out_dev); break;
-        VBNMF_FOR_EACH_R(X)
-#undef X
-        default: return fail(VBNMF_ERR_BAD_ARG, "unsupported padded rank %d", e->R);
-    }
-    HIPCHECK(hipGetLastError());
-    return VBNMF_OK;
+    return with_rank(e->R, [&](auto rt) {
+        return launch_kernel<k_final<rt()>>(e, dim3(1), 1024, 0, e->bpW, e->ub, tail, e->bpH, e->ub, e->epart, nep, e->lgx, e->r,
+                                            (double)e->n, (double)e->m_global, e->seq, e->d_out, e->h_out_dev);
+    });
 }
 
 // partitioned engines: sweep output -> reduce buffer = [swsum | rowSum(eh) | sum H-terms | sum log lh | data term | lgx]
@@ -706,124 +760,70 @@ int launch_pack(vbnmf_engine *e)
 }
 
 // ---- ML-NMF (mlnmf.h): single-side sweeps and the multiplicative updates ----
-template <int R, bool WIDE, bool LOGTERM, int NT, int SP, bool VB = false>
-int launch_sweep1_t(vbnmf_engine *e, const SweepSide &a)
+// One side's sweep alone (k_sweep1).  VB = false: the ML step's, whose cell side carries the log term (sum x log(wh));
+// VB = true: one side of the VB sweep (cell-partitioned device loop), gene side with the log term, cell side without.
+template <bool VB>
+int launch_side_sweep(vbnmf_engine *e, const SweepSide &a, bool logterm)
 {
-    static std::atomic<bool> attr_set[16];
-    const void *fn = (const void *)k_sweep1<R, WIDE, LOGTERM, NT, VB, SP>;
-    if (e->device >= 16 || !attr_set[e->device].load(std::memory_order_acquire)) {
-        if (int rc = prepare_sweep_kernel(fn)) return rc;
-        if (e->device < 16) attr_set[e->device].store(true, std::memory_order_release);
-    }
-    hipLaunchKernelGGL((k_sweep1<R, WIDE, LOGTERM, NT, VB, SP>), dim3((unsigned)e->n_wg), dim3(NT), e->lds_bytes, e->stream, a);
-    HIPCHECK(hipGetLastError());
-    return VBNMF_OK;
-}
-
-// One side of the VB sweep alone (cell-partitioned device loop): gene side with the log term, cell side without.
-template <int RT>
-int launch_vb_side_r(vbnmf_engine *e, const SweepSide &a, bool gene_side)
-{
-    constexpr int SP = rank_shares(RT), R = RT / SP, NT = sweep_threads(RT);
-    if (e->wide) return gene_side ? launch_sweep1_t<R, true, true, NT, SP, true>(e, a) : launch_sweep1_t<R, true, false, NT, SP, true>(e, a);
-    return gene_side ? launch_sweep1_t<R, false, true, NT, SP, true>(e, a) : launch_sweep1_t<R, false, false, NT, SP, true>(e, a);
-}
-
-template <int RT>
-int launch_sweep1_r(vbnmf_engine *e, const SweepSide &a, bool logterm)
-{
-    constexpr int SP = rank_shares(RT), R = RT / SP, NT = sweep_threads(RT);
-    if (e->wide) return logterm ? launch_sweep1_t<R, true, true, NT, SP>(e, a) : launch_sweep1_t<R, true, false, NT, SP>(e, a);
-    return logterm ? launch_sweep1_t<R, false, true, NT, SP>(e, a) : launch_sweep1_t<R, false, false, NT, SP>(e, a);
+    return with_rank(e->R, [&](auto rt) {
+        return with_sweep_shape<rt()>(e, [&](auto s) {
+            return with_flag(logterm, [&](auto lt) {
+                return launch_lds_kernel<k_sweep1<s.R, s.WIDE, lt(), s.NT, VB, s.SP>>(e, dim3((unsigned)e->n_wg), s.NT, a);
+            });
+        });
+    });
 }
 
 // gene side: lanes own genes (F = w, G = h), statistics for the W update; cell side: F = h, G = w, statistics
 // for the H update and sum x log(wh) in the cell half of epart.
 int launch_sweep1(vbnmf_engine *e, bool gene_side)
 {
-    SweepSide a = sweep_side_args(e, gene_side ? e->A : e->B, gene_side, gene_side ? e->epart : e->epart + e->n_wg);
+    SweepSide a = sweep_side_args(e, gene_side);
     a.logterm = gene_side ? 0 : 1;
     hipEvent_t t0 = gene_side ? e->ev0 : e->ev2, t1 = gene_side ? e->ev1 : e->ev3;
     if (e->timing) { HIPCHECK(hipEventRecord(t0, e->stream)); }
-    int rc = VBNMF_ERR_BAD_ARG;
-    switch (e->R) {
-#define X(RR) case RR: rc = launch_sweep1_r<RR>(e, a, !gene_side); break;
-        VBNMF_FOR_EACH_R(X)
-#undef X
-        default: return fail(VBNMF_ERR_BAD_ARG, "unsupported padded rank %d", e->R);
-    }
-    if (rc) return rc;
+    if (int rc = launch_side_sweep<false>(e, a, !gene_side)) return rc;
     if (e->timing) { HIPCHECK(hipEventRecord(t1, e->stream)); (gene_side ? e->ev_recorded : e->ev2_recorded) = true; }
     return VBNMF_OK;
 }
 
 int launch_vb_side(vbnmf_engine *e, bool gene_side)
 {
-    SweepSide a = sweep_side_args(e, gene_side ? e->A : e->B, gene_side, gene_side ? e->epart : e->epart + e->n_wg);
-    int rc = VBNMF_ERR_BAD_ARG;
-    switch (e->R) {
-#define X(RR) case RR: rc = launch_vb_side_r<RR>(e, a, gene_side); break;
-        VBNMF_FOR_EACH_R(X)
-#undef X
-        default: return fail(VBNMF_ERR_BAD_ARG, "unsupported padded rank %d", e->R);
-    }
-    return rc;
+    return launch_side_sweep<true>(e, sweep_side_args(e, gene_side), gene_side);
 }
 
 int launch_ml_update(vbnmf_engine *e, bool gene_side, int prior, double ga, double gb, double eps, const MlFold *foldp = nullptr)
 {
-    const DeviceSide &S = gene_side ? e->A : e->B;
-    const int64_t nmaj = gene_side ? e->n : e->m;
-    const double *other_bp = gene_side ? e->bpH : e->bpW;
-    double *f = gene_side ? e->lw : e->lh;
-    double *bp = gene_side ? e->bpW : e->bpH;
+    const SideView v = side_view(e, gene_side);
+    const DeviceSide &S = v.S;
     const int32_t *stop = e->run_active ? (e->stop_ptr ? e->stop_ptr : &e->ctl->stop) : nullptr;
     MlFold fold{};
     if (foldp) fold = *foldp;
     const unsigned grid = fold.control_only ? 1 : (unsigned)e->ub;
-    switch (e->R) {
-#define X(RR) case RR: hipLaunchKernelGGL((k_ml_update<RR>), dim3(grid), dim3(kUpdateThreads), 0, e->stream, S.part, S.inv_ptr, S.inv_task, nmaj, e->r, other_bp, e->ub, prior, ga, gb, eps, f, bp, stop, fold, stage_ids(S, grid)); break;
-        VBNMF_FOR_EACH_R(X)
-#undef X
-        default: return fail(VBNMF_ERR_BAD_ARG, "unsupported padded rank %d", e->R);
-    }
-    HIPCHECK(hipGetLastError());
-    return VBNMF_OK;
+    return with_rank(e->R, [&](auto rt) {
+        return launch_kernel<k_ml_update<rt()>>(e, dim3(grid), kUpdateThreads, 0, S.part, S.inv_ptr, S.inv_task, v.nmaj, e->r,
+                                                (const double *)v.other_bp, e->ub, prior, ga, gb, eps, v.l, v.bp, stop, fold,
+                                                stage_ids(S, grid));
+    });
 }
 
 int launch_ml_final(vbnmf_engine *e)
 {
     e->seq += 1.0;
-    switch (e->R) {
-#define X(RR) case RR: hipLaunchKernelGGL((k_ml_final<RR>), dim3(1), dim3(1024), 0, e->stream, e->bpW, e->bpH, e->ub, e->epart + e->n_wg, (int64_t)e->n_wg, e->xlx, e->r, (double)e->n, (double)e->m, e->seq, e->d_out, e->h_out_dev); break;
-        VBNMF_FOR_EACH_R(X)
-#undef X
-        default: return fail(VBNMF_ERR_BAD_ARG, "unsupported padded rank %d", e->R);
-    }
-    HIPCHECK(hipGetLastError());
-    return VBNMF_OK;
+    return with_rank(e->R, [&](auto rt) {
+        return launch_kernel<k_ml_final<rt()>>(e, dim3(1), 1024, 0, e->bpW, e->bpH, e->ub, e->epart + e->n_wg, (int64_t)e->n_wg, e->xlx,
+                                               e->r, (double)e->n, (double)e->m, e->seq, e->d_out, e->h_out_dev);
+    });
 }
 
 // ---- sparse products on the tiled layout (k_spmm) ----
-template <int R, bool WIDE, int NT, int SP>
-int launch_spmm_t(vbnmf_engine *e, const SweepSide &a)
+int launch_spmm(vbnmf_engine *e, const SweepSide &a)
 {
-    static std::atomic<bool> attr_set[16];
-    const void *fn = (const void *)k_spmm<R, WIDE, NT, SP>;
-    if (e->device >= 16 || !attr_set[e->device].load(std::memory_order_acquire)) {
-        if (int rc = prepare_sweep_kernel(fn)) return rc;
-        if (e->device < 16) attr_set[e->device].store(true, std::memory_order_release);
-    }
-    hipLaunchKernelGGL((k_spmm<R, WIDE, NT, SP>), dim3((unsigned)e->n_wg), dim3(NT), e->lds_bytes, e->stream, a);
-    HIPCHECK(hipGetLastError());
-    return VBNMF_OK;
-}
-
-template <int RT>
-int launch_spmm_r(vbnmf_engine *e, const SweepSide &a)
-{
-    constexpr int SP = rank_shares(RT), R = RT / SP, NT = sweep_threads(RT);
-    return e->wide ? launch_spmm_t<R, true, NT, SP>(e, a) : launch_spmm_t<R, false, NT, SP>(e, a);
+    return with_rank(e->R, [&](auto rt) {
+        return with_sweep_shape<rt()>(e, [&](auto s) {
+            return launch_lds_kernel<k_spmm<s.R, s.WIDE, s.NT, s.SP>>(e, dim3((unsigned)e->n_wg), s.NT, a);
+        });
+    });
 }
 
 // Wall-clock bound of the host's waits on the device (seconds): VBNMF_WAIT_TIMEOUT_S, default 300.  A wait that
@@ -941,12 +941,338 @@ int prime_state(vbnmf_engine *e)
 {
     e->has_state = true;
     e->ids_valid = false;
-    if (int rc = launch_prime(e, true)) return rc;
-    if (int rc = launch_prime(e, false)) return rc;
+    if (int rc = launch_prime(e, true, nullptr)) return rc;
+    if (int rc = launch_prime(e, false, e->eh)) return rc;
     if (int rc = launch_sweep(e)) return rc;
     if (e->partitioned) { if (int rc = launch_pack(e)) return rc; }
     e->prime_pending = true;
     if (!e->partitioned) return vbnmf_engine_state_finish(e);
+    return VBNMF_OK;
+}
+
+// ---------------------------------------------------------------- engine creation (vbnmf_engine_create_geom), one step per function
+struct CreateArgs {
+    const vbnmf_matrix *X;
+    int64_t cb, ce, m_global;
+    int32_t r, geometry_rank, device;
+    bool whole_matrix() const { return cb == 0 && ce == X->M.m; }
+};
+
+// VBNMF_BUILD_TIMES=1: where the seconds of this creation go (offsets from here; the layouts' own phases come from host.cpp)
+struct BuildClock {
+    const bool on = getenv("VBNMF_BUILD_TIMES") != nullptr;
+    const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    void mark(const char *what) const
+    {
+        if (on) fprintf(stderr, "  engine create +%.3f s  %s\n", std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(), what);
+    }
+};
+
+// Owner of the engine under construction: destroyed on every exit of create_engine but the release into *out.
+struct EngineDestroy { void operator()(vbnmf_engine *e) const { vbnmf_engine_destroy(e); } };
+using EngineGuard = std::unique_ptr<vbnmf_engine, EngineDestroy>;
+
+// A helper thread of engine creation, joined on every exit of its scope.  start() answers false when the process cannot
+// have another thread (std::system_error: a thread or process limit, which parallel_for in host.cpp survives the same
+// way): the caller then does the work itself.  join() may be called from several threads.
+class HelperThread {
+    std::thread t;
+    std::mutex mu;
+public:
+    template <class F>
+    bool start(F &&f)
+    {
+        try { t = std::thread(std::forward<F>(f)); } catch (const std::system_error &) { return false; }
+        return true;
+    }
+    void join() { std::lock_guard<std::mutex> g(mu); if (t.joinable()) t.join(); }
+    ~HelperThread() { join(); }
+};
+
+// The two sides' layouts while the engine is made: the matrix's cached ones (shared) or this partition's own.
+struct SideLayouts {
+    std::shared_ptr<const Layout> shared[2];
+    Layout own[2];
+    const Layout *L[2] = {nullptr, nullptr};
+};
+
+int check_create_args(const CreateArgs &a)
+{
+    const vbnmf_matrix *X = a.X;
+    if (!X) return fail(VBNMF_ERR_BAD_ARG, "matrix handle is NULL");
+    if (a.r < 1 || a.r > VBNMF_MAX_RANK) return fail(VBNMF_ERR_BAD_ARG, "rank %d is outside [1, %d]", a.r, VBNMF_MAX_RANK);
+    if (a.geometry_rank != 0 && (a.geometry_rank < a.r || a.geometry_rank > VBNMF_MAX_RANK))
+        return fail(VBNMF_ERR_BAD_ARG, "geometry rank %d cannot serve rank %d (it must lie in [rank, %d])", a.geometry_rank, a.r, VBNMF_MAX_RANK);
+    if (a.cb < 0 || a.ce > X->M.m || a.cb >= a.ce)
+        return fail(VBNMF_ERR_BAD_ARG, "column range [%lld, %lld) is outside the matrix", (long long)a.cb, (long long)a.ce);
+    if (a.m_global < a.ce - a.cb) return fail(VBNMF_ERR_BAD_ARG, "m_global is smaller than the partition");
+    if (X->M.shell && !a.whole_matrix())
+        return fail(VBNMF_ERR_STATE, "this matrix handle is a shell (vbnmf_matrix_shell): it holds no entries to cut a partition's layout from");
+    return check_device(a.device);
+}
+
+// Dimensions, padded rank and the grids of the sweep and of the updates.
+int choose_grid(vbnmf_engine *e, const CreateArgs &a)
+{
+    e->device = a.device;
+    e->n = a.X->M.n; e->m = a.ce - a.cb; e->m_global = a.m_global; e->col_begin = a.cb;
+    e->r = a.r; e->R = padded_rank(a.r);
+    if (tl_pad_R > e->R) e->R = tl_pad_R;                    // (engines of several ranks meant for ONE batch: vbnmf_set_engine_padding)
+    e->NT = sweep_threads(e->R);
+    {
+        // Blocks of the update kernels.  Fewer than one per CU on small matrices (one pass of the longer factor per block)
+        // was measured and is SLOWER: 200 x 500 at rank 3 36.1 against 30.9 us per step with 2 blocks, 2 000 x 10 000 at
+        // rank 5 82.7 against 79.2 with 59 -- the gather of the task partials is address work (64 scattered 8-byte loads
+        // per wave instruction) that 256 CUs' texture units share and 2 do not.  VBNMF_UPDATE_BLOCKS overrides (experiments).
+        int ub = kUpdateBlocks;
+        if (const char *sv = getenv("VBNMF_UPDATE_BLOCKS")) { int v = atoi(sv); if (v >= 1 && v <= kUpdateBlocks) ub = v; }
+        if (tl_grid_ub > 0) ub = std::min(ub, tl_grid_ub);          // (engines meant for a batch: vbnmf_set_engine_grid)
+        e->ub = ub;
+    }
+    e->wide = !a.X->M.counts_int;
+    e->partitioned = (a.ce - a.cb) != a.m_global;
+    if (int rc = sweep_workgroups(a.device, e->partitioned, e->n_wg)) return rc;
+    if (!e->partitioned && tl_grid_nwg > 0) e->n_wg = std::min(e->n_wg, tl_grid_nwg);
+    return VBNMF_OK;
+}
+
+// The two sides' layouts, cut or taken from the matrix's cache, and their device copies.
+int build_sides(vbnmf_engine *e, const CreateArgs &a, const BuildClock &clock, SideLayouts &lay)
+{
+    const vbnmf_matrix *X = a.X;
+    const int device = a.device;
+    // This process's FIRST use of the device (HIP context, first allocation, code object: 0.1-0.15 s, once) runs on a helper
+    // thread beside the host's cut of the layouts and is waited for where the first upload needs it (a failure there
+    // resurfaces at that upload).  Later engines find the device warm and start no thread.
+    // (Where no thread can be started the warm-up runs here instead, so the flag stays set on either path.)
+    static std::atomic<bool> warm_started[16];
+    HelperThread warm;
+    if (device < 16 && !warm_started[device].exchange(true)) {
+        auto warm_up = [device] { try { (void)vbnmf_device_warmup(device); } catch (...) {} };
+        if (!warm.start(warm_up)) warm_up();
+    }
+
+    std::vector<int32_t> part_order;                         // a partition orders its own cells (both sides alike)
+    if (!a.whole_matrix()) part_order = compute_cell_order(X->M, a.cb, a.ce);
+    // The two sides are cut (or taken from the matrix's cache) and uploaded SIDE BY SIDE: the cell side on a second host
+    // thread, the gene side here.  Each cut is memory-bound well before it uses all host threads, and a side's upload
+    // (200 MB of pageable memory at the headline size) runs beside the other side's cut.  Engine creation at the headline
+    // size: 0.41 -> 0.3 s on the GPU box (profiles/r05_setup_times.txt).  VBNMF_SERIAL_SIDES=1: one after the other.
+    clock.mark("start");
+    if (a.whole_matrix() && !X->M.shell) (void)X->M.cell_order();          // (both sides start from it: formed once, here)
+    clock.mark("cell order");
+    auto do_side = [&](int side) -> int {
+        int src = VBNMF_OK;
+        const int64_t nmaj = side == 0 ? e->n : e->m, nmin = side == 0 ? e->m : e->n;
+        // The geometry is that of the matrix's rank CLASS (vbnmf_matrix_plan_ranks; without a plan the class is this
+        // rank's own): the ranks of a sweep share one pair of layouts, cut for the widest rows among them.
+        const int Rc = std::max(e->R, a.geometry_rank ? padded_rank(a.geometry_rank) : plan_class(X, e->R));
+        const int64_t nnz_part = a.whole_matrix() ? X->M.nnz : X->M.colptr[a.ce] - X->M.colptr[a.cb];
+        LayoutParams lp = default_layout_params(nmaj, nmin, Rc, e->n_wg, nnz_part);
+        std::shared_ptr<const Layout> &shared = lay.shared[side];
+        const Layout *L = &lay.own[side];
+        if (a.whole_matrix()) {                          // whole matrix: the layout may already exist (another rank, a restart)
+            shared = shared_layout(X, side, lp, src);
+            L = shared.get();
+        } else {
+            src = build_layout(X->M, a.cb, a.ce, side, lp, &part_order, lay.own[side]);
+        }
+        clock.mark(side == 0 ? "gene side cut" : "cell side cut");
+        warm.join();
+        if (!src) src = upload_side(*L, e->R, device, shared ? X : nullptr, side == 0 ? e->A : e->B);
+        clock.mark(side == 0 ? "gene side uploaded" : "cell side uploaded");
+        lay.L[side] = L;
+        return src;
+    };
+    static const bool serial_sides = [] { const char *v = getenv("VBNMF_SERIAL_SIDES"); return v && v[0] == '1'; }();
+    static const int side_share = [] { const char *v = getenv("VBNMF_SIDE_THREAD_SHARE"); return v ? std::max(1, atoi(v)) : 1; }();
+    int rc = VBNMF_OK, rc1 = VBNMF_OK;
+    std::string msg1;
+    std::exception_ptr thrown1;                              // what the cell side's thread threw: rethrown on this one
+    HelperThread cell_side;                                  // (declared after everything its thread touches: joined first)
+    const bool side_by_side = !serial_sides && cell_side.start([&] {
+        try {
+            if (hipSetDevice(device) != hipSuccess) { rc1 = VBNMF_ERR_HIP; msg1 = "hipSetDevice failed on the layout thread"; return; }
+            set_thread_share(side_share);
+            rc1 = do_side(1);
+            if (rc1) msg1 = last_error_cstr();               // (error messages are per host thread)
+        } catch (...) { thrown1 = std::current_exception(); }
+    });
+    if (side_by_side) {
+        set_thread_share(side_share);
+        try { rc = do_side(0); } catch (...) { set_thread_share(1); throw; }
+        set_thread_share(1);
+        cell_side.join();
+        if (thrown1) std::rethrow_exception(thrown1);
+        if (!rc && rc1) rc = fail(rc1, "%s", msg1.c_str());
+    } else {
+        rc = do_side(0);
+        if (!rc) rc = do_side(1);
+    }
+    if (rc) return rc;
+    e->nnz = lay.L[0]->nnz; e->cell_perm = lay.L[0]->cell_perm;
+    if (lay.L[1]->cell_perm != e->cell_perm) return fail(VBNMF_ERR_STATE, "the two sides' layouts disagree on the order of the cells");
+    return VBNMF_OK;
+}
+
+int build_pair_table(vbnmf_engine *e, const SideLayouts &lay)
+{
+    // One launch for both posterior updates (k_update2): unpartitioned engines whose blocks' work fits the kernel's
+    // table; VBNMF_NO_UPDATE_PAIR=1 keeps the two launches (A/B switch, and the form the pair is held to in
+    // tests/test_gpu_update_pair.py).
+    // Where it pays (round 5, same-box A/Bs in profiles/r05_pair_ab*.txt, r05_small_pair_ab.txt): the launch it saves is
+    // worth ~3 us of a step whatever the size, the column sums it needs cost the gene side of the sweep ~60 + 4 R
+    // instructions per SLICE.  5 000 x 20 000 at rank 8: 64.0 -> 60.1 us per step (+6 %); C2 (2 000 x 10 000 dense,
+    // rank 5) +1.9 %; C1 and the PBMC-sized sample +-0; the headline (4.9e7 entries, rank 10) -0.3 %, rank 20 -1.2 %.
+    // So: on up to 2.5e8 entries x padded rank, off beyond.  VBNMF_UPDATE_PAIR=1 / VBNMF_NO_UPDATE_PAIR=1 force it.
+    const char *np = getenv("VBNMF_NO_UPDATE_PAIR"), *fp = getenv("VBNMF_UPDATE_PAIR");
+    const bool forced = fp && fp[0] == '1';
+    const bool pays = (double)lay.L[0]->nnz * (double)e->R <= 2.5e8;
+    e->pair = !e->partitioned && !(np && np[0] == '1') && (forced || pays) && lay.L[0]->n_wg == lay.L[1]->n_wg;
+    if (!e->pair) return VBNMF_OK;
+    std::vector<uint32_t> tab;
+    e->pair = build_update_table(*lay.L[0], *lay.L[1], e->ub, e->R, tab, e->upd_stride4, e->upd_V, e->upd_ids_off);
+    if (!e->pair) return VBNMF_OK;
+    uint32_t *d = nullptr;
+    const int rc = dev_upload(&d, tab);
+    e->upd_tab = reinterpret_cast<uint4 *>(d);
+    return rc;
+}
+
+int create_stream_and_events(vbnmf_engine *e)
+{
+    // The engine's stream, before the first fill: everything that initialises the engine's own buffers below is queued ON it
+    // (hipMemsetAsync), so it is ordered with the engine's kernels.  A plain hipMemset goes to the device's null stream,
+    // which this non-blocking stream does not wait for, and may return before the fill has run: with several host threads
+    // creating engines side by side (vb_factorize(concurrent=K)) a fill queued behind the other threads' null-stream work
+    // could land AFTER the engine's first kernels had written the buffer -- zeroed block partials, a different trajectory
+    // (seen once in round 5, tests/test_gpu_end_to_end.py::test_concurrent_units_give_the_same_result).
+    // (Created HERE and not at the top: this process's first use of the device -- 0.1 s of HIP start-up -- then happens on the
+    // cell side's thread, at its upload, beside the gene side's cut, instead of in front of both.)
+    hipError_t hs;
+    if ((hs = hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking)) != hipSuccess ||
+        (hs = hipEventCreate(&e->ev0)) != hipSuccess || (hs = hipEventCreate(&e->ev1)) != hipSuccess ||
+        (hs = hipEventCreate(&e->ev2)) != hipSuccess || (hs = hipEventCreate(&e->ev3)) != hipSuccess)
+        return fail(VBNMF_ERR_HIP, "engine setup failed: %s", hipGetErrorString(hs));
+    e->own_stream = true;
+    return VBNMF_OK;
+}
+
+// The cells' order on the device, the constants of the two likelihoods, the cache policy and the sweep's LDS size.
+int scalar_terms(vbnmf_engine *e, const CreateArgs &a, const BuildClock &clock)
+{
+    const vbnmf_matrix *X = a.X;
+    if (!e->cell_perm.empty()) { if (int rc = dev_upload(&e->d_perm, e->cell_perm)) return rc; }
+    e->lgx = a.whole_matrix() ? X->lgx : sum_lgamma_x1(X->M, a.cb, a.ce);
+    if (a.whole_matrix()) {                           // whole matrix: formed once per matrix, not per engine (a pass over X)
+        std::call_once(X->xlx_once, [&] { X->xlx = sum_xlogx(X->M, 0, X->M.m); });      // (a shell carries the value already)
+        e->xlx = X->xlx;
+    } else {
+        e->xlx = sum_xlogx(X->M, a.cb, a.ce);
+    }
+    {
+        // Cache policy of the entry stream (kernels.h: ld_stream).  What a step moves between two uses of a line: both sides' entry
+        // streams and the per-task partial rows, written and read back.  Beyond the Infinity Cache (256 MB: the headline moves
+        // 410 + 2 x 75 MB) the stream is read non-temporally so that the partial rows and the state stay on the die; inside it
+        // (C2: 130 MB; 5 000 x 20 000: 61 MB) the stream itself stays resident from step to step and the default policy is the
+        // faster one (profiles/r05_nt_ab.txt, r05_small_nt_ab.txt).  VBNMF_STREAM_NT=0 / 1 forces it.
+        const double entry_b = e->wide ? 12.0 : 4.0;
+        const double moved = entry_b * ((double)e->A.n_slots + (double)e->B.n_slots) +
+                             2.0 * 8.0 * e->R * 64.0 * ((double)e->A.n_slices + (double)e->B.n_slices);
+        e->stream_nt = moved > 200e6;
+        if (const char *v = getenv("VBNMF_STREAM_NT")) e->stream_nt = v[0] == '1';
+    }
+    clock.mark("sum x log x");
+    static_assert(kLdsRowBase == kLdsReserveBytes, "host and device disagree on the sweep's LDS reserve");
+    e->lds_bytes = kLdsRowBase + std::max((size_t)e->A.block_width * e->A.row_slots, (size_t)e->B.block_width * e->B.row_slots) * 16;
+    if (e->lds_bytes > 160 * 1024) return fail(VBNMF_ERR_BAD_ARG, "the layout's blocks need %zu bytes of LDS", e->lds_bytes);
+    return VBNMF_OK;
+}
+
+// The ln table, the control blocks of the device-driven loops and the alternate tables of the folded and the pair form.
+int control_blocks(vbnmf_engine *e)
+{
+    std::vector<LogTabEntry> tab(kLogTabSize);
+    fill_log_table(tab.data());
+    if (int rc = dev_upload(&e->logtab, tab)) return rc;
+    if (int rc = dev_alloc(&e->ctl, 1)) return rc;
+    const char *nf = getenv("VBNMF_NO_CONTROL_FOLD");
+    // (partitioned engines: the evidence partials of the two sweeps must fit the fixed slots of the second all-reduce)
+    e->fold = !(nf && nf[0] == '1') && (!e->partitioned || 2 * (int64_t)e->n_wg <= kEvSlots);
+    if (e->fold) { if (int rc = dev_alloc(&e->ctl2, 2)) return rc; }
+    if (e->fold || e->pair) {
+        const size_t bpn = (size_t)kUpdateBlocks * (e->R + 2);
+        if (int rc = dev_alloc(&e->bpW_alt, bpn)) return rc;
+        if (int rc = dev_alloc(&e->bpH_alt, bpn)) return rc;
+        if (hipMemsetAsync(e->bpW_alt, 0, bpn * sizeof(double), e->stream) != hipSuccess ||
+            hipMemsetAsync(e->bpH_alt, 0, bpn * sizeof(double), e->stream) != hipSuccess) return fail(VBNMF_ERR_HIP, "hipMemsetAsync failed");
+    }
+    if (e->pair) {
+        if (int rc = dev_alloc(&e->csl, (size_t)std::max<int64_t>(e->A.n_slices, 1) * e->R)) return rc;
+        if (int rc = dev_alloc(&e->csum, (size_t)e->n_wg * e->R)) return rc;
+        if (hipMemsetAsync(e->csum, 0, (size_t)e->n_wg * e->R * sizeof(double), e->stream) != hipSuccess) return fail(VBNMF_ERR_HIP, "hipMemsetAsync failed");
+    }
+    return VBNMF_OK;
+}
+
+// The state arrays, the reduce buffer and the result blocks, and their initial fills on the engine's stream.
+int state_arrays(vbnmf_engine *e)
+{
+    int rc = VBNMF_OK;
+    const size_t nR = (size_t)e->n * e->R, mR = (size_t)e->m * e->R;
+    const size_t bpn = (size_t)kUpdateBlocks * (e->R + 2);
+    e->red_count = (int64_t)nR + e->R + 4;
+    if ((rc = dev_alloc(&e->lw, nR)) || (rc = dev_alloc(&e->llw, nR)) || (rc = dev_alloc(&e->ew, nR)) || (rc = dev_alloc(&e->dw, nR)) ||
+        (rc = dev_alloc(&e->lh, mR)) || (rc = dev_alloc(&e->llh, mR)) || (rc = dev_alloc(&e->eh, mR)) || (rc = dev_alloc(&e->dh, mR)) ||
+        (rc = dev_alloc(&e->bpW, bpn)) || (rc = dev_alloc(&e->bpH, bpn)) ||
+        (rc = dev_alloc(&e->red, (size_t)red_alloc_count(e))) || (rc = dev_alloc(&e->d_out, 8)))
+        return rc;
+    if (e->partitioned && 2 * (int64_t)e->n_wg <= kEvSlots) { e->epart = e->red + e->red_count; e->epart_in_red = true; }
+    else if ((rc = dev_alloc(&e->epart, 2 * (size_t)e->n_wg))) return rc;
+    hipError_t he;
+    if ((he = hipHostMalloc((void **)&e->h_out, kHostOut * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent)) != hipSuccess ||
+        (he = hipHostGetDevicePointer((void **)&e->h_out_dev, e->h_out, 0)) != hipSuccess)
+        return fail(VBNMF_ERR_HIP, "engine setup failed: %s", hipGetErrorString(he));
+    std::memset(e->h_out, 0, kHostOut * sizeof(double));
+    if (getenv("VBNMF_DEBUG_TIMES")) {
+        e->dbg_count = 2 * (size_t)e->n_wg * (2 + 2 * (e->NT / 64));
+        if ((rc = dev_alloc(&e->dbg, e->dbg_count))) return rc;
+    }
+    if ((he = hipMemsetAsync(e->ew, 0, nR * sizeof(double), e->stream)) != hipSuccess || (he = hipMemsetAsync(e->dw, 0, nR * sizeof(double), e->stream)) != hipSuccess ||
+        (he = hipMemsetAsync(e->dh, 0, mR * sizeof(double), e->stream)) != hipSuccess || (he = hipMemsetAsync(e->bpW, 0, bpn * sizeof(double), e->stream)) != hipSuccess ||
+        (he = hipMemsetAsync(e->bpH, 0, bpn * sizeof(double), e->stream)) != hipSuccess ||
+        (he = hipMemsetAsync(e->red, 0, (size_t)red_alloc_count(e) * sizeof(double), e->stream)) != hipSuccess)
+        return fail(VBNMF_ERR_HIP, "hipMemsetAsync failed: %s", hipGetErrorString(he));
+    // (sum lgamma(x + 1) into its slot of the reduce buffer: BEHIND the fill above, on the same stream; e->lgx lives as long as the engine)
+    if (e->epart_in_red && (he = hipMemcpyAsync(e->red + e->red_count + kEvSlots, &e->lgx, sizeof(double), hipMemcpyHostToDevice, e->stream)) != hipSuccess)
+        return fail(VBNMF_ERR_HIP, "hipMemcpyAsync failed: %s", hipGetErrorString(he));
+    // creation ends with the engine's buffers in their initial state whatever else the device is doing
+    if ((he = hipStreamSynchronize(e->stream)) != hipSuccess) return fail(VBNMF_ERR_HIP, "engine setup failed: %s", hipGetErrorString(he));
+    return VBNMF_OK;
+}
+
+// The steps in order.  Every exit, a return or an exception, frees the engine through `e` and joins the helper threads
+// through the guards inside build_sides; only the last line hands the engine on.
+int create_engine(const CreateArgs &a, vbnmf_engine **out)
+{
+    if (int rc = check_create_args(a)) return rc;
+    HIPCHECK(hipSetDevice(a.device));
+    EngineGuard e(new (std::nothrow) vbnmf_engine());
+    if (!e) return fail(VBNMF_ERR_OOM, "out of host memory");
+    const BuildClock clock;
+    if (int rc = choose_grid(e.get(), a)) return rc;
+    {
+        SideLayouts lay;
+        if (int rc = build_sides(e.get(), a, clock, lay)) return rc;
+        if (int rc = build_pair_table(e.get(), lay)) return rc;
+    }
+    clock.mark("both sides, update table");
+    if (int rc = create_stream_and_events(e.get())) return rc;
+    if (int rc = scalar_terms(e.get(), a, clock)) return rc;
+    if (int rc = control_blocks(e.get())) return rc;
+    if (int rc = state_arrays(e.get())) return rc;
+    clock.mark("state arrays, initial fills, done");
+    *out = e.release();
     return VBNMF_OK;
 }
 
@@ -1006,248 +1332,21 @@ void vbnmf_engine_destroy(vbnmf_engine *e)
 
 // geometry_rank: the rank whose LDS row size the tiled layouts are cut for (>= r: several ranks of a sweep share one pair
 // of layouts); 0: this rank's class in the matrix's plan (vbnmf_matrix_plan_ranks), its own geometry without one.
-int vbnmf_device_warmup(int32_t device);
-
 int vbnmf_engine_create_geom(const vbnmf_matrix *X, int64_t cb, int64_t ce, int64_t m_global, int32_t r, int32_t geometry_rank,
                              int32_t device, vbnmf_engine **out)
 {
     if (!out) return fail(VBNMF_ERR_BAD_ARG, "out pointer is NULL");
     *out = nullptr;
-    if (!X) return fail(VBNMF_ERR_BAD_ARG, "matrix handle is NULL");
-    if (r < 1 || r > VBNMF_MAX_RANK) return fail(VBNMF_ERR_BAD_ARG, "rank %d is outside [1, %d]", r, VBNMF_MAX_RANK);
-    if (geometry_rank != 0 && (geometry_rank < r || geometry_rank > VBNMF_MAX_RANK))
-        return fail(VBNMF_ERR_BAD_ARG, "geometry rank %d cannot serve rank %d (it must lie in [rank, %d])", geometry_rank, r, VBNMF_MAX_RANK);
-    if (cb < 0 || ce > X->M.m || cb >= ce) return fail(VBNMF_ERR_BAD_ARG, "column range [%lld, %lld) is outside the matrix", (long long)cb, (long long)ce);
-    if (m_global < ce - cb) return fail(VBNMF_ERR_BAD_ARG, "m_global is smaller than the partition");
-    if (X->M.shell && !(cb == 0 && ce == X->M.m))
-        return fail(VBNMF_ERR_STATE, "this matrix handle is a shell (vbnmf_matrix_shell): it holds no entries to cut a partition's layout from");
-    if (int rc = check_device(device)) return rc;
-    HIPCHECK(hipSetDevice(device));
-
-    vbnmf_engine *e = new (std::nothrow) vbnmf_engine();
-    if (!e) return fail(VBNMF_ERR_OOM, "out of host memory");
-    // VBNMF_BUILD_TIMES=1: where the seconds of this creation go (offsets from here; the layouts' own phases come from host.cpp)
-    const bool tl_on = getenv("VBNMF_BUILD_TIMES") != nullptr;
-    const auto tl_0 = std::chrono::steady_clock::now();
-    auto mark = [&](const char *what) {
-        if (tl_on) fprintf(stderr, "  engine create +%.3f s  %s\n", std::chrono::duration<double>(std::chrono::steady_clock::now() - tl_0).count(), what);
-    };
-    e->device = device;
-    e->n = X->M.n; e->m = ce - cb; e->m_global = m_global; e->col_begin = cb;
-    e->r = r; e->R = padded_rank(r);
-    if (tl_pad_R > e->R) e->R = tl_pad_R;                    // (engines of several ranks meant for ONE batch: vbnmf_set_engine_padding)
-    e->NT = sweep_threads(e->R);
-    {
-        // Blocks of the update kernels.  Fewer than one per CU on small matrices (one pass of the longer factor per block)
-        // was measured and is SLOWER: 200 x 500 at rank 3 36.1 against 30.9 us per step with 2 blocks, 2 000 x 10 000 at
-        // rank 5 82.7 against 79.2 with 59 -- the gather of the task partials is address work (64 scattered 8-byte loads
-        // per wave instruction) that 256 CUs' texture units share and 2 do not.  VBNMF_UPDATE_BLOCKS overrides (experiments).
-        int ub = kUpdateBlocks;
-        if (const char *sv = getenv("VBNMF_UPDATE_BLOCKS")) { int v = atoi(sv); if (v >= 1 && v <= kUpdateBlocks) ub = v; }
-        if (tl_grid_ub > 0) ub = std::min(ub, tl_grid_ub);          // (engines meant for a batch: vbnmf_set_engine_grid)
-        e->ub = ub;
-    }
-    e->wide = !X->M.counts_int;
-    e->partitioned = (ce - cb) != m_global;
-    if (int rc = sweep_workgroups(device, e->partitioned, e->n_wg)) { delete e; return rc; }
-    if (!e->partitioned && tl_grid_nwg > 0) e->n_wg = std::min(e->n_wg, tl_grid_nwg);
-    int rc = VBNMF_OK;
-    // This process's FIRST use of the device (HIP context, first allocation, code object: 0.1-0.15 s, once) runs on a helper
-    // thread beside the host's cut of the layouts and is waited for where the first upload needs it (a failure there
-    // resurfaces at that upload).  Later engines find the device warm and start no thread.
-    static std::atomic<bool> warm_started[16];
-    std::thread warm;
-    std::mutex warm_mu;
-    if (device < 16 && !warm_started[device].exchange(true)) warm = std::thread([device] { (void)vbnmf_device_warmup(device); });
-    auto join_warm = [&] { std::lock_guard<std::mutex> g(warm_mu); if (warm.joinable()) warm.join(); };
-    auto bail = [&](int code) { join_warm(); vbnmf_engine_destroy(e); return code; };
-
+    // nothing thrown crosses the C ABI: the guards of create_engine have joined its threads and freed the engine by here
     try {
-        std::vector<int32_t> part_order;                         // a partition orders its own cells (both sides alike)
-        if (!(cb == 0 && ce == X->M.m)) part_order = compute_cell_order(X->M, cb, ce);
-        std::shared_ptr<const Layout> shared2[2];
-        Layout own2[2];
-        const Layout *Ls[2] = {nullptr, nullptr};
-        // The two sides are cut (or taken from the matrix's cache) and uploaded SIDE BY SIDE: the cell side on a second host
-        // thread, the gene side here.  Each cut is memory-bound well before it uses all host threads, and a side's upload
-        // (200 MB of pageable memory at the headline size) runs beside the other side's cut.  Engine creation at the headline
-        // size: 0.41 -> 0.3 s on the GPU box (profiles/r05_setup_times.txt).  VBNMF_SERIAL_SIDES=1: one after the other.
-        mark("start");
-        if (cb == 0 && ce == X->M.m && !X->M.shell) (void)X->M.cell_order();          // (both sides start from it: formed once, here)
-        mark("cell order");
-        auto do_side = [&](int side) -> int {
-            int src = VBNMF_OK;
-            const int64_t nmaj = side == 0 ? e->n : e->m, nmin = side == 0 ? e->m : e->n;
-            // The geometry is that of the matrix's rank CLASS (vbnmf_matrix_plan_ranks; without a plan the class is this
-            // rank's own): the ranks of a sweep share one pair of layouts, cut for the widest rows among them.
-            const int Rc = std::max(e->R, geometry_rank ? padded_rank(geometry_rank) : plan_class(X, e->R));
-            const int64_t nnz_part = (cb == 0 && ce == X->M.m) ? X->M.nnz : X->M.colptr[ce] - X->M.colptr[cb];
-            LayoutParams lp = default_layout_params(nmaj, nmin, Rc, e->n_wg, nnz_part);
-            std::shared_ptr<const Layout> &shared = shared2[side];
-            Layout &own = own2[side];
-            const Layout *L = &own;
-            if (cb == 0 && ce == X->M.m) {                   // whole matrix: the layout may already exist (another rank, a restart)
-                shared = shared_layout(X, side, lp, src);
-                L = shared.get();
-            } else {
-                src = build_layout(X->M, cb, ce, side, lp, &part_order, own);
-            }
-            mark(side == 0 ? "gene side cut" : "cell side cut");
-            join_warm();
-            if (!src) src = upload_side(*L, e->R, device, shared ? X : nullptr, side == 0 ? e->A : e->B);
-            mark(side == 0 ? "gene side uploaded" : "cell side uploaded");
-            Ls[side] = L;
-            return src;
-        };
-        static const bool serial_sides = [] { const char *v = getenv("VBNMF_SERIAL_SIDES"); return v && v[0] == '1'; }();
-        int rc1 = VBNMF_OK;
-        std::string msg1;
-        bool oom1 = false;
-        if (serial_sides) {
-            rc = do_side(0);
-            if (!rc) rc = do_side(1);
-        } else {
-            static const int side_share = [] { const char *v = getenv("VBNMF_SIDE_THREAD_SHARE"); return v ? std::max(1, atoi(v)) : 1; }();
-            std::thread cell_side([&] {
-                try {
-                    if (hipSetDevice(device) != hipSuccess) { rc1 = VBNMF_ERR_HIP; msg1 = "hipSetDevice failed on the layout thread"; return; }
-                    set_thread_share(side_share);
-                    rc1 = do_side(1);
-                    if (rc1) msg1 = last_error_cstr();               // (error messages are per host thread)
-                } catch (const std::bad_alloc &) { oom1 = true; }
-            });
-            set_thread_share(side_share);
-            try { rc = do_side(0); } catch (...) { set_thread_share(1); cell_side.join(); throw; }
-            set_thread_share(1);
-            cell_side.join();
-            if (oom1) throw std::bad_alloc();
-            if (!rc && rc1) rc = fail(rc1, "%s", msg1.c_str());
-        }
-        if (!rc) { e->nnz = Ls[0]->nnz; e->cell_perm = Ls[0]->cell_perm; }
-        if (!rc && Ls[1]->cell_perm != e->cell_perm) rc = fail(VBNMF_ERR_STATE, "the two sides' layouts disagree on the order of the cells");
-        if (!rc) {
-            // One launch for both posterior updates (k_update2): unpartitioned engines whose blocks' work fits the kernel's
-            // table; VBNMF_NO_UPDATE_PAIR=1 keeps the two launches (A/B switch, and the form the pair is held to in
-            // tests/test_gpu_update_pair.py).
-            // Where it pays (round 5, same-box A/Bs in profiles/r05_pair_ab*.txt, r05_small_pair_ab.txt): the launch it saves is
-            // worth ~3 us of a step whatever the size, the column sums it needs cost the gene side of the sweep ~60 + 4 R
-            // instructions per SLICE.  5 000 x 20 000 at rank 8: 64.0 -> 60.1 us per step (+6 %); C2 (2 000 x 10 000 dense,
-            // rank 5) +1.9 %; C1 and the PBMC-sized sample +-0; the headline (4.9e7 entries, rank 10) -0.3 %, rank 20 -1.2 %.
-            // So: on up to 2.5e8 entries x padded rank, off beyond.  VBNMF_UPDATE_PAIR=1 / VBNMF_NO_UPDATE_PAIR=1 force it.
-            const char *np = getenv("VBNMF_NO_UPDATE_PAIR"), *fp = getenv("VBNMF_UPDATE_PAIR");
-            const bool forced = fp && fp[0] == '1';
-            const bool pays = (double)Ls[0]->nnz * (double)e->R <= 2.5e8;
-            e->pair = !e->partitioned && !(np && np[0] == '1') && (forced || pays) && Ls[0]->n_wg == Ls[1]->n_wg;
-            if (e->pair) {
-                std::vector<uint32_t> tab;
-                e->pair = build_update_table(*Ls[0], *Ls[1], e->ub, e->R, tab, e->upd_stride4, e->upd_V, e->upd_ids_off);
-                if (e->pair) {
-                    uint32_t *d = nullptr;
-                    rc = dev_upload(&d, tab);
-                    e->upd_tab = reinterpret_cast<uint4 *>(d);
-                }
-            }
-        }
+        return create_engine(CreateArgs{X, cb, ce, m_global, r, geometry_rank, device}, out);
     } catch (const std::bad_alloc &) {
-        rc = fail(VBNMF_ERR_OOM, "out of host memory building the tiled layout");
+        return fail(VBNMF_ERR_OOM, "out of host memory building the tiled layout");
+    } catch (const std::exception &ex) {
+        return fail(VBNMF_ERR_STATE, "engine creation failed: %s", ex.what());
+    } catch (...) {
+        return fail(VBNMF_ERR_STATE, "engine creation failed: unknown exception");
     }
-    join_warm();
-    if (rc) return bail(rc);
-    mark("both sides, update table");
-    {
-        // The engine's stream, before the first fill: everything that initialises the engine's own buffers below is queued ON it
-        // (hipMemsetAsync), so it is ordered with the engine's kernels.  A plain hipMemset goes to the device's null stream,
-        // which this non-blocking stream does not wait for, and may return before the fill has run: with several host threads
-        // creating engines side by side (vb_factorize(concurrent=K)) a fill queued behind the other threads' null-stream work
-        // could land AFTER the engine's first kernels had written the buffer -- zeroed block partials, a different trajectory
-        // (seen once in round 5, tests/test_gpu_end_to_end.py::test_concurrent_units_give_the_same_result).
-        // (Created HERE and not at the top: this process's first use of the device -- 0.1 s of HIP start-up -- then happens on the
-        // cell side's thread, at its upload, beside the gene side's cut, instead of in front of both.)
-        hipError_t hs;
-        if ((hs = hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking)) != hipSuccess ||
-            (hs = hipEventCreate(&e->ev0)) != hipSuccess || (hs = hipEventCreate(&e->ev1)) != hipSuccess ||
-            (hs = hipEventCreate(&e->ev2)) != hipSuccess || (hs = hipEventCreate(&e->ev3)) != hipSuccess)
-            return bail(fail(VBNMF_ERR_HIP, "engine setup failed: %s", hipGetErrorString(hs)));
-        e->own_stream = true;
-    }
-
-    if (!e->cell_perm.empty() && (rc = dev_upload(&e->d_perm, e->cell_perm))) return bail(rc);
-    e->lgx = (cb == 0 && ce == X->M.m) ? X->lgx : sum_lgamma_x1(X->M, cb, ce);
-    if (cb == 0 && ce == X->M.m) {                    // whole matrix: formed once per matrix, not per engine (a pass over X)
-        std::call_once(X->xlx_once, [&] { X->xlx = sum_xlogx(X->M, 0, X->M.m); });      // (a shell carries the value already)
-        e->xlx = X->xlx;
-    } else {
-        e->xlx = sum_xlogx(X->M, cb, ce);
-    }
-    {
-        // Cache policy of the entry stream (kernels.h: ld_stream).  What a step moves between two uses of a line: both sides' entry
-        // streams and the per-task partial rows, written and read back.  Beyond the Infinity Cache (256 MB: the headline moves
-        // 410 + 2 x 75 MB) the stream is read non-temporally so that the partial rows and the state stay on the die; inside it
-        // (C2: 130 MB; 5 000 x 20 000: 61 MB) the stream itself stays resident from step to step and the default policy is the
-        // faster one (profiles/r05_nt_ab.txt, r05_small_nt_ab.txt).  VBNMF_STREAM_NT=0 / 1 forces it.
-        const double entry_b = e->wide ? 12.0 : 4.0;
-        const double moved = entry_b * ((double)e->A.n_slots + (double)e->B.n_slots) +
-                             2.0 * 8.0 * e->R * 64.0 * ((double)e->A.n_slices + (double)e->B.n_slices);
-        e->stream_nt = moved > 200e6;
-        if (const char *v = getenv("VBNMF_STREAM_NT")) e->stream_nt = v[0] == '1';
-    }
-    mark("sum x log x");
-    static_assert(kLdsRowBase == kLdsReserveBytes, "host and device disagree on the sweep's LDS reserve");
-    e->lds_bytes = kLdsRowBase + std::max((size_t)e->A.block_width * e->A.row_slots, (size_t)e->B.block_width * e->B.row_slots) * 16;
-    if (e->lds_bytes > 160 * 1024) return bail(fail(VBNMF_ERR_BAD_ARG, "the layout's blocks need %zu bytes of LDS", e->lds_bytes));
-    {
-        std::vector<LogTabEntry> tab(kLogTabSize);
-        fill_log_table(tab.data());
-        if ((rc = dev_upload(&e->logtab, tab))) return bail(rc);
-        if ((rc = dev_alloc(&e->ctl, 1))) return bail(rc);
-        const char *nf = getenv("VBNMF_NO_CONTROL_FOLD");
-        // (partitioned engines: the evidence partials of the two sweeps must fit the fixed slots of the second all-reduce)
-        e->fold = !(nf && nf[0] == '1') && (!e->partitioned || 2 * (int64_t)e->n_wg <= kEvSlots);
-        if (e->fold && (rc = dev_alloc(&e->ctl2, 2))) return bail(rc);
-        if (e->fold || e->pair) {
-            if ((rc = dev_alloc(&e->bpW_alt, (size_t)kUpdateBlocks * (e->R + 2))) ||
-                (rc = dev_alloc(&e->bpH_alt, (size_t)kUpdateBlocks * (e->R + 2)))) return bail(rc);
-            if (hipMemsetAsync(e->bpW_alt, 0, (size_t)kUpdateBlocks * (e->R + 2) * sizeof(double), e->stream) != hipSuccess ||
-                hipMemsetAsync(e->bpH_alt, 0, (size_t)kUpdateBlocks * (e->R + 2) * sizeof(double), e->stream) != hipSuccess) return bail(fail(VBNMF_ERR_HIP, "hipMemsetAsync failed"));
-        }
-        if (e->pair) {
-            if ((rc = dev_alloc(&e->csl, (size_t)std::max<int64_t>(e->A.n_slices, 1) * e->R)) || (rc = dev_alloc(&e->csum, (size_t)e->n_wg * e->R))) return bail(rc);
-            if (hipMemsetAsync(e->csum, 0, (size_t)e->n_wg * e->R * sizeof(double), e->stream) != hipSuccess) return bail(fail(VBNMF_ERR_HIP, "hipMemsetAsync failed"));
-        }
-    }
-
-    const size_t nR = (size_t)e->n * e->R, mR = (size_t)e->m * e->R;
-    const size_t bpn = (size_t)kUpdateBlocks * (e->R + 2);
-    e->red_count = (int64_t)nR + e->R + 4;
-    if ((rc = dev_alloc(&e->lw, nR)) || (rc = dev_alloc(&e->llw, nR)) || (rc = dev_alloc(&e->ew, nR)) || (rc = dev_alloc(&e->dw, nR)) ||
-        (rc = dev_alloc(&e->lh, mR)) || (rc = dev_alloc(&e->llh, mR)) || (rc = dev_alloc(&e->eh, mR)) || (rc = dev_alloc(&e->dh, mR)) ||
-        (rc = dev_alloc(&e->bpW, bpn)) || (rc = dev_alloc(&e->bpH, bpn)) ||
-        (rc = dev_alloc(&e->red, (size_t)red_alloc_count(e))) || (rc = dev_alloc(&e->d_out, 8)))
-        return bail(rc);
-    if (e->partitioned && 2 * (int64_t)e->n_wg <= kEvSlots) { e->epart = e->red + e->red_count; e->epart_in_red = true; }
-    else if ((rc = dev_alloc(&e->epart, 2 * (size_t)e->n_wg))) return bail(rc);
-    hipError_t he;
-    if ((he = hipHostMalloc((void **)&e->h_out, kHostOut * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent)) != hipSuccess ||
-        (he = hipHostGetDevicePointer((void **)&e->h_out_dev, e->h_out, 0)) != hipSuccess)
-        return bail(fail(VBNMF_ERR_HIP, "engine setup failed: %s", hipGetErrorString(he)));
-    std::memset(e->h_out, 0, kHostOut * sizeof(double));
-    if (getenv("VBNMF_DEBUG_TIMES")) {
-        e->dbg_count = 2 * (size_t)e->n_wg * (2 + 2 * (e->NT / 64));
-        if ((rc = dev_alloc(&e->dbg, e->dbg_count))) return bail(rc);
-    }
-    if ((he = hipMemsetAsync(e->ew, 0, nR * sizeof(double), e->stream)) != hipSuccess || (he = hipMemsetAsync(e->dw, 0, nR * sizeof(double), e->stream)) != hipSuccess ||
-        (he = hipMemsetAsync(e->dh, 0, mR * sizeof(double), e->stream)) != hipSuccess || (he = hipMemsetAsync(e->bpW, 0, bpn * sizeof(double), e->stream)) != hipSuccess ||
-        (he = hipMemsetAsync(e->bpH, 0, bpn * sizeof(double), e->stream)) != hipSuccess ||
-        (he = hipMemsetAsync(e->red, 0, (size_t)red_alloc_count(e) * sizeof(double), e->stream)) != hipSuccess)
-        return bail(fail(VBNMF_ERR_HIP, "hipMemsetAsync failed: %s", hipGetErrorString(he)));
-    // (sum lgamma(x + 1) into its slot of the reduce buffer: BEHIND the fill above, on the same stream; e->lgx lives as long as the engine)
-    if (e->epart_in_red && (he = hipMemcpyAsync(e->red + e->red_count + kEvSlots, &e->lgx, sizeof(double), hipMemcpyHostToDevice, e->stream)) != hipSuccess)
-        return bail(fail(VBNMF_ERR_HIP, "hipMemcpyAsync failed: %s", hipGetErrorString(he)));
-    // creation ends with the engine's buffers in their initial state whatever else the device is doing
-    if ((he = hipStreamSynchronize(e->stream)) != hipSuccess) return bail(fail(VBNMF_ERR_HIP, "engine setup failed: %s", hipGetErrorString(he)));
-    mark("state arrays, initial fills, done");
-    *out = e;
-    return VBNMF_OK;
 }
 
 int vbnmf_engine_create_part(const vbnmf_matrix *X, int64_t cb, int64_t ce, int64_t m_global, int32_t r,
@@ -1567,14 +1666,10 @@ int launch_control(vbnmf_engine *e, double *hist_dev, bool reduced)
     const int64_t nep = 2 * (int64_t)e->n_wg;
     const double *tail = reduced ? e->red_g + (size_t)e->n * e->R : nullptr;
     const double *small = reduced ? e->red_g + (size_t)e->n * e->R + e->R + 2 : nullptr;
-    switch (e->R) {
-#define X(RR) case RR: hipLaunchKernelGGL((k_control<RR>), dim3(1), dim3(1024), 0, e->stream, e->bpW, e->bpH, e->ub, e->epart, nep, e->lgx, e->r, (double)e->n, (double)e->m_global, e->ctl, hist_dev, e->h_out_dev, tail, small); break;
-        VBNMF_FOR_EACH_R(X)
-#undef X
-        default: return fail(VBNMF_ERR_BAD_ARG, "unsupported padded rank %d", e->R);
-    }
-    HIPCHECK(hipGetLastError());
-    return VBNMF_OK;
+    return with_rank(e->R, [&](auto rt) {
+        return launch_kernel<k_control<rt()>>(e, dim3(1), 1024, 0, e->bpW, e->bpH, e->ub, e->epart, nep, e->lgx, e->r, (double)e->n,
+                                              (double)e->m_global, e->ctl, hist_dev, e->h_out_dev, tail, small);
+    });
 }
 
 // The engines one device-driven loop advances together: a single engine, or the partition engines of a local group.
@@ -2039,49 +2134,22 @@ int vbnmf_engine_run(vbnmf_engine *e, double *hyper, double fudge, int32_t max_i
 // ---------------------------------------------------------------- a batch of engines stepped by one launch (kernels.h: k_update2_batch)
 namespace {
 
-#ifdef VBNMF_DEV_FEW_RANKS
-#define VBNMF_FOR_EACH_R_BATCH(X) X(4) X(6) X(8) X(10)
-#else
-#define VBNMF_FOR_EACH_R_BATCH(X) X(2) X(4) X(6) X(8) X(10) X(12) X(14) X(16)
-#endif
-constexpr int kBatchMaxPaddedRank = 16;      // the small-matrix regime the batch is for (instantiations cost build time)
 constexpr int kBatchMax = 64;
-
-template <int R, bool WIDE>
-int launch_sweep_batch_t(vbnmf_engine *e, const SweepSide *jobs, int B)
-{
-    constexpr int NT = sweep_threads(R);
-    static std::atomic<bool> attr_set[16];
-    const void *fn = (const void *)k_sweep_batch<R, WIDE, NT, 1>;
-    if (e->device >= 16 || !attr_set[e->device].load(std::memory_order_acquire)) {
-        if (int rc = prepare_sweep_kernel(fn)) return rc;
-        if (e->device < 16) attr_set[e->device].store(true, std::memory_order_release);
-    }
-    hipLaunchKernelGGL((k_sweep_batch<R, WIDE, NT, 1>), dim3((unsigned)e->n_wg, (unsigned)B), dim3(NT), e->lds_bytes, e->stream, jobs);
-    HIPCHECK(hipGetLastError());
-    return VBNMF_OK;
-}
 
 int launch_sweep_batch(vbnmf_engine *e, const SweepSide *jobs, int B)
 {
-    switch (e->R) {
-#define X(RR) case RR: return e->wide ? launch_sweep_batch_t<RR, true>(e, jobs, B) : launch_sweep_batch_t<RR, false>(e, jobs, B);
-        VBNMF_FOR_EACH_R_BATCH(X)
-#undef X
-        default: return fail(VBNMF_ERR_BAD_ARG, "a batch serves padded ranks up to %d (this engine: %d)", kBatchMaxPaddedRank, e->R);
-    }
+    return with_batch_rank(e->R, [&](auto rt) {
+        return with_sweep_shape<rt()>(e, [&](auto s) {
+            return launch_lds_kernel<k_sweep_batch<s.R, s.WIDE, s.NT, 1>>(e, dim3((unsigned)e->n_wg, (unsigned)B), s.NT, jobs);
+        });
+    });
 }
 
 int launch_update2_batch(vbnmf_engine *e, const Upd2Job *jobs, int B)
 {
-    switch (e->R) {
-#define X(RR) case RR: hipLaunchKernelGGL((k_update2_batch<RR>), dim3((unsigned)e->ub, (unsigned)B), dim3(kUpdateThreads), 0, e->stream, jobs); break;
-        VBNMF_FOR_EACH_R_BATCH(X)
-#undef X
-        default: return fail(VBNMF_ERR_BAD_ARG, "a batch serves padded ranks up to %d (this engine: %d)", kBatchMaxPaddedRank, e->R);
-    }
-    HIPCHECK(hipGetLastError());
-    return VBNMF_OK;
+    return with_batch_rank(e->R, [&](auto rt) {
+        return launch_kernel<k_update2_batch<rt()>>(e, dim3((unsigned)e->ub, (unsigned)B), kUpdateThreads, 0, jobs);
+    });
 }
 
 // The engines a batch run takes (vb: vbnmf_batch_run, else vbnmf_batch_ml_run): no null or repeated handle; unpartitioned, the
@@ -2171,18 +2239,16 @@ int vbnmf_batch_run(vbnmf_engine **engs, int32_t count, double *hyper, double fu
         for (int v = 0; v < 3; v++) {
             const int t = v == 0 ? 1 : (v == 1 ? 3 : 2);
             Upd2Job &J = ju[(size_t)v * B + b];
-            J.W.part = e->A.part; J.W.nmaj = e->n; J.W.l = e->lw; J.W.ll = e->llw; J.W.e = e->ew; J.W.d = e->dw;
-            J.H.part = e->B.part; J.H.nmaj = e->m; J.H.l = e->lh; J.H.ll = e->llh; J.H.e = e->eh; J.H.d = e->dh;
-            J.W.bp_prev = Wt[(t - 1) & 1]; J.W.bp = Wt[t & 1];
-            J.H.bp_prev = Ht[(t - 1) & 1]; J.H.bp = Ht[t & 1];
+            J.W = upd_side(e, true, Wt[(t - 1) & 1], Wt[t & 1]);
+            J.H = upd_side(e, false, Ht[(t - 1) & 1], Ht[t & 1]);
             J.T = UpdTable{e->upd_tab, e->upd_stride4, e->upd_V, e->upd_ids_off};
             J.r = e->r; J.nb = e->ub; J.ncs = e->n_wg; J.csum = e->csum; J.fudge = fudge;
             J.fold = vb_fold(e, t, hist);
         }
         for (int par = 0; par < 2; par++) {                       // the sweep of step t reads the stop flag that step's update left
             SweepSide *s = &js[((size_t)par * B + b) * 2];
-            s[0] = sweep_side_args(e, e->A, true, e->epart);
-            s[1] = sweep_side_args(e, e->B, false, e->epart + e->n_wg);
+            s[0] = sweep_side_args(e, true);
+            s[1] = sweep_side_args(e, false);
             s[0].stop = s[1].stop = &(e->ctl2 + par)->stop;
         }
     }
@@ -2225,42 +2291,22 @@ int vbnmf_batch_run(vbnmf_engine **engs, int32_t count, double *hyper, double fu
 
 namespace {
 
-template <int R, bool WIDE, bool LOGTERM>
-int launch_sweep1_batch_t(vbnmf_engine *e, const SweepSide *jobs, int B)
-{
-    constexpr int NT = sweep_threads(R);
-    static std::atomic<bool> attr_set[16];
-    const void *fn = (const void *)k_sweep1_batch<R, WIDE, LOGTERM, NT>;
-    if (e->device >= 16 || !attr_set[e->device].load(std::memory_order_acquire)) {
-        if (int rc = prepare_sweep_kernel(fn)) return rc;
-        if (e->device < 16) attr_set[e->device].store(true, std::memory_order_release);
-    }
-    hipLaunchKernelGGL((k_sweep1_batch<R, WIDE, LOGTERM, NT>), dim3((unsigned)e->n_wg, (unsigned)B), dim3(NT), e->lds_bytes, e->stream, jobs);
-    HIPCHECK(hipGetLastError());
-    return VBNMF_OK;
-}
-
 int launch_sweep1_batch(vbnmf_engine *e, const SweepSide *jobs, int B, bool logterm)
 {
-    switch (e->R) {
-#define X(RR) case RR: return e->wide ? (logterm ? launch_sweep1_batch_t<RR, true, true>(e, jobs, B) : launch_sweep1_batch_t<RR, true, false>(e, jobs, B)) \
-                                      : (logterm ? launch_sweep1_batch_t<RR, false, true>(e, jobs, B) : launch_sweep1_batch_t<RR, false, false>(e, jobs, B));
-        VBNMF_FOR_EACH_R_BATCH(X)
-#undef X
-        default: return fail(VBNMF_ERR_BAD_ARG, "a batch serves padded ranks up to %d (this engine: %d)", kBatchMaxPaddedRank, e->R);
-    }
+    return with_batch_rank(e->R, [&](auto rt) {
+        return with_sweep_shape<rt()>(e, [&](auto s) {
+            return with_flag(logterm, [&](auto lt) {
+                return launch_lds_kernel<k_sweep1_batch<s.R, s.WIDE, lt(), s.NT>>(e, dim3((unsigned)e->n_wg, (unsigned)B), s.NT, jobs);
+            });
+        });
+    });
 }
 
 int launch_ml_update_batch(vbnmf_engine *e, const MlUpdJob *jobs, int B)
 {
-    switch (e->R) {
-#define X(RR) case RR: hipLaunchKernelGGL((k_ml_update_batch<RR>), dim3((unsigned)e->ub, (unsigned)B), dim3(kUpdateThreads), 0, e->stream, jobs); break;
-        VBNMF_FOR_EACH_R_BATCH(X)
-#undef X
-        default: return fail(VBNMF_ERR_BAD_ARG, "a batch serves padded ranks up to %d (this engine: %d)", kBatchMaxPaddedRank, e->R);
-    }
-    HIPCHECK(hipGetLastError());
-    return VBNMF_OK;
+    return with_batch_rank(e->R, [&](auto rt) {
+        return launch_kernel<k_ml_update_batch<rt()>>(e, dim3((unsigned)e->ub, (unsigned)B), kUpdateThreads, 0, jobs);
+    });
 }
 
 }  // namespace
@@ -2310,9 +2356,9 @@ int vbnmf_batch_ml_run(vbnmf_engine **engs, int32_t count, int32_t prior, double
             J.r = e->r; J.other_nb = e->ub; J.prior = prior;
             J.stage_ids = stage_ids(e->A, e->ub);
             J.fold = MlFold{};
-            SweepSide g = sweep_side_args(e, e->A, true, e->epart);
+            SweepSide g = sweep_side_args(e, true);
             g.logterm = 0;
-            SweepSide c = sweep_side_args(e, e->B, false, e->epart + e->n_wg);
+            SweepSide c = sweep_side_args(e, false);
             c.logterm = 1;
             g.stop = c.stop = stop;
             jg[(size_t)par * B + b] = g; jc[(size_t)par * B + b] = c;
@@ -2600,19 +2646,8 @@ int vbnmf_engine_ml_set_state(vbnmf_engine *e, const double *w, const double *h)
         return fail(VBNMF_ERR_OOM, "out of host memory staging the state");
     }
     // colSums(w) block partials, then the cell-side statistics the first H update starts from
-    switch (e->R) {
-#define X(RR) case RR: hipLaunchKernelGGL((k_prime<RR>), dim3(e->ub), dim3(kUpdateThreads), 0, e->stream, e->n, e->r, e->lw, e->llw, e->lw, e->bpW); break;
-        VBNMF_FOR_EACH_R(X)
-#undef X
-        default: return fail(VBNMF_ERR_BAD_ARG, "unsupported padded rank %d", e->R);
-    }
-    HIPCHECK(hipGetLastError());
-    switch (e->R) {                                  // rowSums(h) block partials, for the likelihood of the loaded pair
-#define X(RR) case RR: hipLaunchKernelGGL((k_prime<RR>), dim3(e->ub), dim3(kUpdateThreads), 0, e->stream, e->m, e->r, e->lh, e->llh, e->lh, e->bpH); break;
-        VBNMF_FOR_EACH_R(X)
-#undef X
-    }
-    HIPCHECK(hipGetLastError());
+    if (int rc = launch_prime(e, true, e->lw)) return rc;
+    if (int rc = launch_prime(e, false, e->lh)) return rc;       // rowSums(h) block partials, for the likelihood of the loaded pair
     const bool timing = e->timing;
     e->timing = false;                               // the priming sweep is not a step
     int rc = launch_sweep1(e, false);
@@ -2688,15 +2723,14 @@ int vbnmf_engine_ml_run(vbnmf_engine *e, int32_t prior, double gamma_a, double g
         if (!q) q = launch_ml_update(e, true, prior, gamma_a, gamma_b, eps);
         if (!q) q = launch_sweep1(e, false);
         if (q) return q;
-        switch (e->R) {
-#define X(RR) case RR: hipLaunchKernelGGL((k_ml_control<RR>), dim3(1), dim3(1024), 0, e->stream, e->bpW, e->bpH, e->ub, e->epart + e->n_wg, (int64_t)e->n_wg, e->xlx, e->r, (double)e->n, (double)e->m, e->ctl, hist ? e->h_hist_dev : nullptr, e->h_out_dev); break;
-            VBNMF_FOR_EACH_R(X)
-#undef X
-            default: return fail(VBNMF_ERR_BAD_ARG, "unsupported padded rank %d", e->R);
-        }
-        hipError_t le = hipGetLastError();
-        if (le != hipSuccess) return fail(VBNMF_ERR_HIP, "k_ml_control launch failed: %s", hipGetErrorString(le));
-        return VBNMF_OK;
+        return with_rank(e->R, [&](auto rt) {
+            hipLaunchKernelGGL((k_ml_control<rt()>), dim3(1), dim3(1024), 0, e->stream, e->bpW, e->bpH, e->ub, e->epart + e->n_wg,
+                               (int64_t)e->n_wg, e->xlx, e->r, (double)e->n, (double)e->m, e->ctl, hist ? e->h_hist_dev : nullptr,
+                               e->h_out_dev);
+            hipError_t le = hipGetLastError();
+            if (le != hipSuccess) return fail(VBNMF_ERR_HIP, "k_ml_control launch failed: %s", hipGetErrorString(le));
+            return (int)VBNMF_OK;
+        });
     });
     if ((rc = S.end(rc))) return rc;
     read_out(&e, 1, it_out, nullptr, lk_out, reason_out, nullptr, history, history_rows, 1);
@@ -2795,22 +2829,13 @@ namespace {
 // major straight into `target`.
 int spmm_device(vbnmf_engine *e, bool gene_side, double *target)
 {
-    SweepSide a = sweep_side_args(e, gene_side ? e->A : e->B, gene_side, gene_side ? e->epart : e->epart + e->n_wg);
+    SweepSide a = sweep_side_args(e, gene_side);
     a.logterm = 0;
     a.stop = nullptr;
-    int rc = VBNMF_ERR_BAD_ARG;
-    switch (e->R) {
-#define X(RR) case RR: rc = launch_spmm_r<RR>(e, a); break;
-        VBNMF_FOR_EACH_R(X)
-#undef X
-        default: return fail(VBNMF_ERR_BAD_ARG, "unsupported padded rank %d", e->R);
-    }
-    if (rc) return rc;
-    const DeviceSide &S = gene_side ? e->A : e->B;
-    const int64_t cnt = (gene_side ? e->n : e->m) * e->R;
-    hipLaunchKernelGGL(k_pack, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, e->stream, S.part, S.inv_ptr, S.inv_task, gene_side ? e->n : e->m, e->R, target);
-    HIPCHECK(hipGetLastError());
-    return VBNMF_OK;
+    if (int rc = launch_spmm(e, a)) return rc;
+    const SideView v = side_view(e, gene_side);
+    const int64_t cnt = v.nmaj * e->R;
+    return launch_kernel<k_pack>(e, dim3((unsigned)((cnt + 255) / 256)), 256, 0, v.S.part, v.S.inv_ptr, v.S.inv_task, v.nmaj, e->R, target);
 }
 
 // work space of the truncated SVD: [gram partials kGramBlocks * R*R | S (R*R) | S2 (R*R) | vals (R)]
@@ -2826,39 +2851,25 @@ SvdWs svd_ws(vbnmf_engine *e)
 int launch_gram(vbnmf_engine *e, const double *A, int64_t N)
 {
     SvdWs w = svd_ws(e);
-    switch (e->R) {
-#define X(RR) case RR: hipLaunchKernelGGL((k_gram<RR>), dim3(kGramBlocks), dim3(1024), 0, e->stream, A, N, w.gp); break;
-        VBNMF_FOR_EACH_R_UP_TO_64(X)
-#undef X
-        default: return fail(VBNMF_ERR_BAD_ARG, "unsupported padded rank %d", e->R);
-    }
-    HIPCHECK(hipGetLastError());
-    return VBNMF_OK;
+    return with_rank_up_to_64(e->R, [&](auto rt) {
+        return launch_kernel<k_gram<rt()>>(e, dim3(kGramBlocks), 1024, 0, A, N, w.gp);
+    });
 }
 
 int launch_small(vbnmf_engine *e, int mode, bool want_s2, double *vals_host, double seq)
 {
     SvdWs w = svd_ws(e);
-    switch (e->R) {
-#define X(RR) case RR: hipLaunchKernelGGL((k_small<RR>), dim3(1), dim3(1024), 0, e->stream, w.gp, kGramBlocks, e->r, mode, w.S, want_s2 ? w.S2 : nullptr, w.vals, vals_host, seq, e->svd_status); break;
-        VBNMF_FOR_EACH_R_UP_TO_64(X)
-#undef X
-        default: return fail(VBNMF_ERR_BAD_ARG, "unsupported padded rank %d", e->R);
-    }
-    HIPCHECK(hipGetLastError());
-    return VBNMF_OK;
+    return with_rank_up_to_64(e->R, [&](auto rt) {
+        return launch_kernel<k_small<rt()>>(e, dim3(1), 1024, 0, w.gp, kGramBlocks, e->r, mode, w.S, want_s2 ? w.S2 : nullptr, w.vals,
+                                            vals_host, seq, e->svd_status);
+    });
 }
 
 int launch_apply(vbnmf_engine *e, const double *A, const double *S, int64_t N, double *B)
 {
-    switch (e->R) {
-#define X(RR) case RR: hipLaunchKernelGGL((k_apply<RR>), dim3((unsigned)((N + 255) / 256)), dim3(256), 0, e->stream, A, S, N, B); break;
-        VBNMF_FOR_EACH_R_UP_TO_64(X)
-#undef X
-        default: return fail(VBNMF_ERR_BAD_ARG, "unsupported padded rank %d", e->R);
-    }
-    HIPCHECK(hipGetLastError());
-    return VBNMF_OK;
+    return with_rank_up_to_64(e->R, [&](auto rt) {
+        return launch_kernel<k_apply<rt()>>(e, dim3((unsigned)((N + 255) / 256)), 256, 0, A, S, N, B);
+    });
 }
 
 // A <- orthonormal basis of range(A), A tall [N][R]: CholeskyQR twice (Gram matrix, its Cholesky factor's inverse,
@@ -2972,29 +2983,17 @@ int vbnmf_engine_spmm(vbnmf_engine *e, int32_t transpose, const double *B, doubl
     // the factor arrays serve as operand storage: whatever state the engine held is gone
     e->has_state = false; e->stats_ready = false; e->step_pending = false; e->prime_pending = false; e->ml_ready = false;
     const bool gene_side = transpose == 0;             // C = X t(B): lanes own genes and gather rows of B (one per cell)
-    const int64_t n_in = gene_side ? e->m : e->n, n_out = gene_side ? e->n : e->m;
-    double *operand = gene_side ? e->lh : e->lw;       // gathered through LDS
-    double *dense = gene_side ? e->ew : e->eh;         // [n_out][R] result before the download
+    const SideView out = side_view(e, gene_side), in = side_view(e, !gene_side);
+    const int64_t n_in = in.nmaj, n_out = out.nmaj;
+    double *operand = in.l;                            // gathered through LDS
+    double *dense = out.e;                             // [n_out][R] result before the download
     try {
         std::vector<double> tmp;
         to_index_major(B, n_in, e->r, e->R, gene_side, tmp, gene_side ? &e->cell_perm : nullptr);     // B: one row per cell on the gene side
         HIPCHECK(hipMemcpyAsync(operand, tmp.data(), tmp.size() * sizeof(double), hipMemcpyHostToDevice, e->stream));
         HIPCHECK(hipStreamSynchronize(e->stream));
-        SweepSide a = sweep_side_args(e, gene_side ? e->A : e->B, gene_side, gene_side ? e->epart : e->epart + e->n_wg);
-        a.logterm = 0;
-        a.stop = nullptr;
-        int rc = VBNMF_ERR_BAD_ARG;
-        switch (e->R) {
-#define X(RR) case RR: rc = launch_spmm_r<RR>(e, a); break;
-            VBNMF_FOR_EACH_R(X)
-#undef X
-            default: return fail(VBNMF_ERR_BAD_ARG, "unsupported padded rank %d", e->R);
-        }
-        if (rc) return rc;
-        const DeviceSide &S = gene_side ? e->A : e->B;
+        if (int rc = spmm_device(e, gene_side, dense)) return rc;
         const int64_t cnt = n_out * e->R;
-        hipLaunchKernelGGL(k_pack, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, e->stream, S.part, S.inv_ptr, S.inv_task, n_out, e->R, dense);
-        HIPCHECK(hipGetLastError());
         tmp.resize((size_t)cnt);
         HIPCHECK(hipMemcpyAsync(tmp.data(), dense, tmp.size() * sizeof(double), hipMemcpyDeviceToHost, e->stream));
         HIPCHECK(hipStreamSynchronize(e->stream));
