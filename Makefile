@@ -17,6 +17,14 @@ $(OBJ)/host.o: $(CSRC)/host.cpp $(HOST_HDRS)
 	mkdir -p $(OBJ)
 	$(HIPCC) $(CXXFLAGS) -c -o $@ $<
 
+$(OBJ)/layout.o: $(CSRC)/layout.cpp $(HOST_HDRS)
+	mkdir -p $(OBJ)
+	$(HIPCC) $(CXXFLAGS) -c -o $@ $<
+
+$(OBJ)/blob.o: $(CSRC)/blob.cpp $(HOST_HDRS)
+	mkdir -p $(OBJ)
+	$(HIPCC) $(CXXFLAGS) -c -o $@ $<
+
 $(OBJ)/mtx.o: $(CSRC)/mtx.cpp $(HOST_HDRS)
 	mkdir -p $(OBJ)
 	$(HIPCC) $(CXXFLAGS) -c -o $@ $<
@@ -29,7 +37,7 @@ $(OBJ)/engine.o: $(CSRC)/engine.hip $(DEV_HDRS)
 	mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c -o $@ -x hip $<
 
-$(LIB): $(OBJ)/host.o $(OBJ)/mtx.o $(OBJ)/order.o $(OBJ)/engine.o
+$(LIB): $(OBJ)/host.o $(OBJ)/layout.o $(OBJ)/blob.o $(OBJ)/mtx.o $(OBJ)/order.o $(OBJ)/engine.o
 	mkdir -p $(dir $(LIB))
 	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) -o $@ $^ -pthread
 

@@ -18,6 +18,7 @@ namespace vbnmf {
 // ---- error plumbing: one message per host thread, surfaced by vbnmf_last_error() ----
 void set_error(const char *fmt, ...);
 int fail(int code, const char *fmt, ...);
+int env_int(const char *name, int dflt);    // an integer environment switch (unset or empty: dflt)
 
 // ---- simple fork-join over [0, count) with std::thread (no OpenMP runtime needed) ----
 void parallel_for(int64_t count, const std::function<void(int64_t begin, int64_t end, int tid)> &fn,
@@ -84,13 +85,15 @@ double sum_xlogx(const Matrix &X, int64_t cb, int64_t ce);
 // A *task* is a run of at most `max_len` stored entries of one major (gene on side 0, cell
 // on side 1) whose minors fall in one minor block; one lane of the sweep kernel owns it.
 // Tasks of a block are sorted by length (descending) and cut into *slices* of 64 (one
-// wavefront).  Each block's slices are dealt out in strides so that any contiguous stretch of
-// the resulting work list holds a mix of long and short slices; the list is cut into `n_wg`
-// stretches of equal cost, one per persistent workgroup; a *segment* is the part of a
-// stretch that lies in one block (the workgroup stages that block of the gathered factor in
-// LDS once per segment).  Slices are numbered in processing order -- workgroup by workgroup,
-// segment by segment, longest first inside a segment -- and the waves of the workgroup pull
-// them through a ticket counter, so a segment is just the id range [seg_ptr[g], seg_ptr[g+1]).
+// wavefront).  Whole persistent workgroups are apportioned to the blocks in proportion to the
+// blocks' modelled cost, and a block's slices are dealt to its workgroups longest-processing-time
+// first (costliest slice to the least loaded workgroup), so every share holds the same cost and the
+// same mix of long and short slices; with more blocks than workgroups, whole blocks are bin-packed
+// onto workgroups instead.  A *segment* is the part of a workgroup's share that lies in one block
+// (the workgroup stages that block of the gathered factor in LDS once per segment).  Slices are
+// numbered in processing order -- workgroup by workgroup, segment by segment, longest first
+// inside a segment -- and the waves of the workgroup pull them through a ticket counter, so a
+// segment is just the id range [seg_ptr[g], seg_ptr[g+1]).
 constexpr int kLanes = 64;          // one slice = one wavefront
 constexpr int kUnroll = 4;          // entries per lane per 16-byte load
 constexpr int kWidthQuantum = 4;    // slice widths are multiples of this (one 4-entry group of the packed stream)
@@ -135,7 +138,8 @@ struct Layout {
     std::vector<int32_t> slice_width;    // n_slices ; entries per lane, multiple of 4
     std::vector<int64_t> slice_off;      // n_slices ; first slot of the slice
     std::vector<int32_t> slice_block;    // n_slices ; minor block (host-side bookkeeping / tests)
-    std::vector<int32_t> slice_fast;     // n_slices ; leading entries per lane that are stored ones in EVERY lane (multiple of 8)
+    std::vector<int32_t> slice_fast;     // n_slices ; low half: leading entries per lane that are stored ones in EVERY lane (multiple
+                                         // of 8); high half: ... that are ones or twos in every lane (ones first; >= the low half)
     std::vector<int64_t> block_start;    // n_blocks + 1 ; first minor of each block (blocks differ in width, see build_layout)
     std::vector<int32_t> seg_block;      // n_segs
     std::vector<int32_t> wg_seg0;        // n_wg + 1
@@ -163,6 +167,11 @@ struct LayoutParams {
     int32_t n_wg;          // persistent workgroups of the sweep kernel
     int32_t row_slots;     // 16-byte LDS slots per staged factor row at this rank (lds_row_bytes / 16)
 };
+// the same geometry: what the layout cache keys on (with the side)
+inline bool operator==(const LayoutParams &a, const LayoutParams &b)
+{
+    return a.block_width == b.block_width && a.block_cap == b.block_cap && a.max_len == b.max_len && a.n_wg == b.n_wg && a.row_slots == b.row_slots;
+}
 
 // Padded rank used on the device (even, so a factor row is a whole number of 16-byte LDS reads).
 // Ranks up to 32 are padded to even; above, SP = 2 (to 64) or 4 (to 128) lanes of the sweep share a task's R * SP
@@ -214,6 +223,16 @@ int build_layout(const Matrix &X, int64_t cb, int64_t ce, int side, const Layout
 std::vector<int32_t> compute_cell_order(const Matrix &X, int64_t cb, int64_t ce);
 
 const char *last_error_cstr();
+
+// Argument checks that several ABI entries share (message set, VBNMF_ERR_BAD_ARG): the dimensions of a matrix; the side,
+// rank and workgroup count that name a geometry (entries without a workgroup count leave it out).
+int check_dims(int64_t n, int64_t m);
+int check_geometry_args(int side, int rank, int n_wg = 1);
+
+// host.cpp: transposes a canonical compressed matrix (see the definition).  Instantiated for std::vector and BigVec outputs.
+template <class VI, class VD>
+void transpose_compressed(int64_t nouter, int64_t ninner, const int64_t *ptr, const int32_t *idx, const double *val,
+                          int32_t idx_offset, std::vector<int64_t> &tptr, VI &tidx, VD &tval, const int32_t *perm);
 
 // Canonical matrix from compressed columns in any order within a column (duplicates summed, zeros dropped).
 int matrix_from_csc(int64_t n, int64_t m, const int32_t *p, const int32_t *i, const double *x, Matrix &X);

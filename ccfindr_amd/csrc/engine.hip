@@ -958,7 +958,7 @@ struct CreateArgs {
     bool whole_matrix() const { return cb == 0 && ce == X->M.m; }
 };
 
-// VBNMF_BUILD_TIMES=1: where the seconds of this creation go (offsets from here; the layouts' own phases come from host.cpp)
+// VBNMF_BUILD_TIMES=1: where the seconds of this creation go (offsets from here; the layouts' own phases come from layout.cpp)
 struct BuildClock {
     const bool on = getenv("VBNMF_BUILD_TIMES") != nullptr;
     const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();

@@ -179,7 +179,7 @@ constexpr uint32_t kLdsEvBase = kLdsTabBytes;
 constexpr uint32_t kLdsCtrBase = kLdsEvBase + kLdsEvSlots * sizeof(double);
 constexpr uint32_t kLdsRowBase = kLdsCtrBase + 16;
 // One row (R doubles) of the staged factor block, by byte offset into the block.  The sweep kernels own no static
-// LDS, so their dynamic LDS starts at address 0 (launch_sweep_t checks it) and the row address is the offset itself
+// LDS, so their dynamic LDS starts at address 0 (launch_lds_kernel checks it) and the row address is the offset itself
 // plus kLdsRowBase, a constant the ds_read instructions carry in their immediate: no VALU address arithmetic.
 template <int R>
 __device__ __forceinline__ void lds_row(const double2 *__restrict__ ldsG, uint32_t byte_off, double2 (&gv)[R / 2])

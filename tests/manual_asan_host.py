@@ -3,7 +3,8 @@
 layout, Matrix Market reader / writer); GPU sanitizers are not available on the pool, so this is the CPU build only.
 
     g++ -O1 -g -std=c++17 -fPIC -shared -fsanitize=address,undefined -fno-omit-frame-pointer \\
-        -o /tmp/libhost_asan.so ccfindr_amd/csrc/host.cpp ccfindr_amd/csrc/mtx.cpp -pthread
+        -o /tmp/libhost_asan.so ccfindr_amd/csrc/host.cpp ccfindr_amd/csrc/layout.cpp ccfindr_amd/csrc/blob.cpp \\
+        ccfindr_amd/csrc/order.cpp ccfindr_amd/csrc/mtx.cpp -pthread
     LD_PRELOAD=$(g++ -print-file-name=libasan.so):$(g++ -print-file-name=libubsan.so) ASAN_OPTIONS=detect_leaks=0 \\
         python3 tests/manual_asan_host.py /tmp/libhost_asan.so
 
