@@ -103,6 +103,8 @@ SIGNATURES = {
     "vbnmf_batch_run": (ctypes.c_int, [_VPP, _I32, c_double_p, _D, _I32, _D, _I32, _I32, c_int32_p, c_int32_p, c_double_p,
                                        c_double_p, c_int32_p, c_double_p, _I64]),
     "vbnmf_batch_ml_run": (ctypes.c_int, [_VPP, _I32, _I32, _D, _D, _I32, _D, c_int32_p, c_double_p, c_int32_p, c_double_p, _I64]),
+    "vbnmf_batch_ml_run_connectivity": (ctypes.c_int, [_VPP, _I32, _I32, _D, _D, _I32, _I32, c_int32_p, c_double_p, c_int32_p, c_double_p,
+                                                       _I64, c_int64_p, _I64]),
     "vbnmf_comm_unique_id": (ctypes.c_int, [_VP, _I64]),
     "vbnmf_comm_create": (ctypes.c_int, [_VP, _I64, _I32, _I32, _I32, _VPP]),
     "vbnmf_comm_create_local": (ctypes.c_int, [_I32, _I32, _VPP]),
@@ -129,6 +131,8 @@ SIGNATURES = {
     "vbnmf_engine_ml_set_state": (ctypes.c_int, [_VP, c_double_p, c_double_p]),
     "vbnmf_engine_ml_step": (ctypes.c_int, [_VP, _I32, _D, _D, c_double_p]),
     "vbnmf_engine_ml_run": (ctypes.c_int, [_VP, _I32, _D, _D, _I32, _D, c_int32_p, c_double_p, c_int32_p, c_double_p, _I64]),
+    "vbnmf_engine_ml_run_connectivity": (ctypes.c_int, [_VP, _I32, _D, _D, _I32, _I32, c_int32_p, c_double_p, c_int32_p, c_double_p, _I64,
+                                                        c_int64_p, _I64]),
     "vbnmf_engine_ml_likelihood": (ctypes.c_int, [_VP, c_double_p]),
     "vbnmf_engine_ml_get_state": (ctypes.c_int, [_VP, c_double_p, c_double_p]),
     "vbnmf_ml_update_dense": (ctypes.c_int, [_I64, _I64, _I32, c_double_p, c_double_p, c_double_p, _I32, _D, _D,

@@ -238,6 +238,8 @@ struct vbnmf_engine {
     int ids_cur = 0;
     bool ids_valid = false;
     unsigned long long *d_table = nullptr;    // [(r+1)^2 + 1] contingency table of two labelings, then the pair count
+    unsigned long long *d_ctab = nullptr;     // [4][(r+1)^2] the tables of the device-driven connectivity rule (mlnmf.h: MlConn)
+    size_t chg_off = 0;                       // ... and where its per-step counts start in h_hist (behind the run's history rows)
     double *svd_ws = nullptr;         // truncated SVD work space: Gram block partials, two k x k matrices, values
     int32_t *svd_status = nullptr;
     int r = 0, R = 0, NT = 0, n_wg = 0;
@@ -1314,7 +1316,7 @@ void vbnmf_engine_destroy(vbnmf_engine *e)
     dev_free(e->lh); dev_free(e->llh); dev_free(e->eh); dev_free(e->dh);
     if (!e->epart_in_red) dev_free(e->epart);
     dev_free(e->bpW); dev_free(e->bpH); dev_free(e->csl); dev_free(e->csum); dev_free(e->upd_tab);
-    dev_free(e->d_perm); dev_free(e->d_ids[0]); dev_free(e->d_ids[1]); dev_free(e->d_table); dev_free(e->svd_ws); dev_free(e->svd_status);
+    dev_free(e->d_perm); dev_free(e->d_ids[0]); dev_free(e->d_ids[1]); dev_free(e->d_table); dev_free(e->d_ctab); dev_free(e->svd_ws); dev_free(e->svd_status);
     dev_free(e->red); dev_free(e->red_g); dev_free(e->d_out);
     for (hipEvent_t ev : e->ev_ring) (void)hipEventDestroy(ev);
     if (e->cstream) (void)hipStreamDestroy(e->cstream); dev_free(e->dbg); dev_free(e->logtab); dev_free(e->ctl);
@@ -2069,6 +2071,62 @@ LoopCtl ml_ctl(double tol, int32_t max_it)
     return c;
 }
 
+// counters of one (r+1) x (r+1) table of the connectivity rule (mlnmf.h: MlConn)
+size_t conn_table_count(const vbnmf_engine *e) { return (size_t)(e->r + 1) * (e->r + 1); }
+
+// ... under criterion = 'connectivity' (R/factorize.R:198-208): stop once the labels have stood still for ncnn_step steps
+LoopCtl ml_conn_ctl(int32_t max_it, int32_t ncnn_step)
+{
+    LoopCtl c = ml_ctl(0.0, max_it);
+    c.criterion = 1; c.zstep = 0; c.ncnn_step = ncnn_step;                // zstep <- 0 (:194)
+    return c;
+}
+
+// What that rule needs on an engine beside the ML state: the two label arrays and the four tables ...
+int conn_alloc(vbnmf_engine *e)
+{
+    for (int q = 0; q < 2; q++)
+        if (!e->d_ids[q]) { if (int rc = dev_alloc(&e->d_ids[q], (size_t)e->m)) return rc; }
+    if (!e->d_ctab) { if (int rc = dev_alloc(&e->d_ctab, 4 * conn_table_count(e))) return rc; }
+    return VBNMF_OK;
+}
+
+// ... the tables zero as the run starts: queued on the stream the run's launches follow (call it inside the RunScope)
+int conn_zero(vbnmf_engine *e)
+{
+    HIPCHECK(hipMemsetAsync(e->d_ctab, 0, 4 * conn_table_count(e) * sizeof(unsigned long long), e->stream));
+    return VBNMF_OK;
+}
+
+// Step t's share of them (mlnmf.h: MlConn): labels by parity, tables by t & 3.  The control step of step t reads table t & 3:
+// it sits in step t + 1's fold (tab_read), or takes conn_step(t + 1) as a kernel of its own.
+MlConn conn_step(const vbnmf_engine *e, int t, bool changes)
+{
+    const size_t q2 = conn_table_count(e);
+    MlConn c{};
+    c.ids_out = e->d_ids[t & 1];
+    c.ids_prev = t > 1 ? e->d_ids[(t - 1) & 1] : nullptr;
+    c.tab_add = e->d_ctab + (size_t)(t & 3) * q2;
+    c.tab_zero = e->d_ctab + (size_t)((t + 1) & 3) * q2;
+    c.tab_read = e->d_ctab + (size_t)((t - 1) & 3) * q2;
+    c.changes = changes ? reinterpret_cast<int64_t *>(e->h_hist_dev + e->chg_off) : nullptr;
+    c.npair = e->m * (e->m - 1) / 2;
+    return c;
+}
+
+// After such a run the labels of the last step executed are the engine's "previous labels" (vbnmf_engine_cluster_changes);
+// changes: the nchange of every step run, from the pinned block behind the history.
+void conn_finish(vbnmf_engine *const *engs, int count, int64_t *changes, int64_t changes_rows)
+{
+    for (int b = 0; b < count; b++) {
+        vbnmf_engine *e = engs[b];
+        const int it = (int)e->h_out[5];
+        e->ids_cur = it & 1;
+        e->ids_valid = it >= 1;
+        if (changes && it > 0) std::memcpy(changes + (size_t)b * changes_rows, e->h_hist + e->chg_off, (size_t)it * sizeof(int64_t));
+    }
+}
+
 int run_group(const LoopGroup &G, double *hyper, double fudge, int32_t max_it, double tol, int32_t n0, int32_t dn,
               const int32_t *flags, int32_t *it_out, double *lk0_out, double *lkh_out, int32_t *reason_out,
               double *history, int64_t history_rows)
@@ -2313,32 +2371,35 @@ int launch_ml_update_batch(vbnmf_engine *e, const MlUpdJob *jobs, int B)
 
 extern "C" {
 
-// The device-driven ML-NMF loops (vbnmf_engine_ml_run; factorize() under criterion = 'likelihood', reference
-// R/factorize.R:194-213) of `count` engines of ONE rank on ONE matrix -- the `nrun` restarts factorize() makes of every rank
-// (R/factorize.R:181; its default is nrun = 20) -- stepped together: four launches per step for the whole batch.  Per engine
-// the results are those of vbnmf_engine_ml_run on it alone, bit for bit.  it_out, lk_out, reason_out: [count]; history (or
-// NULL): [count][history_rows], history_rows >= max_it.  Engines as for vbnmf_batch_run, their states set by ml_set_state.
-int vbnmf_batch_ml_run(vbnmf_engine **engs, int32_t count, int32_t prior, double gamma_a, double gamma_b, int32_t max_it, double tol,
-                       int32_t *it_out, double *lk_out, int32_t *reason_out, double *history, int64_t history_rows)
+}  // extern "C"
+
+namespace {
+
+// The batch's ML loops under either stopping rule (ncnn_step 0: the likelihood's, with tol); arguments checked by the entries.
+int batch_ml_run(vbnmf_engine **engs, int32_t count, int32_t prior, double gamma_a, double gamma_b, int32_t max_it, double tol,
+                 int32_t ncnn_step, int32_t *it_out, double *lk_out, int32_t *reason_out, double *history, int64_t history_rows,
+                 int64_t *changes, int64_t changes_rows)
 {
-    if (!engs) return fail(VBNMF_ERR_BAD_ARG, "NULL argument");
-    if (count < 1 || count > kBatchMax) return fail(VBNMF_ERR_BAD_ARG, "a batch holds 1 to %d engines", kBatchMax);
-    if (max_it < 1) return fail(VBNMF_ERR_BAD_ARG, "max_it must be >= 1");
-    if (history && history_rows < max_it) return fail(VBNMF_ERR_BAD_ARG, "history needs max_it doubles per engine");
     const int B = count;
-    if (int rc = batch_admit(engs, B, false, history ? (size_t)max_it : 0)) return rc;
+    const bool conn = ncnn_step > 0, chg = changes != nullptr;
+    if (int rc = batch_admit(engs, B, false, (history || chg) ? (size_t)max_it * (chg ? 2 : 1) : 0)) return rc;
     vbnmf_engine *e0 = engs[0];
     const double eps = 2.220446049250313e-16;
 
     const bool hist = history != nullptr;
-    // jobs: the H update's of step 1, of the odd and of the even steps; the W update's and the two sweeps' by parity
-    std::vector<MlUpdJob> jh((size_t)3 * B), jw((size_t)2 * B);
+    // jobs: the H update's of step 1, of the odd and of the even steps (criterion = 'connectivity': of step 1 and of the steps
+    // t & 3 = 0..3, the period of its tables); the W update's and the two sweeps' by parity
+    const int NV = conn ? 5 : 3;
+    auto variant = [&](int t) { return t == 1 ? 0 : conn ? 1 + (t & 3) : ((t & 1) ? 1 : 2); };
+    std::vector<MlUpdJob> jh((size_t)NV * B), jw((size_t)2 * B);
     std::vector<SweepSide> jg((size_t)2 * B), jc((size_t)2 * B);
     for (int b = 0; b < B; b++) {
         vbnmf_engine *e = engs[b];
         double *Ht[2] = {e->bpH, e->bpH_alt};                                    // [0]: the latest table as the run starts
-        for (int v = 0; v < 3; v++) {
-            const int t = v == 0 ? 1 : (v == 1 ? 3 : 2);
+        e->chg_off = (size_t)max_it;
+        if (conn) { if (int rc = conn_alloc(e)) return rc; }                     // (the tables are zeroed inside the run's scope)
+        for (int v = 0; v < NV; v++) {
+            const int t = v == 0 ? 1 : conn ? 4 + (v - 1) : (v == 1 ? 3 : 2);          // a step of that variant
             MlUpdJob &J = jh[(size_t)v * B + b];
             J.part = e->B.part; J.inv_ptr = e->B.inv_ptr; J.inv_task = e->B.inv_task; J.nmaj = e->m;
             J.other_bp = e->bpW; J.f = e->lh; J.bp = Ht[t & 1]; J.stop = nullptr;
@@ -2346,6 +2407,7 @@ int vbnmf_batch_ml_run(vbnmf_engine **engs, int32_t count, int32_t prior, double
             J.r = e->r; J.other_nb = e->ub; J.prior = prior;
             J.stage_ids = stage_ids(e->B, e->ub);
             J.fold = ml_fold(e, t, hist, Ht[(t - 1) & 1]);
+            if (conn) J.fold.cn = conn_step(e, t, chg);
         }
         for (int par = 0; par < 2; par++) {                                      // step t of parity par = t & 1
             const int32_t *stop = &(e->ctl2 + par)->stop;                        // what that step's H update left
@@ -2374,9 +2436,10 @@ int vbnmf_batch_ml_run(vbnmf_engine **engs, int32_t count, int32_t prior, double
     if (rc) { free_jobs(); return rc; }
 
     RunScope S{engs, B, e0->stream};
-    rc = S.begin([&](int) { return ml_ctl(tol, max_it); });
+    rc = S.begin([&](int) { return conn ? ml_conn_ctl(max_it, ncnn_step) : ml_ctl(tol, max_it); });
+    for (int b = 0; b < B && conn && !rc; b++) rc = conn_zero(engs[b]);
     if (!rc) rc = drive_loop(engs, B, false, max_it, true, [&](int t) -> int {
-        const int v = t == 1 ? 0 : ((t & 1) ? 1 : 2), par = t & 1;
+        const int v = variant(t), par = t & 1;
         if (int q = launch_ml_update_batch(e0, d_jh + (size_t)v * B, B)) return q;           // H <- , the previous step's control folded in
         for (int b = 0; b < B; b++) { vbnmf_engine *e = engs[b]; std::swap(e->bpH, e->bpH_alt); e->fold_step = t; }
         if (int q = launch_sweep1_batch(e0, d_jg + (size_t)par * B, B, false)) return q;     // gene side on (w, h_new)
@@ -2386,6 +2449,7 @@ int vbnmf_batch_ml_run(vbnmf_engine **engs, int32_t count, int32_t prior, double
             for (int b = 0; b < B; b++) {
                 vbnmf_engine *e = engs[b];
                 MlFold g = ml_fold(e, t + 1, hist, e->bpH);
+                if (conn) g.cn = conn_step(e, t + 1, chg);
                 g.control_only = 1;
                 if (int q = launch_ml_update(e, false, prior, gamma_a, gamma_b, eps, &g)) return q;
             }
@@ -2397,7 +2461,43 @@ int vbnmf_batch_ml_run(vbnmf_engine **engs, int32_t count, int32_t prior, double
     free_jobs();
     if (rc) return rc;
     read_out(engs, B, it_out, nullptr, lk_out, reason_out, nullptr, history, history_rows, 1);
+    if (conn) conn_finish(engs, B, changes, changes_rows);
     return VBNMF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// The device-driven ML-NMF loops (vbnmf_engine_ml_run; factorize() under criterion = 'likelihood', reference
+// R/factorize.R:194-213) of `count` engines of ONE rank on ONE matrix -- the `nrun` restarts factorize() makes of every rank
+// (R/factorize.R:181; its default is nrun = 20) -- stepped together: four launches per step for the whole batch.  Per engine
+// the results are those of vbnmf_engine_ml_run on it alone, bit for bit.  it_out, lk_out, reason_out: [count]; history (or
+// NULL): [count][history_rows], history_rows >= max_it.  Engines as for vbnmf_batch_run, their states set by ml_set_state.
+int vbnmf_batch_ml_run(vbnmf_engine **engs, int32_t count, int32_t prior, double gamma_a, double gamma_b, int32_t max_it, double tol,
+                       int32_t *it_out, double *lk_out, int32_t *reason_out, double *history, int64_t history_rows)
+{
+    if (!engs) return fail(VBNMF_ERR_BAD_ARG, "NULL argument");
+    if (count < 1 || count > kBatchMax) return fail(VBNMF_ERR_BAD_ARG, "a batch holds 1 to %d engines", kBatchMax);
+    if (max_it < 1) return fail(VBNMF_ERR_BAD_ARG, "max_it must be >= 1");
+    if (history && history_rows < max_it) return fail(VBNMF_ERR_BAD_ARG, "history needs max_it doubles per engine");
+    return batch_ml_run(engs, count, prior, gamma_a, gamma_b, max_it, tol, 0, it_out, lk_out, reason_out, history, history_rows, nullptr, 0);
+}
+
+// The same batch under criterion = 'connectivity' (vbnmf_engine_ml_run_connectivity: R/factorize.R:198-208): still four launches
+// per step, every engine's H update forming its own labels and table, its own control block counting and deciding.  Per engine
+// the results are those of vbnmf_engine_ml_run_connectivity on it alone, bit for bit.  changes (or NULL): [count][changes_rows].
+int vbnmf_batch_ml_run_connectivity(vbnmf_engine **engs, int32_t count, int32_t prior, double gamma_a, double gamma_b, int32_t max_it,
+                                    int32_t ncnn_step, int32_t *it_out, double *lk_out, int32_t *reason_out, double *history,
+                                    int64_t history_rows, int64_t *changes, int64_t changes_rows)
+{
+    if (!engs) return fail(VBNMF_ERR_BAD_ARG, "engine handle is NULL");
+    if (count < 1 || count > kBatchMax) return fail(VBNMF_ERR_BAD_ARG, "a batch holds 1 to %d engines", kBatchMax);
+    if (max_it < 1 || ncnn_step < 1) return fail(VBNMF_ERR_BAD_ARG, "max_it and ncnn_step must be >= 1");
+    if (history && history_rows < max_it) return fail(VBNMF_ERR_BAD_ARG, "history needs max_it doubles per engine");
+    if (changes && changes_rows < max_it) return fail(VBNMF_ERR_BAD_ARG, "changes needs max_it counts per engine");
+    return batch_ml_run(engs, count, prior, gamma_a, gamma_b, max_it, 0.0, ncnn_step, it_out, lk_out, reason_out, history, history_rows,
+                        changes, changes_rows);
 }
 
 // ---------------------------------------------------------------- communicators (comm.h)
@@ -2684,27 +2784,32 @@ int vbnmf_engine_ml_step(vbnmf_engine *e, int32_t prior, double gamma_a, double 
     return VBNMF_OK;
 }
 
-// Device-driven form of factorize()'s inner loop under criterion = 'likelihood' (reference R/factorize.R:194-213).
-int vbnmf_engine_ml_run(vbnmf_engine *e, int32_t prior, double gamma_a, double gamma_b, int32_t max_it, double tol,
-                        int32_t *it_out, double *lk_out, int32_t *reason_out, double *history, int64_t history_rows)
+}  // extern "C"
+
+namespace {
+
+// The device-driven ML loop of one engine under either stopping rule (ncnn_step 0: the likelihood's, with tol).
+int ml_run_one(vbnmf_engine *e, int32_t prior, double gamma_a, double gamma_b, int32_t max_it, double tol, int32_t ncnn_step,
+               int32_t *it_out, double *lk_out, int32_t *reason_out, double *history, int64_t history_rows, int64_t *changes)
 {
-    if (!e) return fail(VBNMF_ERR_BAD_ARG, "engine handle is NULL");
-    if (!e->ml_ready) return fail(VBNMF_ERR_STATE, "ml_run before ml_set_state");
-    if (max_it < 1) return fail(VBNMF_ERR_BAD_ARG, "max_it must be >= 1");
-    if (history && history_rows < max_it) return fail(VBNMF_ERR_BAD_ARG, "history needs max_it doubles");
+    const bool conn = ncnn_step > 0;
     if (int rc = use_device(e)) return rc;
     const double eps = 2.220446049250313e-16;
-    if (history) { if (int rc = ensure_history(e, (size_t)max_it)) return rc; }
+    if (history || changes) { if (int rc = ensure_history(e, (size_t)max_it * (changes ? 2 : 1))) return rc; }
+    e->chg_off = (size_t)max_it;
+    if (conn) { if (int rc = conn_alloc(e)) return rc; }
 
-    const bool hist = history != nullptr;
+    const bool hist = history != nullptr, chg = changes != nullptr;
     RunScope S{&e, 1};
-    int rc = S.begin([&](int) { return ml_ctl(tol, max_it); });
+    int rc = S.begin([&](int) { return conn ? ml_conn_ctl(max_it, ncnn_step) : ml_ctl(tol, max_it); });
+    if (!rc && conn) rc = conn_zero(e);
     if (!rc) rc = drive_loop(&e, 1, true, max_it, e->fold, [&](int) -> int {
         if (e->fold) {
             // k_ml_update(H, with the control step of the PREVIOUS cell-side sweep folded in)  sweep  k_ml_update(W)  sweep ;
             // behind the last step of the run the control step alone (mlnmf.h: MlFold)
             const int t = ++e->fold_step;
             MlFold f = ml_fold(e, t, hist, e->bpH);
+            if (conn) f.cn = conn_step(e, t, chg);
             std::swap(e->bpH, e->bpH_alt);                          // this step's H-side partials go to the other table
             int q = launch_ml_update(e, false, prior, gamma_a, gamma_b, eps, &f);
             e->stop_ptr = &f.next->stop;
@@ -2713,12 +2818,23 @@ int vbnmf_engine_ml_run(vbnmf_engine *e, int32_t prior, double gamma_a, double g
             if (!q) q = launch_sweep1(e, false);
             if (!q && t == max_it) {
                 MlFold g = ml_fold(e, t + 1, hist, e->bpH);
+                if (conn) g.cn = conn_step(e, t + 1, chg);
                 g.control_only = 1;
                 q = launch_ml_update(e, false, prior, gamma_a, gamma_b, eps, &g);
             }
             return q;
         }
-        int q = launch_ml_update(e, false, prior, gamma_a, gamma_b, eps);
+        int q;
+        MlConn cn{};                                                // (what k_ml_control reads: the table this step fills)
+        if (conn) {
+            const int t = ++e->fold_step;                           // (no fold: only the rule's step counter here)
+            MlFold f{};
+            f.cn = conn_step(e, t, chg);
+            cn = conn_step(e, t + 1, chg);
+            q = launch_ml_update(e, false, prior, gamma_a, gamma_b, eps, &f);
+        } else {
+            q = launch_ml_update(e, false, prior, gamma_a, gamma_b, eps);
+        }
         if (!q) q = launch_sweep1(e, true);
         if (!q) q = launch_ml_update(e, true, prior, gamma_a, gamma_b, eps);
         if (!q) q = launch_sweep1(e, false);
@@ -2726,7 +2842,7 @@ int vbnmf_engine_ml_run(vbnmf_engine *e, int32_t prior, double gamma_a, double g
         return with_rank(e->R, [&](auto rt) {
             hipLaunchKernelGGL((k_ml_control<rt()>), dim3(1), dim3(1024), 0, e->stream, e->bpW, e->bpH, e->ub, e->epart + e->n_wg,
                                (int64_t)e->n_wg, e->xlx, e->r, (double)e->n, (double)e->m, e->ctl, hist ? e->h_hist_dev : nullptr,
-                               e->h_out_dev);
+                               e->h_out_dev, cn);
             hipError_t le = hipGetLastError();
             if (le != hipSuccess) return fail(VBNMF_ERR_HIP, "k_ml_control launch failed: %s", hipGetErrorString(le));
             return (int)VBNMF_OK;
@@ -2734,7 +2850,39 @@ int vbnmf_engine_ml_run(vbnmf_engine *e, int32_t prior, double gamma_a, double g
     });
     if ((rc = S.end(rc))) return rc;
     read_out(&e, 1, it_out, nullptr, lk_out, reason_out, nullptr, history, history_rows, 1);
+    if (conn) conn_finish(&e, 1, changes, max_it);
     return VBNMF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// Device-driven form of factorize()'s inner loop under criterion = 'likelihood' (reference R/factorize.R:194-213).
+int vbnmf_engine_ml_run(vbnmf_engine *e, int32_t prior, double gamma_a, double gamma_b, int32_t max_it, double tol,
+                        int32_t *it_out, double *lk_out, int32_t *reason_out, double *history, int64_t history_rows)
+{
+    if (!e) return fail(VBNMF_ERR_BAD_ARG, "engine handle is NULL");
+    if (!e->ml_ready) return fail(VBNMF_ERR_STATE, "ml_run before ml_set_state");
+    if (max_it < 1) return fail(VBNMF_ERR_BAD_ARG, "max_it must be >= 1");
+    if (history && history_rows < max_it) return fail(VBNMF_ERR_BAD_ARG, "history needs max_it doubles");
+    return ml_run_one(e, prior, gamma_a, gamma_b, max_it, tol, 0, it_out, lk_out, reason_out, history, history_rows, nullptr);
+}
+
+// ... under criterion = 'connectivity' (reference R/factorize.R:198-208): the labels which.max(h[, j]) of every step are formed
+// by the step's own H update, the count of changed pairs by the control step; stop (reason 2) once it has been 0 for ncnn_step
+// steps in a row, else (reason 4) at max_it.  The likelihood is computed and reported as in vbnmf_engine_ml_run and stops nothing.
+int vbnmf_engine_ml_run_connectivity(vbnmf_engine *e, int32_t prior, double gamma_a, double gamma_b, int32_t max_it, int32_t ncnn_step,
+                                     int32_t *it_out, double *lk_out, int32_t *reason_out, double *history, int64_t history_rows,
+                                     int64_t *changes, int64_t changes_rows)
+{
+    if (!e) return fail(VBNMF_ERR_BAD_ARG, "engine handle is NULL");
+    if (max_it < 1 || ncnn_step < 1) return fail(VBNMF_ERR_BAD_ARG, "max_it and ncnn_step must be >= 1");
+    if (history && history_rows < max_it) return fail(VBNMF_ERR_BAD_ARG, "history needs max_it doubles");
+    if (changes && changes_rows < max_it) return fail(VBNMF_ERR_BAD_ARG, "changes needs max_it counts");
+    if (e->partitioned) return fail(VBNMF_ERR_STATE, "ML-NMF needs an unpartitioned engine");
+    if (!e->ml_ready) return fail(VBNMF_ERR_STATE, "ml_run_connectivity before ml_set_state");
+    return ml_run_one(e, prior, gamma_a, gamma_b, max_it, 0.0, ncnn_step, it_out, lk_out, reason_out, history, history_rows, changes);
 }
 
 int vbnmf_engine_ml_get_state(vbnmf_engine *e, double *w, double *h)

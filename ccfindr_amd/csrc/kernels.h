@@ -875,6 +875,9 @@ struct LoopCtl {
     int32_t it, stop, reason;      // reason: 1 NaN evidence, 2 converged, 3 hyper Newton failed, 4 Itmax
     int32_t max_it, n0, dn;
     int32_t flags[4];              // hyper.update
+    // the ML loop under criterion = 'connectivity' (mlnmf.h; reference R/factorize.R:198-208); 0 in every other loop
+    int32_t criterion;             // 1: stop on the labels, not on the likelihood
+    int32_t zstep, ncnn_step;      // steps in a row without a changed pair / how many of them end the run
 };
 
 __device__ inline int dev_hyper_update_pair(const int32_t *flags, const double *stats, double *hyper, int lane);

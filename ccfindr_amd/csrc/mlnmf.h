@@ -23,6 +23,57 @@ namespace vbnmf {
 // the VB loop folds its own into the gene-side update (kernels.h: ControlFold): every block forms it from the same
 // inputs, block 0 writes it out, and what a block reads is never written in the same launch (the control block and the
 // table of H-side block partials alternate between two buffers by step parity).
+//
+// criterion = 'connectivity' (R/factorize.R:198-208; MlConn, ids_out set): the H update of step t also forms the labels of
+// its h_new -- which.max(h_new[, j]), k_argmax's rules, from the values its threads have just written -- and adds every
+// cell to entry [label of step t-1][label of step t] of an (r+1) x (r+1) table (integer atomics: no order in the result).
+// The control step of step t (in the NEXT launch of this kernel, or k_ml_control) reads the finished table:
+//   nchange = pairs(rows) + pairs(cols) - 2 pairs(cells)   (k_label_pairs' arithmetic, init.h);  it == 1: m (m - 1) / 2
+//   zstep   = nchange == 0 ? zstep + 1 : 0 ;  stop (reason 2) at zstep == ncnn_step, else (reason 4) at max_it
+// Nothing is read and written in one launch: labels alternate between two arrays by step parity, tables rotate among four
+// -- step t fills table t & 3, its control reads (t - 1) & 3, and it zeroes (t + 1) & 3 for the next step; a period of
+// four (three would do for one engine) keeps the batch's pre-built argument blocks, which also alternate by parity, at four.
+constexpr int kConnLdsTable = 33 * 33;     // counters of a block's own table in LDS: ranks up to 32
+struct MlConn {
+    int32_t *ids_out;                      // [nmaj] labels of this step's h_new, 1-based, 0 = all NaN (null: the rule is off)
+    const int32_t *ids_prev;               // the previous step's (null at step 1: nothing to count against)
+    unsigned long long *tab_add;           // the table this step fills (zero as the launch starts)
+    unsigned long long *tab_zero;          // the table the next step fills
+    const unsigned long long *tab_read;    // the table the previous step filled, for the control step
+    int64_t *changes;                      // [max_it] nchange of every step, device-visible host memory (or null)
+    int64_t npair;                         // m (m - 1) / 2
+};
+
+// pairs(rows) + pairs(cols) - 2 pairs(cells) of an (r+1) x (r+1) contingency table by the whole block, into *s_out (LDS),
+// complete behind the closing barrier.  64-bit integers throughout; the threads' shares wrap, their total is the count.
+__device__ __forceinline__ void block_label_changes(const unsigned long long *__restrict__ tab, int r, unsigned long long *s_out, int nthreads)
+{
+    const int t = threadIdx.x, q = r + 1;
+    if (t == 0) *s_out = 0ull;
+    __syncthreads();
+    auto pairs = [](unsigned long long c) { return c * (c - (c > 0 ? 1ull : 0ull)) / 2ull; };
+    unsigned long long acc = 0ull;
+    for (int i = t; i < q * q; i += nthreads) acc -= 2ull * pairs(tab[i]);
+    for (int a = t; a < q; a += nthreads) {
+        unsigned long long rs = 0ull, cs = 0ull;
+        for (int b = 0; b < q; b++) { rs += tab[(size_t)a * q + b]; cs += tab[(size_t)b * q + a]; }
+        acc += pairs(rs) + pairs(cs);
+    }
+    if (acc) atomicAdd(s_out, acc);
+    __syncthreads();
+}
+
+// The rule itself, for the thread that writes the control block: -> reason (0: go on), zstep updated.
+__device__ __forceinline__ int conn_decide(const MlConn &cn, int it, int max_it, int ncnn_step, unsigned long long counted, int &zstep,
+                                           bool write)
+{
+    const int64_t nchange = it == 1 ? cn.npair : (int64_t)counted;         // :200
+    zstep = nchange == 0 ? zstep + 1 : 0;                                  // :206-207
+    if (write && cn.changes) cn.changes[it - 1] = nchange;
+    if (zstep == ncnn_step) return 2;                                      // :208
+    return it >= max_it ? 4 : 0;
+}
+
 struct MlFold {
     const LoopCtl *prev;           // null: no fold
     LoopCtl *next;
@@ -32,6 +83,7 @@ struct MlFold {
     double xlx, n, m;
     double *history, *out_host;
     int32_t do_control, control_only;
+    MlConn cn;                     // criterion = 'connectivity' (also without a fold: prev null, cn.ids_out set)
 };
 
 template <int R>
@@ -41,6 +93,11 @@ __device__ __forceinline__ void ml_update_body(
     double *__restrict__ f, double *__restrict__ bp, const int32_t *__restrict__ stop, const MlFold &fold, int stage_ids)
 {
     constexpr int RB = kUpdateThreads / R;       // majors per pass
+    // Static LDS of every instantiation, the likelihood rule's and the W side's included: s_other, sH, s_e, the staged ids and
+    // pointers, the connectivity rule's s_tab and s_nch, s_stop.  80 180 B at R = 128: 1 740 B short of the 80 KB up to which
+    // two blocks share a CU's 160 KB -- a further buffer must fit into that, or alias one of these.
+    static_assert(sizeof(double) * (2 * (R + 2) + kUpdateThreads) + sizeof(uint32_t) * (kStageIds + kStagePtr + kConnLdsTable) + 16
+                      <= 80 * 1024, "k_ml_update: two blocks no longer fit a CU's LDS");
     __shared__ double s_other[R + 2];
     __shared__ double s_e[kUpdateThreads];
     __shared__ uint32_t s_ids[kStageIds];
@@ -74,9 +131,12 @@ __device__ __forceinline__ void ml_update_body(
             if (t < R + 2 && !fold.control_only) bp[(size_t)blockIdx.x * (R + 2) + t] = fold.bpH_prev[(size_t)blockIdx.x * (R + 2) + t];
             return;
         }
+        __shared__ unsigned long long s_nch;
+        const bool conn = fold.cn.ids_out != nullptr;        // (uniform over the launch)
+        if (conn && fold.do_control) block_label_changes(fold.cn.tab_read, r, &s_nch, kUpdateThreads);
         const double data = block_sum(pe, s_e);
         if (t == 0) {
-            int reason = 0, it = pv->it;
+            int reason = 0, it = pv->it, zstep = pv->zstep;
             double lk = pv->lkh, new_lk0 = pv->lk0;
             if (fold.do_control) {
                 double cross = 0.0;
@@ -84,13 +144,14 @@ __device__ __forceinline__ void ml_update_body(
                 lk = ((data - cross) + fold.xlx) / fold.n / fold.m;
                 it = pv->it + 1;
                 const double lkold = pv->lk0;
-                if (fabs(lkold - lk) < pv->tol * fabs(lkold)) reason = 2;           // converged (R/factorize.R:211)
+                if (conn) { new_lk0 = lk; reason = conn_decide(fold.cn, it, pv->max_it, pv->ncnn_step, s_nch, zstep, blockIdx.x == 0); }
+                else if (fabs(lkold - lk) < pv->tol * fabs(lkold)) reason = 2;      // converged (R/factorize.R:211)
                 else { new_lk0 = lk; if (it >= pv->max_it) reason = 4; }
             }
             s_stop = reason != 0;
             if (blockIdx.x == 0) {
                 LoopCtl nx = *pv;
-                nx.it = it; nx.lkh = lk; nx.lk0 = new_lk0;
+                nx.it = it; nx.lkh = lk; nx.lk0 = new_lk0; nx.zstep = zstep;
                 if (reason) { nx.reason = reason; nx.stop = 1; }
                 *fold.next = nx;
                 if (fold.do_control) {
@@ -124,6 +185,62 @@ __device__ __forceinline__ void ml_update_body(
     double down = s_other[k < R ? k : 0];
     if (prior) down = down + ga / gb;            // R/factorize.R:12,21
     double ve = 0.0;
+    if (fold.cn.ids_out) {
+        // criterion = 'connectivity': the same update, pass by pass for the whole block, so that the R threads of a major --
+        // which straddle a wavefront boundary wherever R does not divide 64 -- can hand their new values over through LDS.
+        // Up to rank 32 a block counts its cells in a table of its own in LDS and adds the entries it used to the global one at
+        // the end (a block of a large matrix owns hundreds of cells, nearly all on the table's diagonal); the wider ranks'
+        // tables go to the global one directly.
+        __shared__ unsigned int s_tab[kConnLdsTable];
+        const MlConn &cn = fold.cn;
+        const int q = r + 1;
+        const bool lds_tab = q * q <= kConnLdsTable;
+        for (int64_t i = (int64_t)blockIdx.x * kUpdateThreads + t; i < (int64_t)q * q; i += (int64_t)gridDim.x * kUpdateThreads)
+            cn.tab_zero[i] = 0ull;
+        if (lds_tab) for (int i = t; i < q * q; i += kUpdateThreads) s_tab[i] = 0u;      // (a barrier follows before the first count)
+        for (int64_t M0 = m0; M0 < m1; M0 += RB) {
+            const int64_t M = M0 + row;
+            const bool live = row < RB && M < m1;
+            double v = 0.0;
+            if (live) {
+                const size_t o = (size_t)M * R + k;
+                if (k < r) {
+                    const double s = staged ? task_sum_lds(part, s_ids, s_ptr[M - bm0] - q_lo, s_ptr[M - bm0 + 1] - q_lo, R, k)
+                                            : task_sum(part, inv_task, inv_ptr[M], inv_ptr[M + 1], R, k);
+                    double up = f[o] * s;
+                    if (prior) up = up + ga - 1.0;
+                    v = up / down;
+                    if (v < eps) v = eps;
+                    f[o] = v;
+                    ve += v;
+                } else {
+                    f[o] = 0.0;
+                }
+            }
+            s_e[t] = v;
+            __syncthreads();
+            if (live && k == 0) {                // which.max(h_new[, M]): first maximum, NaN never wins, 0 if all are NaN (k_argmax)
+                int best = 0;
+                double bv = 0.0;
+                for (int j = 0; j < r; j++) {
+                    const double u = s_e[t + j];
+                    if (u == u && (best == 0 || u > bv)) { best = j + 1; bv = u; }
+                }
+                cn.ids_out[M] = best;
+                if (cn.ids_prev) {
+                    const int cell = cn.ids_prev[M] * q + best;
+                    if (lds_tab) atomicAdd(&s_tab[cell], 1u);
+                    else atomicAdd(&cn.tab_add[cell], 1ull);
+                }
+            }
+            __syncthreads();
+        }
+        if (lds_tab && cn.ids_prev)
+            for (int i = t; i < q * q; i += kUpdateThreads) {
+                const unsigned int c = s_tab[i];
+                if (c) atomicAdd(&cn.tab_add[i], (unsigned long long)c);
+            }
+    } else
     if (row < RB) {
         for (int64_t M = m0 + row; M < m1; M += RB) {
             const size_t o = (size_t)M * R + k;
@@ -225,15 +342,17 @@ template <int R>
 __global__ __launch_bounds__(1024) void k_ml_control(const double *__restrict__ bpW, const double *__restrict__ bpH, int nb,
                                                      const double *__restrict__ epart, int64_t nepart, double xlx, int r,
                                                      double n, double m, LoopCtl *ctl, double *__restrict__ history,
-                                                     double *__restrict__ out_host)
+                                                     double *__restrict__ out_host, const MlConn cn)
 {
     __shared__ double sW[R + 2], sH[R + 2];
     __shared__ double sm[1024];
+    __shared__ unsigned long long s_nch;
     const int stopped = ctl->stop;               // tested once the reductions' loads are in flight too
     double part = 0.0;
     for (int64_t q = threadIdx.x; q < nepart; q += 1024) part += epart[q];
     bp_colsums2(bpW, bpH, nb, R + 2, sW, sH, 1024);
     if (stopped) return;
+    if (cn.ids_out) block_label_changes(cn.tab_read, r, &s_nch, 1024);   // criterion = 'connectivity': the table this step's H update filled
     const double data = block_sum(part, sm);
     if (threadIdx.x != 0) return;
     double cross = 0.0;
@@ -242,7 +361,13 @@ __global__ __launch_bounds__(1024) void k_ml_control(const double *__restrict__ 
     const int it = ctl->it + 1;
     const double lkold = ctl->lk0;
     int reason = 0;
-    if (fabs(lkold - lk) < ctl->tol * fabs(lkold)) reason = 2;           // converged (:211)
+    if (cn.ids_out) {
+        int zstep = ctl->zstep;
+        ctl->lk0 = lk;
+        reason = conn_decide(cn, it, ctl->max_it, ctl->ncnn_step, s_nch, zstep, true);
+        ctl->zstep = zstep;
+    }
+    else if (fabs(lkold - lk) < ctl->tol * fabs(lkold)) reason = 2;      // converged (:211)
     else { ctl->lk0 = lk; if (it >= ctl->max_it) reason = 4; }
     ctl->it = it; ctl->lkh = lk;
     if (history) history[it - 1] = lk;

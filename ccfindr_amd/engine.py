@@ -340,17 +340,33 @@ class VBEngine:
         N.check(self._lib.vbnmf_engine_ml_step(self._h, int(bool(prior)), float(gamma_a), float(gamma_b), ctypes.byref(lk)))
         return lk.value
 
-    def ml_run(self, Itmax=10000, Tol=1e-5, prior=False, gamma_a=1.0, gamma_b=1.0, history=False):
-        """factorize()'s likelihood-criterion loop on the resident pair, driven by the device ->
-        ``{"it", "lk", "reason"[, "history"]}`` (reason 2 converged, 4 Itmax)."""
+    def ml_run(self, Itmax=10000, Tol=1e-5, prior=False, gamma_a=1.0, gamma_b=1.0, history=False, criterion="likelihood",
+               ncnn_step=40, changes=False):
+        """factorize()'s inner loop on the resident pair, driven by the device -> ``{"it", "lk", "reason"[, "history"]}``
+        (reason 2 converged, 4 Itmax).  ``criterion="likelihood"``: the likelihood's rule with ``Tol`` (R/factorize.R:211-213);
+        ``"connectivity"``: stop once the cells' labels have not moved for ``ncnn_step`` steps (:198-208), ``Tol`` unused;
+        ``changes=True`` adds ``"changes"``, the count of changed pairs of every step (the first is m (m - 1) / 2)."""
         it, reason, lk = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_double()
         hist = np.empty(int(Itmax)) if history else None
-        N.check(self._lib.vbnmf_engine_ml_run(self._h, int(bool(prior)), float(gamma_a), float(gamma_b), int(Itmax), float(Tol),
-                                              ctypes.byref(it), ctypes.byref(lk), ctypes.byref(reason), N.dptr(hist),
-                                              int(Itmax) if history else 0))
+        if criterion == "connectivity":
+            chg = np.empty(int(Itmax), dtype=np.int64) if changes else None
+            N.check(self._lib.vbnmf_engine_ml_run_connectivity(
+                self._h, int(bool(prior)), float(gamma_a), float(gamma_b), int(Itmax), int(ncnn_step), ctypes.byref(it), ctypes.byref(lk),
+                ctypes.byref(reason), N.dptr(hist), int(Itmax) if history else 0,
+                chg.ctypes.data_as(N.c_int64_p) if changes else None, int(Itmax) if changes else 0))
+        elif criterion != "likelihood":
+            raise ValueError("Unknown stopping criterion.")
+        elif changes:
+            raise ValueError("changes are counted under criterion='connectivity' only")
+        else:
+            N.check(self._lib.vbnmf_engine_ml_run(self._h, int(bool(prior)), float(gamma_a), float(gamma_b), int(Itmax), float(Tol),
+                                                  ctypes.byref(it), ctypes.byref(lk), ctypes.byref(reason), N.dptr(hist),
+                                                  int(Itmax) if history else 0))
         out = {"it": it.value, "lk": lk.value, "reason": reason.value}
         if history:
             out["history"] = hist[:it.value].copy()
+        if changes:
+            out["changes"] = chg[:it.value].copy()
         return out
 
     def ml_likelihood(self):
@@ -539,21 +555,30 @@ def run_batch(engines, hypers, Itmax=10000, Tol=1e-5, n0=10, dn=1, flags=(True,)
              "history": hist[b, :it[b]].copy() if history else None} for b in range(B)]
 
 
-def run_batch_ml(engines, Itmax=10000, Tol=1e-5, prior=False, gamma_a=1.0, gamma_b=1.0, history=False):
+def run_batch_ml(engines, Itmax=10000, Tol=1e-5, prior=False, gamma_a=1.0, gamma_b=1.0, history=False, criterion="likelihood",
+                 ncnn_step=40):
     """The ML-NMF loops (``VBEngine.ml_run``) of several engines of ONE rank on ONE ``CountMatrix`` -- the ``nrun`` restarts
-    ``factorize`` makes of a rank, reference R/factorize.R:181 -- stepped together (``vbnmf_batch_ml_run``).  Every engine has
-    had ``ml_set_state``.  Returns one ``ml_run`` result per engine, bit for bit what ``ml_run`` gives on that engine alone."""
+    ``factorize`` makes of a rank, reference R/factorize.R:181 -- stepped together (``vbnmf_batch_ml_run``, or
+    ``vbnmf_batch_ml_run_connectivity`` under ``criterion="connectivity"``).  Every engine has had ``ml_set_state``.  Returns one
+    ``ml_run`` result per engine, bit for bit what ``ml_run`` gives on that engine alone."""
     B = len(engines)
     if B < 1:
         raise ValueError("an empty batch")
+    if criterion not in ("likelihood", "connectivity"):
+        raise ValueError("Unknown stopping criterion.")
     lib = engines[0]._lib
     hs = (ctypes.c_void_p * B)(*(e._h for e in engines))
     it = np.zeros(B, dtype=np.int32); reason = np.zeros(B, dtype=np.int32)
     lk = np.zeros(B)
     hist = np.zeros((B, int(Itmax))) if history else None
-    N.check(lib.vbnmf_batch_ml_run(hs, B, int(bool(prior)), float(gamma_a), float(gamma_b), int(Itmax), float(Tol),
-                                   it.ctypes.data_as(N.c_int32_p), N.dptr(lk), reason.ctypes.data_as(N.c_int32_p),
-                                   N.dptr(hist), int(Itmax) if history else 0))
+    if criterion == "connectivity":
+        N.check(lib.vbnmf_batch_ml_run_connectivity(hs, B, int(bool(prior)), float(gamma_a), float(gamma_b), int(Itmax), int(ncnn_step),
+                                                    it.ctypes.data_as(N.c_int32_p), N.dptr(lk), reason.ctypes.data_as(N.c_int32_p),
+                                                    N.dptr(hist), int(Itmax) if history else 0, None, 0))
+    else:
+        N.check(lib.vbnmf_batch_ml_run(hs, B, int(bool(prior)), float(gamma_a), float(gamma_b), int(Itmax), float(Tol),
+                                       it.ctypes.data_as(N.c_int32_p), N.dptr(lk), reason.ctypes.data_as(N.c_int32_p),
+                                       N.dptr(hist), int(Itmax) if history else 0))
     return [{"it": int(it[b]), "lk": float(lk[b]), "reason": int(reason[b]),
              "history": hist[b, :it[b]].copy() if history else None} for b in range(B)]
 

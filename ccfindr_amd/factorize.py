@@ -131,11 +131,13 @@ def factorize(mat, ranks=2, nrun=20, randomize=False, nsmpl=1, verbose=2, progre
 
     ``mat``: genes x cells counts (dense array, scipy sparse, or ``CountMatrix``).  ``seed`` seeds the numpy
     Generator behind ``init`` and the ``randomize`` permutations.  ``engine_factory(count_matrix, rank)`` replaces
-    the engine constructor (the CPU tests of this loop pass a stand-in).  ``device_loop``: under
-    ``criterion='likelihood'`` (and ``verbose < 3``) the inner loop (:194-213) runs on the device
-    (``vbnmf_engine_ml_run``) instead of one call per iteration.  ``batch``: how many of a rank's ``nrun`` restarts
+    the engine constructor (the CPU tests of this loop pass a stand-in).  ``device_loop``: with ``verbose < 3`` the inner
+    loop (:194-213) runs on the device under either criterion (``vbnmf_engine_ml_run``,
+    ``vbnmf_engine_ml_run_connectivity``) instead of one call per iteration.  ``batch``: how many of a rank's ``nrun`` restarts
     (:181) are stepped by ONE launch (``engine.run_batch_ml``; 1: one at a time; None: up to 16 where the device loop runs,
     the rank is at most 16 and the matrix holds up to 2e7 stored entries) -- on a small matrix one loop cannot fill the GPU.
+    Under ``criterion='connectivity'`` restarts are batched only when ``batch > 1`` is passed: a batch's narrower grids
+    change the sums' order, and a rounding difference can flip a label and move this rule's stop.
     The restarts draw their starts from the same stream in the same order either way.  Returns ``MLResult``.
     """
     del progress_bar
@@ -183,11 +185,16 @@ def factorize(mat, ranks=2, nrun=20, randomize=False, nsmpl=1, verbose=2, progre
                 Ms = M
             # the restarts of this rank stepped `nb` at a time by one launch (engine.run_batch_ml), or one engine for all of them
             nb = 1
-            if (engine_factory is None and device_loop and criterion == "likelihood" and verbose < 3 and nrun > 1 and rank <= BATCH_MAX_RANK
-                    and (batch is None or int(batch) > 1) and os.environ.get("VBNMF_NO_CONTROL_FOLD", "0") != "1"):
+            can_batch = (engine_factory is None and device_loop and verbose < 3 and nrun > 1 and rank <= BATCH_MAX_RANK
+                         and os.environ.get("VBNMF_NO_CONTROL_FOLD", "0") != "1")
+            if can_batch and criterion == "likelihood" and (batch is None or int(batch) > 1):
                 nb = min(nrun, int(batch), 64) if batch is not None else auto_batch(Ms.nnz, nrun)
+            elif can_batch and criterion == "connectivity" and batch is not None and int(batch) > 1:
+                # only when asked: a batch's engines sit on narrower grids and agree with a default engine to rounding, and
+                # under this rule a rounding difference can flip a label and move the stop
+                nb = min(nrun, int(batch), 64)
             elif batch is not None and int(batch) > 1:
-                raise ValueError("batch > 1 needs nrun > 1, rank <= %d, criterion 'likelihood', the device loop and the library's own engines" % BATCH_MAX_RANK)
+                raise ValueError("batch > 1 needs nrun > 1, rank <= %d, the device loop and the library's own engines" % BATCH_MAX_RANK)
             if nb > 1:
                 from .engine import batch_grid, run_batch_ml
                 batch_engines = [VBEngine(Ms, rank, device=device, grid=batch_grid(nb)) for _ in range(nb)]
@@ -195,6 +202,8 @@ def factorize(mat, ranks=2, nrun=20, randomize=False, nsmpl=1, verbose=2, progre
             else:
                 batch_engines = None
                 eng = engine_factory(Ms, rank) if engine_factory else VBEngine(Ms, rank, device=device)
+            # the device loop's stopping rule: under 'likelihood' the call is today's, keywords and all (stand-in engines)
+            rule = {"criterion": criterion, "ncnn_step": ncnn_step} if criterion == "connectivity" else {}
             rmax, wmax, hmax, disp, steps = -np.inf, None, None, np.nan, []
             ahead = {}                                                             # batched: results of runs already stepped
             try:
@@ -207,18 +216,18 @@ def factorize(mat, ranks=2, nrun=20, randomize=False, nsmpl=1, verbose=2, progre
                             for slot, jrun in enumerate(chunk):
                                 whj = init(nrow, ncol, rank, rng)
                                 batch_engines[slot].ml_set_state(whj["ew"], whj["eh"])
-                            for slot, (jrun, res) in enumerate(zip(chunk, run_batch_ml(batch_engines[:len(chunk)], Itmax=Itmax, Tol=Tol))):
+                            for slot, (jrun, res) in enumerate(zip(chunk, run_batch_ml(batch_engines[:len(chunk)], Itmax=Itmax, Tol=Tol, **rule))):
                                 ahead[jrun] = (batch_engines[slot], res)
                         eng, run = ahead.pop(irun)
                     else:
                         wh = init(nrow, ncol, rank, rng)                           # :192
                         eng.ml_set_state(wh["ew"], wh["eh"])
                     zstep, lkold, cid0, lk0, it = 0, -np.inf, None, np.nan, 0
-                    on_device = device_loop and criterion == "likelihood" and verbose < 3 and hasattr(eng, "ml_run")
+                    on_device = device_loop and verbose < 3 and hasattr(eng, "ml_run")
                     if batch_engines is not None:
                         it, lk0 = run["it"], run["lk"]
                     elif on_device:                                                # the loop below, driven by the device
-                        run = eng.ml_run(Itmax=Itmax, Tol=Tol)
+                        run = eng.ml_run(Itmax=Itmax, Tol=Tol, **rule)
                         it, lk0 = run["it"], run["lk"]
                     for it in (() if on_device else range(1, Itmax + 1)):          # :196
                         lk0 = eng.ml_step()                                        # :197-198

@@ -408,6 +408,24 @@ int vbnmf_engine_ml_run(vbnmf_engine *e, int32_t prior, double gamma_a, double g
  * [count] (any may be NULL); history (or NULL): [count][history_rows], history_rows >= max_it. */
 int vbnmf_batch_ml_run(vbnmf_engine **engines, int32_t count, int32_t prior, double gamma_a, double gamma_b, int32_t max_it,
                        double tol, int32_t *it_out, double *lk_out, int32_t *reason_out, double *history, int64_t history_rows);
+/* The same loop under criterion = 'connectivity' (R/factorize.R:198-208), the rule the reference names for cluster
+ * stability, run by the device: every step's H update forms the labels which.max(h[, j]) of its new h and their
+ * contingency table against the previous step's; the control step counts nchange = sum(cnn != cnn0) from it
+ * (it == 1: npair = m (m - 1) / 2, :200), zstep = nchange == 0 ? zstep + 1 : 0 (:206-207), and stops with reason 2 at
+ * zstep == ncnn_step (:208), else with reason 4 at max_it.  No launch is added to the step.  The likelihood is computed,
+ * reported and written to the history every step; it stops nothing (a NaN likelihood included, as in the reference).
+ * changes (or NULL): the nchange of every step run, changes_rows >= max_it; changes[0] = npair.  Afterwards the labels of
+ * the last step are the engine's previous labels: vbnmf_engine_cluster_changes right behind the run reports 0.
+ * VBNMF_ERR_BAD_ARG: NULL handle, max_it < 1, ncnn_step < 1; VBNMF_ERR_STATE: before ml_set_state, partitioned engine. */
+int vbnmf_engine_ml_run_connectivity(vbnmf_engine *e, int32_t prior, double gamma_a, double gamma_b, int32_t max_it,
+                                     int32_t ncnn_step, int32_t *it, double *lk, int32_t *reason, double *history,
+                                     int64_t history_rows, int64_t *changes, int64_t changes_rows);
+/* ... of the restarts of a rank stepped together (R/factorize.R:181, :198-208): vbnmf_batch_ml_run's engines, admission
+ * rules and four launches per step.  Per engine the results are those of vbnmf_engine_ml_run_connectivity on it alone, bit
+ * for bit.  it_out, lk_out, reason_out: [count]; history: [count][history_rows]; changes: [count][changes_rows] (or NULL). */
+int vbnmf_batch_ml_run_connectivity(vbnmf_engine **engines, int32_t count, int32_t prior, double gamma_a, double gamma_b,
+                                    int32_t max_it, int32_t ncnn_step, int32_t *it_out, double *lk_out, int32_t *reason_out,
+                                    double *history, int64_t history_rows, int64_t *changes, int64_t changes_rows);
 int vbnmf_engine_ml_likelihood(vbnmf_engine *e, double *lk);
 int vbnmf_engine_ml_get_state(vbnmf_engine *e, double *w, double *h);
 /* Stateless forms of the same step: nmf_updateR(x, w, h, n, m, r, prior, gamma.a, gamma.b)
