@@ -135,6 +135,12 @@ SIGNATURES = {
                                                         c_int64_p, _I64]),
     "vbnmf_engine_ml_likelihood": (ctypes.c_int, [_VP, c_double_p]),
     "vbnmf_engine_ml_get_state": (ctypes.c_int, [_VP, c_double_p, c_double_p]),
+    "vbnmf_engine_ml_state_finish": (ctypes.c_int, [_VP]),
+    "vbnmf_engine_reduce_tail": (ctypes.c_int, [_VP, c_int64_p, c_int64_p]),
+    "vbnmf_engine_ml_step_local": (ctypes.c_int, [_VP, _I32, _D, _D]),
+    "vbnmf_engine_ml_step_finish": (ctypes.c_int, [_VP, c_double_p]),
+    "vbnmf_group_ml_state_finish": (ctypes.c_int, [_VP]),
+    "vbnmf_group_ml_run": (ctypes.c_int, [_VP, _I32, _D, _D, _I32, _D, c_int32_p, c_double_p, c_int32_p, c_double_p, _I64]),
     "vbnmf_ml_update_dense": (ctypes.c_int, [_I64, _I64, _I32, c_double_p, c_double_p, c_double_p, _I32, _D, _D,
                                              c_double_p, c_double_p, c_double_p]),
     "vbnmf_ml_update_csc": (ctypes.c_int, [_I64, _I64, _I32, c_int32_p, c_int32_p, c_double_p, c_double_p, c_double_p,

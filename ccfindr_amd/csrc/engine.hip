@@ -298,6 +298,8 @@ struct vbnmf_engine {
     bool has_state = false, stats_ready = false, step_pending = false, prime_pending = false;
     bool poisoned = false;            // a wait on the device timed out: work may still be queued, nothing is waited for or freed
     bool ml_ready = false;            // lw / lh hold an ML-NMF state (w, h) and the cell-side statistics are current
+    bool ml_prime_pending = false;    // partitioned engine: ml_set_state left its partials in `red`, ml_state_finish has not run
+    int ml_phase = 0;                 // host-stepped ML step: 0 idle, 1 / 2 behind the first / second ml_step_local
     bool timing = false;
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;
     bool ev_recorded = false, ev2_recorded = false;
@@ -794,6 +796,8 @@ int launch_vb_side(vbnmf_engine *e, bool gene_side)
     return launch_side_sweep<true>(e, sweep_side_args(e, gene_side), gene_side);
 }
 
+// The W side of a partitioned engine is the dense form (mlnmf.h: ml_update_body): the statistics come summed over tasks and
+// partitions from the reduce buffer, `down` = rowSums(h_new) of all cells from its reduced tail (one row of "block partials").
 int launch_ml_update(vbnmf_engine *e, bool gene_side, int prior, double ga, double gb, double eps, const MlFold *foldp = nullptr)
 {
     const SideView v = side_view(e, gene_side);
@@ -802,20 +806,49 @@ int launch_ml_update(vbnmf_engine *e, bool gene_side, int prior, double ga, doub
     MlFold fold{};
     if (foldp) fold = *foldp;
     const unsigned grid = fold.control_only ? 1 : (unsigned)e->ub;
+    const bool dense = gene_side && e->partitioned;
+    const double *redin = e->red_in ? e->red_in : e->red;
+    const double *part = dense ? redin : S.part;
+    const int32_t *inv_ptr = dense ? nullptr : S.inv_ptr;
+    const uint32_t *inv_task = dense ? nullptr : S.inv_task;
+    const double *other_bp = dense ? redin + (size_t)e->n * e->R : v.other_bp;
+    const int other_nb = dense ? 1 : e->ub;
     return with_rank(e->R, [&](auto rt) {
-        return launch_kernel<k_ml_update<rt()>>(e, dim3(grid), kUpdateThreads, 0, S.part, S.inv_ptr, S.inv_task, v.nmaj, e->r,
-                                                (const double *)v.other_bp, e->ub, prior, ga, gb, eps, v.l, v.bp, stop, fold,
-                                                stage_ids(S, grid));
+        return launch_kernel<k_ml_update<rt()>>(e, dim3(grid), kUpdateThreads, 0, part, inv_ptr, inv_task, v.nmaj, e->r,
+                                                other_bp, other_nb, prior, ga, gb, eps, v.l, v.bp, stop, fold,
+                                                stage_ids(S, grid, dense));
     });
 }
 
+// partitioned: rowSums(h), the data term and the constant come reduced from the tail of `red` (launch_ml_tail + the exchange)
 int launch_ml_final(vbnmf_engine *e)
 {
     e->seq += 1.0;
+    const double *tail = e->partitioned ? e->red + (size_t)e->n * e->R : nullptr;
     return with_rank(e->R, [&](auto rt) {
         return launch_kernel<k_ml_final<rt()>>(e, dim3(1), 1024, 0, e->bpW, e->bpH, e->ub, e->epart + e->n_wg, (int64_t)e->n_wg, e->xlx,
-                                               e->r, (double)e->n, (double)e->m, e->seq, e->d_out, e->h_out_dev);
+                                               e->r, (double)e->n, (double)e->m_global, e->seq, e->d_out, e->h_out_dev, tail);
     });
+}
+
+// partitioned engines, host-stepped: the tail of `red` = [rowSums(h)_k of this partition (R) | 0 | 0 | sum x log(wh) | sum_{x>0}(-x log x + x)]
+// (k_tail's shape with the ML constant in the last slot), what the exchange in front of ml_state_finish / ml_step_finish carries
+int launch_ml_tail(vbnmf_engine *e)
+{
+    hipLaunchKernelGGL(k_tail, dim3(1), dim3(1024), 0, e->stream, e->bpH, e->ub, e->R, e->epart + e->n_wg, (int64_t)e->n_wg, e->xlx,
+                       e->red + (size_t)e->n * e->R);
+    HIPCHECK(hipGetLastError());
+    return VBNMF_OK;
+}
+
+// ... and the first exchange of a step: [sum over a gene's tasks of the gene-side partial rows (n*R) | rowSums(h_new) (R) | 0 | 0]
+int launch_ml_pack(vbnmf_engine *e, const int32_t *stop)
+{
+    const int64_t cnt = e->n * e->R;
+    hipLaunchKernelGGL(k_pack_tail, dim3((unsigned)((cnt + 255) / 256) + 1), dim3(256), 0, e->stream, e->A.part, e->A.inv_ptr, e->A.inv_task, e->n, e->R, e->red,
+                       e->bpH, e->ub, stop);
+    HIPCHECK(hipGetLastError());
+    return VBNMF_OK;
 }
 
 // ---- sparse products on the tiled layout (k_spmm) ----
@@ -1505,7 +1538,7 @@ int vbnmf_engine_set_state(vbnmf_engine *e, const double *lw, const double *lh, 
         if (int rc = bounded_stream_sync(e, e->stream, "the previous set_state of this engine")) return rc;
     }
     e->has_state = false; e->stats_ready = false; e->step_pending = false; e->prime_pending = false;
-    e->ml_ready = false;
+    e->ml_ready = false; e->ml_prime_pending = false; e->ml_phase = 0;
     {
         // the three arrays in index-major form in ONE pinned staging buffer, three asynchronous copies, one wait
         const size_t nR = (size_t)e->n * e->R, mR = (size_t)e->m * e->R;
@@ -1530,7 +1563,7 @@ int vbnmf_engine_random_state(vbnmf_engine *e, double aw, double bw, double ah, 
     if (!(aw > 0.0) || !(bw > 0.0) || !(ah > 0.0) || !(bh > 0.0)) return fail(VBNMF_ERR_BAD_ARG, "Gamma shapes and means must be positive");
     if (int rc = use_device(e)) return rc;
     e->has_state = false; e->stats_ready = false; e->step_pending = false; e->prime_pending = false;
-    e->ml_ready = false; e->ids_valid = false;
+    e->ml_ready = false; e->ids_valid = false; e->ml_prime_pending = false; e->ml_phase = 0;
     const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
     const int64_t nw = e->n * e->R, nh = e->m * e->R;
     hipLaunchKernelGGL(k_gamma_init, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, e->stream, e->lw, e->ew, e->dw, e->n, (int64_t)0, e->r, e->R, aw, bw, 0u, k0, k1, (const int32_t *)nullptr);
@@ -1580,6 +1613,14 @@ int vbnmf_engine_reduce_buffer(vbnmf_engine *e, void **device_ptr, int64_t *coun
     if (!e) return fail(VBNMF_ERR_BAD_ARG, "engine handle is NULL");
     if (device_ptr) *device_ptr = e->red;
     if (count) *count = e->red_count;
+    return VBNMF_OK;
+}
+
+int vbnmf_engine_reduce_tail(const vbnmf_engine *e, int64_t *offset, int64_t *count)
+{
+    if (!e) return fail(VBNMF_ERR_BAD_ARG, "engine handle is NULL");
+    if (offset) *offset = e->n * e->R;
+    if (count) *count = e->red_count - e->n * e->R;
     return VBNMF_OK;
 }
 
@@ -1984,6 +2025,7 @@ struct RunScope {
     vbnmf_engine *const *e;
     int count;
     hipStream_t shared = nullptr;
+    bool plain_ctl = false;            // the loop keeps its control block in e->ctl whatever e->fold says (partitioned ML loop)
     std::vector<hipStream_t> own;
     std::vector<char> timing;
 
@@ -1998,7 +2040,7 @@ struct RunScope {
             x->timing = false;                                     // event pairs cannot follow launches queued ahead
             x->ev_recorded = false; x->ev2_recorded = false;
             if (shared) x->stream = shared;
-            hipLaunchKernelGGL(k_ctl_init, dim3(1), dim3(1), 0, x->stream, x->fold ? x->ctl2 : x->ctl, ctl(p));
+            hipLaunchKernelGGL(k_ctl_init, dim3(1), dim3(1), 0, x->stream, x->fold && !plain_ctl ? x->ctl2 : x->ctl, ctl(p));
             x->fold_step = 0;
             volatile double *ho = x->h_out;
             ho[5] = 0.0; ho[6] = 0.0; ho[7] = 0.0;
@@ -2593,7 +2635,11 @@ int vbnmf_engine_allreduce(vbnmf_engine *e)
     if (!e) return fail(VBNMF_ERR_BAD_ARG, "engine handle is NULL");
     if (!e->comm || e->comm->kind != 0) return fail(VBNMF_ERR_STATE, "allreduce needs an RCCL communicator attached to the engine");
     if (int rc = use_device(e)) return rc;
-    return rccl_check(rccl_api().AllReduce(e->red, e->red, (size_t)e->red_count, ncclDouble, ncclSum, e->comm->nc, e->stream), "ncclAllReduce");
+    // Behind ml_set_state and the second ml_step_local only the tail [rowSums(h) | 0 0 | data term | constant] is read afterwards.
+    // Sending the tail alone there is an OPTIMISATION, not part of the protocol (it spares a second n*R all-reduce per step): a
+    // caller that sums the whole buffer at every exchange gets the same results.
+    const size_t off = (e->ml_prime_pending || e->ml_phase == 2) ? (size_t)e->n * e->R : 0;
+    return rccl_check(rccl_api().AllReduce(e->red + off, e->red + off, (size_t)e->red_count - off, ncclDouble, ncclSum, e->comm->nc, e->stream), "ncclAllReduce");
 }
 
 static int group_members(vbnmf_comm *c, LoopGroup &G)
@@ -2606,18 +2652,10 @@ static int group_members(vbnmf_comm *c, LoopGroup &G)
     return VBNMF_OK;
 }
 
-// Local group: the state exchange after set_state on every member (sums the reduce buffers in place, partition
-// order), then state_finish on each.
-int vbnmf_group_state_finish(vbnmf_comm *c)
+// The reduce buffers of a local group summed in place, partition order, behind everything queued on the members' streams.
+static int group_sum_in_place(const LoopGroup &G)
 {
-    LoopGroup G{};
-    if (int rc = group_members(c, G)) return rc;
-    if (int rc = use_device(G.e[0])) return rc;
-    if (int rc = group_tables(c)) return rc;
-    for (int p = 0; p < G.count; p++) {
-        if (!G.e[p]->prime_pending) return fail(VBNMF_ERR_STATE, "group_state_finish: partition %d has no pending set_state", p);
-        HIPCHECK(hipStreamSynchronize(G.e[p]->stream));
-    }
+    for (int p = 0; p < G.count; p++) HIPCHECK(hipStreamSynchronize(G.e[p]->stream));
     vbnmf_engine *L = G.e[0];
     // in place: every element is read from all partitions before it is written to any
     std::vector<double *> ptr(G.count);
@@ -2632,6 +2670,20 @@ int vbnmf_group_state_finish(vbnmf_comm *c)
     if (he == hipSuccess) he = hipStreamSynchronize(L->stream);
     dev_free(d_ptr);
     if (he != hipSuccess) return fail(VBNMF_ERR_HIP, "group state exchange failed: %s", hipGetErrorString(he));
+    return VBNMF_OK;
+}
+
+// Local group: the state exchange after set_state on every member (sums the reduce buffers in place, partition
+// order), then state_finish on each.
+int vbnmf_group_state_finish(vbnmf_comm *c)
+{
+    LoopGroup G{};
+    if (int rc = group_members(c, G)) return rc;
+    if (int rc = use_device(G.e[0])) return rc;
+    if (int rc = group_tables(c)) return rc;
+    for (int p = 0; p < G.count; p++)
+        if (!G.e[p]->prime_pending) return fail(VBNMF_ERR_STATE, "group_state_finish: partition %d has no pending set_state", p);
+    if (int rc = group_sum_in_place(G)) return rc;
     for (int p = 0; p < G.count; p++)
         if (int rc = vbnmf_engine_state_finish(G.e[p])) return rc;
     return VBNMF_OK;
@@ -2731,9 +2783,9 @@ int vbnmf_engine_debug_times(vbnmf_engine *e, unsigned long long *out, int64_t c
 int vbnmf_engine_ml_set_state(vbnmf_engine *e, const double *w, const double *h)
 {
     if (!e || !w || !h) return fail(VBNMF_ERR_BAD_ARG, "NULL argument");
-    if (e->partitioned) return fail(VBNMF_ERR_STATE, "ML-NMF needs an unpartitioned engine");
     if (int rc = use_device(e)) return rc;
     e->has_state = false; e->stats_ready = false; e->step_pending = false; e->prime_pending = false; e->ml_ready = false; e->ids_valid = false;
+    e->ml_prime_pending = false; e->ml_phase = 0;
     try {
         std::vector<double> tmp;
         to_index_major(w, e->n, e->r, e->R, false, tmp);
@@ -2753,8 +2805,29 @@ int vbnmf_engine_ml_set_state(vbnmf_engine *e, const double *w, const double *h)
     int rc = launch_sweep1(e, false);
     e->timing = timing;
     if (rc) return rc;
+    if (e->partitioned) {
+        // the likelihood of the loaded pair needs rowSums(h), the data term and the constant of ALL cells: this partition's go
+        // into the tail of the reduce buffer, the caller sums it over the partitions, vbnmf_engine_ml_state_finish follows
+        if ((rc = launch_ml_tail(e))) return rc;
+        e->ml_prime_pending = true;
+        return VBNMF_OK;
+    }
     if ((rc = launch_ml_final(e))) return rc;
     if ((rc = wait_result(e))) return rc;
+    e->ml_ready = true;
+    return VBNMF_OK;
+}
+
+// Partitioned engines: behind the exchange that follows ml_set_state (vbnmf_engine_allreduce, vbnmf_group_ml_state_finish or
+// the caller's own sum of the reduce buffer) -- the likelihood of the loaded pair (R/factorize.R:40-49) from the reduced tail.
+int vbnmf_engine_ml_state_finish(vbnmf_engine *e)
+{
+    if (!e) return fail(VBNMF_ERR_BAD_ARG, "engine handle is NULL");
+    if (int rc = use_device(e)) return rc;
+    if (!e->ml_prime_pending) return fail(VBNMF_ERR_STATE, "ml_state_finish without a pending ml_set_state on a partitioned engine");
+    if (int rc = launch_ml_final(e)) return rc;
+    if (int rc = wait_result(e)) return rc;          // (bounded: a state exchange whose peer never joined sits on this stream)
+    e->ml_prime_pending = false;
     e->ml_ready = true;
     return VBNMF_OK;
 }
@@ -2770,7 +2843,10 @@ int vbnmf_engine_ml_likelihood(vbnmf_engine *e, double *lk)
 int vbnmf_engine_ml_step(vbnmf_engine *e, int32_t prior, double gamma_a, double gamma_b, double *lk)
 {
     if (!e) return fail(VBNMF_ERR_BAD_ARG, "engine handle is NULL");
+    if (e->partitioned)
+        return fail(VBNMF_ERR_STATE, "a partitioned engine needs ml_step_local / all-reduce / ml_step_local / all-reduce / ml_step_finish");
     if (!e->ml_ready) return fail(VBNMF_ERR_STATE, "ml_step before ml_set_state");
+    if (e->ml_phase) return fail(VBNMF_ERR_STATE, "ml_step between ml_step_local and ml_step_finish");
     if (int rc = use_device(e)) return rc;
     const double eps = 2.220446049250313e-16;        // .Machine$double.eps (R/factorize.R:15,24)
     if (int rc = launch_ml_update(e, false, prior, gamma_a, gamma_b, eps)) return rc;   // H first (:8-15)
@@ -2784,73 +2860,216 @@ int vbnmf_engine_ml_step(vbnmf_engine *e, int32_t prior, double gamma_a, double 
     return VBNMF_OK;
 }
 
+// The host-stepped step of a partitioned engine (reference R/factorize.R:2-27 on this partition's cells, :40-49): two local
+// halves, each followed by one exchange of the reduce buffer, then the likelihood.
+//   1st ml_step_local : k_ml_update(H) (:8-15)  k_sweep1(gene side: w, h_new)  pack -> red = [gene statistics n*R | rowSums(h_new) R | 0 0 | . .]
+//   exchange          : sum over the partitions of red[0 : n*R + R + 2)
+//   2nd ml_step_local : k_ml_update(W <- the reduced statistics) (:17-24)  k_sweep1(cell side: h_new, w_new)
+//                       tail -> red[n*R ...) = [rowSums(h_new) R | 0 0 | sum x log(wh) | sum_{x>0}(-x log x + x)] of this partition
+//   exchange          : sum over the partitions of the tail red[n*R : n*R + R + 4)
+//   ml_step_finish    : lk (:40-49) from the reduced tail and the replicated colSums(w_new)
+// An unpartitioned engine takes the same calls (nothing is packed and there is nothing to exchange).
+int vbnmf_engine_ml_step_local(vbnmf_engine *e, int32_t prior, double gamma_a, double gamma_b)
+{
+    if (!e) return fail(VBNMF_ERR_BAD_ARG, "engine handle is NULL");
+    if (int rc = use_device(e)) return rc;
+    if (!e->ml_ready) return fail(VBNMF_ERR_STATE, "ml_step_local before ml_set_state (or before ml_state_finish on a partitioned engine)");
+    if (e->ml_phase >= 2) return fail(VBNMF_ERR_STATE, "ml_step_local called a third time without ml_step_finish");
+    const double eps = 2.220446049250313e-16;        // .Machine$double.eps (R/factorize.R:15,24)
+    if (e->ml_phase == 0) {
+        if (int rc = launch_ml_update(e, false, prior, gamma_a, gamma_b, eps)) return rc;   // H first (:8-15)
+        if (int rc = launch_sweep1(e, true)) return rc;
+        if (e->partitioned) { if (int rc = launch_ml_pack(e, nullptr)) return rc; }
+    } else {
+        if (int rc = launch_ml_update(e, true, prior, gamma_a, gamma_b, eps)) return rc;    // then W on the new h (:17-24)
+        if (int rc = launch_sweep1(e, false)) return rc;
+        if (e->partitioned) { if (int rc = launch_ml_tail(e)) return rc; }
+    }
+    e->ml_phase++;
+    return VBNMF_OK;
+}
+
+int vbnmf_engine_ml_step_finish(vbnmf_engine *e, double *lk)
+{
+    if (!e) return fail(VBNMF_ERR_BAD_ARG, "engine handle is NULL");
+    if (int rc = use_device(e)) return rc;
+    if (e->ml_phase != 2) return fail(VBNMF_ERR_STATE, "ml_step_finish without ml_step_local (a step has two, each followed by an exchange)");
+    if (int rc = launch_ml_final(e)) return rc;
+    if (int rc = wait_result(e)) return rc;
+    e->ml_phase = 0;
+    if (int rc = harvest_timing(e)) return rc;
+    if (lk) *lk = e->h_out[0];
+    return VBNMF_OK;
+}
+
 }  // extern "C"
 
 namespace {
 
-// The device-driven ML loop of one engine under either stopping rule (ncnn_step 0: the likelihood's, with tol).
-int ml_run_one(vbnmf_engine *e, int32_t prior, double gamma_a, double gamma_b, int32_t max_it, double tol, int32_t ncnn_step,
-               int32_t *it_out, double *lk_out, int32_t *reason_out, double *history, int64_t history_rows, int64_t *changes)
-{
-    const bool conn = ncnn_step > 0;
-    if (int rc = use_device(e)) return rc;
-    const double eps = 2.220446049250313e-16;
-    if (history || changes) { if (int rc = ensure_history(e, (size_t)max_it * (changes ? 2 : 1))) return rc; }
-    e->chg_off = (size_t)max_it;
-    if (conn) { if (int rc = conn_alloc(e)) return rc; }
+// What a step of the device-driven ML loop is run with (the arguments of vbnmf_engine_ml_run* that do not change over the run).
+struct MlStepArgs {
+    int32_t prior;
+    double ga, gb;
+    bool hist, chg, conn;
+    int max_it;
+};
 
-    const bool hist = history != nullptr, chg = changes != nullptr;
-    RunScope S{&e, 1};
-    int rc = S.begin([&](int) { return conn ? ml_conn_ctl(max_it, ncnn_step) : ml_ctl(tol, max_it); });
-    if (!rc && conn) rc = conn_zero(e);
-    if (!rc) rc = drive_loop(&e, 1, true, max_it, e->fold, [&](int) -> int {
+// k_ml_control as a kernel of its own behind the step (no fold; partitioned engines).  reduced: the inputs come summed over the
+// partitions from red_g -- rowSums(h_new) in the tail of the first exchange, [data term | constant] from the second.
+int launch_ml_control(vbnmf_engine *e, bool hist, const MlConn &cn, bool reduced)
+{
+    const size_t nR = (size_t)e->n * e->R;
+    const double *tail = reduced ? e->red_g + nR : nullptr;
+    const double *small = reduced ? e->red_g + nR + e->R + 2 : nullptr;
+    return with_rank(e->R, [&](auto rt) {
+        return launch_kernel<k_ml_control<rt()>>(e, dim3(1), 1024, 0, e->bpW, e->bpH, e->ub, e->epart + e->n_wg, (int64_t)e->n_wg, e->xlx,
+                                                 e->r, (double)e->n, (double)e->m_global, e->ctl, hist ? e->h_hist_dev : nullptr,
+                                                 e->h_out_dev, cn, tail, small);
+    });
+}
+
+// One step of the device-driven ML loop (reference R/factorize.R:194-213 around nmf_updateR, :2-27), queued on every engine of the group.
+//   unpartitioned : k_ml_update(H, + the control step of the previous cell-side sweep)  k_sweep1(gene)  k_ml_update(W)  k_sweep1(cell)
+//   partitioned   : k_ml_update(H)  k_sweep1(gene side: w, h_new)  k_pack_tail | event
+//                   -> comm stream: all-reduce [gene statistics n*R | rowSums(h_new) R | 2]        (RCCL, or k_group_sum)
+//                   -> main stream: k_ml_update(W <- the reduced statistics)  k_sweep1(cell side: h_new, w_new)  k_tail_data
+//                   -> main stream: all-reduce [sum x log(wh) | sum_{x>0}(-x log x + x)]           (two doubles)
+//                   -> k_ml_control on the reduced inputs: the same decision on every partition
+// The W update needs the first exchange, so unlike the VB step nothing runs beside it; it still goes on the comm stream, as
+// queue_vb_step's, so that both loops order their collectives the same way.  The all-reduces are out of place (red -> red_g):
+// behind the stop every kernel returns at once, `red` keeps what the stopping step packed, and the exchanges queued past the
+// stop deliver the same sums again.
+int queue_ml_step(const LoopGroup &G, const MlStepArgs &a)
+{
+    const double eps = 2.220446049250313e-16;        // .Machine$double.eps (R/factorize.R:15,24)
+    if (!G.comm) {
+        vbnmf_engine *e = G.e[0];
         if (e->fold) {
             // k_ml_update(H, with the control step of the PREVIOUS cell-side sweep folded in)  sweep  k_ml_update(W)  sweep ;
             // behind the last step of the run the control step alone (mlnmf.h: MlFold)
             const int t = ++e->fold_step;
-            MlFold f = ml_fold(e, t, hist, e->bpH);
-            if (conn) f.cn = conn_step(e, t, chg);
+            MlFold f = ml_fold(e, t, a.hist, e->bpH);
+            if (a.conn) f.cn = conn_step(e, t, a.chg);
             std::swap(e->bpH, e->bpH_alt);                          // this step's H-side partials go to the other table
-            int q = launch_ml_update(e, false, prior, gamma_a, gamma_b, eps, &f);
+            int q = launch_ml_update(e, false, a.prior, a.ga, a.gb, eps, &f);
             e->stop_ptr = &f.next->stop;
             if (!q) q = launch_sweep1(e, true);
-            if (!q) q = launch_ml_update(e, true, prior, gamma_a, gamma_b, eps);
+            if (!q) q = launch_ml_update(e, true, a.prior, a.ga, a.gb, eps);
             if (!q) q = launch_sweep1(e, false);
-            if (!q && t == max_it) {
-                MlFold g = ml_fold(e, t + 1, hist, e->bpH);
-                if (conn) g.cn = conn_step(e, t + 1, chg);
+            if (!q && t == a.max_it) {
+                MlFold g = ml_fold(e, t + 1, a.hist, e->bpH);
+                if (a.conn) g.cn = conn_step(e, t + 1, a.chg);
                 g.control_only = 1;
-                q = launch_ml_update(e, false, prior, gamma_a, gamma_b, eps, &g);
+                q = launch_ml_update(e, false, a.prior, a.ga, a.gb, eps, &g);
             }
             return q;
         }
         int q;
         MlConn cn{};                                                // (what k_ml_control reads: the table this step fills)
-        if (conn) {
+        if (a.conn) {
             const int t = ++e->fold_step;                           // (no fold: only the rule's step counter here)
             MlFold f{};
-            f.cn = conn_step(e, t, chg);
-            cn = conn_step(e, t + 1, chg);
-            q = launch_ml_update(e, false, prior, gamma_a, gamma_b, eps, &f);
+            f.cn = conn_step(e, t, a.chg);
+            cn = conn_step(e, t + 1, a.chg);
+            q = launch_ml_update(e, false, a.prior, a.ga, a.gb, eps, &f);
         } else {
-            q = launch_ml_update(e, false, prior, gamma_a, gamma_b, eps);
+            q = launch_ml_update(e, false, a.prior, a.ga, a.gb, eps);
         }
         if (!q) q = launch_sweep1(e, true);
-        if (!q) q = launch_ml_update(e, true, prior, gamma_a, gamma_b, eps);
+        if (!q) q = launch_ml_update(e, true, a.prior, a.ga, a.gb, eps);
         if (!q) q = launch_sweep1(e, false);
-        if (q) return q;
-        return with_rank(e->R, [&](auto rt) {
-            hipLaunchKernelGGL((k_ml_control<rt()>), dim3(1), dim3(1024), 0, e->stream, e->bpW, e->bpH, e->ub, e->epart + e->n_wg,
-                               (int64_t)e->n_wg, e->xlx, e->r, (double)e->n, (double)e->m, e->ctl, hist ? e->h_hist_dev : nullptr,
-                               e->h_out_dev, cn);
-            hipError_t le = hipGetLastError();
-            if (le != hipSuccess) return fail(VBNMF_ERR_HIP, "k_ml_control launch failed: %s", hipGetErrorString(le));
-            return (int)VBNMF_OK;
-        });
-    });
-    if ((rc = S.end(rc))) return rc;
-    read_out(&e, 1, it_out, nullptr, lk_out, reason_out, nullptr, history, history_rows, 1);
-    if (conn) conn_finish(&e, 1, changes, max_it);
+        if (!q) q = launch_ml_control(e, a.hist, cn, false);
+        return q;
+    }
+    vbnmf_comm *c = G.comm;
+    const int P = G.count;
+    vbnmf_engine *L = G.e[0];                                  // leader: owner of the comm stream used by a local group
+    const int64_t nbig = L->n * L->R + L->R + 2, nsmall = 2;
+    hipEvent_t evA[64], evB[64];
+    for (int p = 0; p < P; p++) {
+        vbnmf_engine *e = G.e[p];
+        int rc = launch_ml_update(e, false, a.prior, a.ga, a.gb, eps);          // H: this partition's cells, colSums(w) replicated
+        if (!rc) rc = launch_sweep1(e, true);
+        if (!rc) rc = launch_ml_pack(e, &e->ctl->stop);
+        if (rc) return rc;
+        evA[p] = next_event(e);
+        HIPCHECK(hipEventRecord(evA[p], e->stream));
+    }
+    if (c->kind == 0) {
+        HIPCHECK(hipStreamWaitEvent(L->cstream, evA[0], 0));
+        if (int rc = rccl_check(rccl_api().AllReduce(L->red, L->red_g, (size_t)nbig, ncclDouble, ncclSum, c->nc, L->cstream), "ncclAllReduce")) return rc;
+    } else {
+        for (int p = 0; p < P; p++) HIPCHECK(hipStreamWaitEvent(L->cstream, evA[p], 0));
+        hipLaunchKernelGGL(k_group_sum, dim3((unsigned)((nbig + 255) / 256)), dim3(256), 0, L->cstream, c->d_send_big, c->d_recv_big, P, nbig);
+        HIPCHECK(hipGetLastError());
+    }
+    hipEvent_t evBig = next_event(L);
+    HIPCHECK(hipEventRecord(evBig, L->cstream));
+    for (int p = 0; p < P; p++) {
+        vbnmf_engine *e = G.e[p];
+        HIPCHECK(hipStreamWaitEvent(e->stream, evBig, 0));
+        int rc = launch_ml_update(e, true, a.prior, a.ga, a.gb, eps);           // W <- red_g (e->red_in), on every partition the same bits
+        if (!rc) rc = launch_sweep1(e, false);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_tail_data, dim3(1), dim3(1024), 0, e->stream, e->epart + e->n_wg, (int64_t)e->n_wg, e->xlx, e->red + nbig, &e->ctl->stop);
+        HIPCHECK(hipGetLastError());
+        if (p > 0) {                                           // (only where another stream waits on it)
+            evB[p] = next_event(e);
+            HIPCHECK(hipEventRecord(evB[p], e->stream));
+        }
+    }
+    // the second exchange on the leader's main stream, behind the first (queue_vb_step: same order of collectives on every rank)
+    hipEvent_t evD = P > 1 ? next_event(L) : nullptr;
+    if (c->kind == 0) {
+        if (int rc = rccl_check(rccl_api().AllReduce(L->red + nbig, L->red_g + nbig, (size_t)nsmall, ncclDouble, ncclSum, c->nc, L->stream), "ncclAllReduce")) return rc;
+    } else {
+        for (int p = 1; p < P; p++) HIPCHECK(hipStreamWaitEvent(L->stream, evB[p], 0));
+        hipLaunchKernelGGL(k_group_sum_at, dim3(1), dim3(256), 0, L->stream, c->d_send_big, c->d_recv_big, P, nbig, nsmall);
+        HIPCHECK(hipGetLastError());
+    }
+    if (evD) HIPCHECK(hipEventRecord(evD, L->stream));
+    for (int p = 0; p < P; p++) {
+        vbnmf_engine *e = G.e[p];
+        if (evD && e->stream != L->stream) HIPCHECK(hipStreamWaitEvent(e->stream, evD, 0));
+        if (int rc = launch_ml_control(e, a.hist && p == 0, MlConn{}, true)) return rc;
+    }
+    return VBNMF_OK;
+}
+
+// The device-driven ML loop under either stopping rule (ncnn_step 0: the likelihood's, with tol) of one unpartitioned engine, or
+// -- the likelihood's rule only -- of the partitions of one factorisation: a local group, or this process's engine with its
+// RCCL communicator.
+int ml_run_group(const LoopGroup &G, int32_t prior, double gamma_a, double gamma_b, int32_t max_it, double tol, int32_t ncnn_step,
+                 int32_t *it_out, double *lk_out, int32_t *reason_out, double *history, int64_t history_rows, int64_t *changes)
+{
+    vbnmf_engine *e = G.e[0];
+    const bool conn = ncnn_step > 0;
+    for (int p = 0; p < G.count; p++) {
+        if (int rc = use_device(G.e[p])) return rc;
+        if (!G.e[p]->ml_ready) return fail(VBNMF_ERR_STATE, "ml_run before ml_set_state (or before the state exchange of a partitioned engine)");
+        if (G.e[p]->ml_phase) return fail(VBNMF_ERR_STATE, "ml_run between ml_step_local and ml_step_finish");
+    }
+    if (int rc = use_device(e)) return rc;
+    if (history || changes) { if (int rc = ensure_history(e, (size_t)max_it * (changes ? 2 : 1))) return rc; }
+    e->chg_off = (size_t)max_it;
+    if (conn) { if (int rc = conn_alloc(e)) return rc; }
+
+    const MlStepArgs a{prior, gamma_a, gamma_b, history != nullptr, changes != nullptr, conn, max_it};
+    RunScope S{G.e, G.count};
+    S.plain_ctl = G.comm != nullptr;                               // partitioned: the control step is a kernel of its own, on e->ctl
+    int rc = S.begin([&](int) { return conn ? ml_conn_ctl(max_it, ncnn_step) : ml_ctl(tol, max_it); });
+    if (!rc && conn) rc = conn_zero(e);
+    if (G.comm) for (int p = 0; p < G.count; p++) G.e[p]->red_in = G.e[p]->red_g;      // what the W updates read: the receive side
+    if (!rc) rc = drive_loop(G.e, 1, true, max_it, !G.comm && e->fold, [&](int) { return queue_ml_step(G, a); });
+    rc = S.end(rc);
+    if (G.comm) for (int p = 0; p < G.count; p++) G.e[p]->red_in = nullptr;
+    if (rc) return rc;
+    for (int p = 1; p < G.count; p++)                              // (replicated decisions: anything else is a broken exchange)
+        if (G.e[p]->h_out[5] != e->h_out[5] || G.e[p]->h_out[6] != e->h_out[6])
+            return fail(VBNMF_ERR_STATE, "partition %d ended the loop at step %d (reason %d), partition 0 at step %d (reason %d)", p,
+                        (int)G.e[p]->h_out[5], (int)G.e[p]->h_out[6], (int)e->h_out[5], (int)e->h_out[6]);
+    read_out(G.e, 1, it_out, nullptr, lk_out, reason_out, nullptr, history, history_rows, 1);
+    if (conn) conn_finish(G.e, 1, changes, max_it);
     return VBNMF_OK;
 }
 
@@ -2863,10 +3082,46 @@ int vbnmf_engine_ml_run(vbnmf_engine *e, int32_t prior, double gamma_a, double g
                         int32_t *it_out, double *lk_out, int32_t *reason_out, double *history, int64_t history_rows)
 {
     if (!e) return fail(VBNMF_ERR_BAD_ARG, "engine handle is NULL");
-    if (!e->ml_ready) return fail(VBNMF_ERR_STATE, "ml_run before ml_set_state");
     if (max_it < 1) return fail(VBNMF_ERR_BAD_ARG, "max_it must be >= 1");
     if (history && history_rows < max_it) return fail(VBNMF_ERR_BAD_ARG, "history needs max_it doubles");
-    return ml_run_one(e, prior, gamma_a, gamma_b, max_it, tol, 0, it_out, lk_out, reason_out, history, history_rows, nullptr);
+    LoopGroup G{&e, 1, nullptr};
+    if (e->partitioned) {
+        if (!e->comm || e->comm->kind != 0)
+            return fail(VBNMF_ERR_STATE, "the device-driven ML loop of a partitioned engine needs an RCCL communicator (vbnmf_engine_attach_comm), or vbnmf_group_ml_run for a local group");
+        if (int rc = use_device(e)) return rc;
+        if (int rc = ensure_comm_resources(e)) return rc;
+        G.comm = e->comm;
+    }
+    return ml_run_group(G, prior, gamma_a, gamma_b, max_it, tol, 0, it_out, lk_out, reason_out, history, history_rows, nullptr);
+}
+
+// Local group: the exchange behind ml_set_state on every member (the reduce buffers summed in place, partition order), then
+// vbnmf_engine_ml_state_finish on each (the likelihood of the loaded pair, R/factorize.R:40-49).
+int vbnmf_group_ml_state_finish(vbnmf_comm *c)
+{
+    LoopGroup G{};
+    if (int rc = group_members(c, G)) return rc;
+    if (int rc = use_device(G.e[0])) return rc;
+    if (int rc = group_tables(c)) return rc;
+    for (int p = 0; p < G.count; p++)
+        if (!G.e[p]->ml_prime_pending) return fail(VBNMF_ERR_STATE, "group_ml_state_finish: partition %d has no pending ml_set_state", p);
+    if (int rc = group_sum_in_place(G)) return rc;
+    for (int p = 0; p < G.count; p++)
+        if (int rc = vbnmf_engine_ml_state_finish(G.e[p])) return rc;
+    return VBNMF_OK;
+}
+
+// Local group: vbnmf_engine_ml_run (R/factorize.R:194-213, criterion = 'likelihood') for the partitions of one factorisation.
+int vbnmf_group_ml_run(vbnmf_comm *c, int32_t prior, double gamma_a, double gamma_b, int32_t max_it, double tol,
+                       int32_t *it_out, double *lk_out, int32_t *reason_out, double *history, int64_t history_rows)
+{
+    if (max_it < 1) return fail(VBNMF_ERR_BAD_ARG, "max_it must be >= 1");
+    if (history && history_rows < max_it) return fail(VBNMF_ERR_BAD_ARG, "history needs max_it doubles");
+    LoopGroup G{};
+    if (int rc = group_members(c, G)) return rc;
+    if (int rc = use_device(G.e[0])) return rc;
+    if (int rc = group_tables(c)) return rc;
+    return ml_run_group(G, prior, gamma_a, gamma_b, max_it, tol, 0, it_out, lk_out, reason_out, history, history_rows, nullptr);
 }
 
 // ... under criterion = 'connectivity' (reference R/factorize.R:198-208): the labels which.max(h[, j]) of every step are formed
@@ -2880,9 +3135,11 @@ int vbnmf_engine_ml_run_connectivity(vbnmf_engine *e, int32_t prior, double gamm
     if (max_it < 1 || ncnn_step < 1) return fail(VBNMF_ERR_BAD_ARG, "max_it and ncnn_step must be >= 1");
     if (history && history_rows < max_it) return fail(VBNMF_ERR_BAD_ARG, "history needs max_it doubles");
     if (changes && changes_rows < max_it) return fail(VBNMF_ERR_BAD_ARG, "changes needs max_it counts");
-    if (e->partitioned) return fail(VBNMF_ERR_STATE, "ML-NMF needs an unpartitioned engine");
-    if (!e->ml_ready) return fail(VBNMF_ERR_STATE, "ml_run_connectivity before ml_set_state");
-    return ml_run_one(e, prior, gamma_a, gamma_b, max_it, 0.0, ncnn_step, it_out, lk_out, reason_out, history, history_rows, changes);
+    if (e->partitioned)
+        return fail(VBNMF_ERR_STATE, "criterion = 'connectivity' is not available on a partitioned engine (the label tables are not all-reduced); "
+                                     "run the host rule on ml_get_state, or the likelihood criterion");
+    LoopGroup G{&e, 1, nullptr};
+    return ml_run_group(G, prior, gamma_a, gamma_b, max_it, 0.0, ncnn_step, it_out, lk_out, reason_out, history, history_rows, changes);
 }
 
 int vbnmf_engine_ml_get_state(vbnmf_engine *e, double *w, double *h)

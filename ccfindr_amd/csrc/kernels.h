@@ -1494,6 +1494,18 @@ __global__ __launch_bounds__(256) void k_group_sum(const double *const *__restri
     for (int p = 0; p < parts; p++) recv[p][i] = s;
 }
 
+// The same on `count` doubles from offset `off` of every partition's buffer (the two-double exchange of the partitioned ML loop,
+// mlnmf.h, whose offset does not depend on the VB loop's fold as the send / receive tables of its own small exchange do).
+__global__ __launch_bounds__(256) void k_group_sum_at(const double *const *__restrict__ send, double *const *__restrict__ recv,
+                                                      int parts, int64_t off, int64_t count)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= count) return;
+    double s = send[0][off + i];
+    for (int p = 1; p < parts; p++) s += send[p][off + i];
+    for (int p = 0; p < parts; p++) recv[p][off + i] = s;
+}
+
 // Sum of v[0..count) by one 1024-thread block, fixed order: thread t adds t, t+1024, ...; a shuffle tree per wave; the
 // 16 wave sums through LDS and one more shuffle tree.  Two barriers (the ten-round LDS tree it replaces cost k_control
 // and k_final about a microsecond each).

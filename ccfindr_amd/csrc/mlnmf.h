@@ -10,6 +10,10 @@
 // The cell-side sweep at the END of step t runs on (w_new, h_new): it yields the statistics the H update of
 // step t+1 starts from AND sum x log(wh) of step t's likelihood; sum(wh) = sum_k colSum(w)_k rowSum(h)_k comes
 // from the updates' block partials, and sum_{x>0}(-x log x + x) is a constant of X computed once at ingestion.
+// Cells partitioned over several engines (W replicated, partition p holding its columns of h): the same kernels around two exchanges,
+//   k_ml_update(H) -> k_sweep1(gene) -> k_pack_tail -> ALL-REDUCE [statistics n*R | rowSums(h_new)] -> k_ml_update(W, dense form)
+//   -> k_sweep1(cell) -> k_tail_data -> ALL-REDUCE [sum x log(wh) | constant] -> k_ml_control / k_ml_final on the reduced values
+// (engine.hip: queue_ml_step; host-stepped: vbnmf_engine_ml_step_local / ml_step_finish).
 #pragma once
 #include "kernels.h"
 
@@ -103,12 +107,16 @@ __device__ __forceinline__ void ml_update_body(
     __shared__ uint32_t s_ids[kStageIds];
     __shared__ int32_t s_ptr[kStagePtr];
     const int t = threadIdx.x;
+    // Cell-partitioned engines, W side (the twin of k_update's dense form, kernels.h): `part` holds the statistics already summed
+    // over a gene's tasks AND over the partitions -- the reduce buffer behind the all-reduce, [nmaj][R] -- and other_bp is ONE
+    // row, its reduced tail rowSums(h_new) of all cells.  No inverse index: nothing to stage, no further LDS.
+    const bool dense = inv_ptr == nullptr;               // (uniform over the launch)
     // the block's stretch of the inverse index into LDS, first thing (as k_update, kernels.h)
     const int64_t per0 = (nmaj + gridDim.x - 1) / gridDim.x;
     const int64_t bm0 = (int64_t)blockIdx.x * per0, bm1 = min(nmaj, bm0 + per0);
     int q_lo = 0;
     bool staged = false;
-    if (stage_ids && !fold.control_only && bm0 < bm1 && bm1 - bm0 < kStagePtr) {
+    if (stage_ids && !dense && !fold.control_only && bm0 < bm1 && bm1 - bm0 < kStagePtr) {
         q_lo = inv_ptr[bm0];
         const int q_hi = inv_ptr[bm1];
         staged = q_hi - q_lo <= kStageIds;               // (block-uniform)
@@ -206,6 +214,7 @@ __device__ __forceinline__ void ml_update_body(
                 const size_t o = (size_t)M * R + k;
                 if (k < r) {
                     const double s = staged ? task_sum_lds(part, s_ids, s_ptr[M - bm0] - q_lo, s_ptr[M - bm0 + 1] - q_lo, R, k)
+                                   : dense  ? part[o]
                                             : task_sum(part, inv_task, inv_ptr[M], inv_ptr[M + 1], R, k);
                     double up = f[o] * s;
                     if (prior) up = up + ga - 1.0;
@@ -246,6 +255,7 @@ __device__ __forceinline__ void ml_update_body(
             const size_t o = (size_t)M * R + k;
             if (k < r) {
                 const double s = staged ? task_sum_lds(part, s_ids, s_ptr[M - bm0] - q_lo, s_ptr[M - bm0 + 1] - q_lo, R, k)
+                               : dense  ? part[o]
                                         : task_sum(part, inv_task, inv_ptr[M], inv_ptr[M + 1], R, k);
                 double up = f[o] * s;
                 if (prior) up = up + ga - 1.0;   // :11,20
@@ -312,18 +322,28 @@ __global__ __launch_bounds__(NT) void k_sweep1_batch(const SweepSide *__restrict
 }
 
 // Likelihood (R/factorize.R:40-49).  One block.  out = [lk, sum x log(wh), sum(wh), 0, 0], out_host[7] = seq.
+// Cell-partitioned engines (tail != null): rowSums(h), the data term and the constant arrive summed over the partitions --
+// tail = [rowSums(h)_k (R) | . | . | sum x log(wh) | sum_{x>0}(-x log x + x)], k_tail's shape behind the all-reduce -- and
+// colSums(w) from bpW, which is replicated; m is then the GLOBAL cell count.
 template <int R>
 __global__ __launch_bounds__(1024) void k_ml_final(const double *__restrict__ bpW, const double *__restrict__ bpH, int nb,
                                                    const double *__restrict__ epart, int64_t nepart, double xlx, int r,
                                                    double n, double m, double seq, double *__restrict__ out,
-                                                   double *__restrict__ out_host)
+                                                   double *__restrict__ out_host, const double *__restrict__ tail)
 {
     __shared__ double sW[R + 2], sH[R + 2];
     __shared__ double sm[1024];
     double part = 0.0;                           // the three reductions' loads travel together
+    if (tail) {
+        bp_colsums(bpW, nb, R + 2, sW, 1024);
+        if (threadIdx.x < R) sH[threadIdx.x] = tail[threadIdx.x];
+        xlx = tail[R + 3];
+    } else {
     for (int64_t q = threadIdx.x; q < nepart; q += 1024) part += epart[q];
     bp_colsums2(bpW, bpH, nb, R + 2, sW, sH, 1024);
-    const double data = block_sum(part, sm);
+    }
+    double data = block_sum(part, sm);           // (its barriers also publish sW / sH)
+    if (tail) data = tail[R + 2];
     if (threadIdx.x == 0) {
         double cross = 0.0;
         for (int k = 0; k < r; k++) cross += sW[k] * sH[k];
@@ -342,18 +362,28 @@ template <int R>
 __global__ __launch_bounds__(1024) void k_ml_control(const double *__restrict__ bpW, const double *__restrict__ bpH, int nb,
                                                      const double *__restrict__ epart, int64_t nepart, double xlx, int r,
                                                      double n, double m, LoopCtl *ctl, double *__restrict__ history,
-                                                     double *__restrict__ out_host, const MlConn cn)
+                                                     double *__restrict__ out_host, const MlConn cn,
+                                                     const double *__restrict__ tail, const double *__restrict__ small)
 {
+    // Cell-partitioned engines (tail != null; as k_control, kernels.h): tail = rowSums(h_new) of ALL cells, the reduced tail of
+    // the step's first all-reduce; small = [sum x log(wh) | sum_{x>0}(-x log x + x)] summed over the partitions by the second;
+    // colSums(w_new) from bpW, replicated; m is the GLOBAL cell count.  Every partition forms the same decision from the same bits.
     __shared__ double sW[R + 2], sH[R + 2];
     __shared__ double sm[1024];
     __shared__ unsigned long long s_nch;
     const int stopped = ctl->stop;               // tested once the reductions' loads are in flight too
     double part = 0.0;
+    if (tail) {
+        bp_colsums(bpW, nb, R + 2, sW, 1024);
+        if (threadIdx.x < R) sH[threadIdx.x] = tail[threadIdx.x];
+    } else {
     for (int64_t q = threadIdx.x; q < nepart; q += 1024) part += epart[q];
     bp_colsums2(bpW, bpH, nb, R + 2, sW, sH, 1024);
+    }
     if (stopped) return;
     if (cn.ids_out) block_label_changes(cn.tab_read, r, &s_nch, 1024);   // criterion = 'connectivity': the table this step's H update filled
-    const double data = block_sum(part, sm);
+    double data = block_sum(part, sm);           // (its barriers also publish sW / sH)
+    if (tail) { data = small[0]; xlx = small[1]; }
     if (threadIdx.x != 0) return;
     double cross = 0.0;
     for (int k = 0; k < r; k++) cross += sW[k] * sH[k];

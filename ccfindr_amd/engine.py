@@ -284,6 +284,7 @@ class VBEngine:
         n, m, r = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int32()
         N.check(L.vbnmf_engine_dims(self._h, ctypes.byref(n), ctypes.byref(m), ctypes.byref(r)))
         self.n, self.m, self.rank = n.value, m.value, r.value
+        self.m_global = int(mg)
         self.device = int(device)
 
     # -- state ---------------------------------------------------------------------------
@@ -328,11 +329,32 @@ class VBEngine:
         return lkh.value, tuple(st)
 
     # -- maximum-likelihood NMF on the same engine (reference R/factorize.R:2-27, :40-49) ----
-    def ml_set_state(self, w, h):
+    def ml_set_state(self, w, h, finish=True):
+        """Load the pair.  An unpartitioned engine finishes inside the call.  A partitioned one (``cols`` narrower than
+        ``m_global``) leaves its share of the loaded pair's likelihood in the tail of the reduce buffer; with ``finish`` and an RCCL
+        communicator attached the library's all-reduce and ``ml_state_finish`` follow here, every process making the same call.
+        ``finish=False``, a local group or no communicator: the caller sums the tail over the partitions
+        (``Communicator.ml_state_finish`` for a group) and calls ``ml_state_finish``."""
         w, h = N.fcol(w), N.fcol(h)
         if w.shape != (self.n, self.rank) or h.shape != (self.rank, self.m):
             raise ValueError(f"state shapes must be w {(self.n, self.rank)}, h {(self.rank, self.m)}")
         N.check(self._lib.vbnmf_engine_ml_set_state(self._h, N.dptr(w), N.dptr(h)))
+        if finish and self.m != self.m_global and getattr(getattr(self, "comm", None), "kind", None) == "rccl":
+            self.allreduce()
+            self.ml_state_finish()
+
+    def ml_state_finish(self):
+        N.check(self._lib.vbnmf_engine_ml_state_finish(self._h))
+
+    def ml_step_local(self, prior=False, gamma_a=1.0, gamma_b=1.0):
+        """One half of a partitioned ML step; a step is ``ml_step_local`` / sum of the reduce buffer / ``ml_step_local`` /
+        sum of its tail / ``ml_step_finish`` (include/vbnmf.h)."""
+        N.check(self._lib.vbnmf_engine_ml_step_local(self._h, int(bool(prior)), float(gamma_a), float(gamma_b)))
+
+    def ml_step_finish(self):
+        lk = ctypes.c_double()
+        N.check(self._lib.vbnmf_engine_ml_step_finish(self._h, ctypes.byref(lk)))
+        return lk.value
 
     def ml_step(self, prior=False, gamma_a=1.0, gamma_b=1.0):
         """One nmf_updateR step on the resident (w, h) -> likelihood of the updated pair."""
@@ -470,6 +492,12 @@ class VBEngine:
         p, c = ctypes.c_void_p(), ctypes.c_int64()
         N.check(self._lib.vbnmf_engine_reduce_buffer(self._h, ctypes.byref(p), ctypes.byref(c)))
         return p.value, c.value
+
+    def reduce_tail(self):
+        """(offset, count) of the reduce buffer's tail, the part the ML protocol's second exchanges carry."""
+        o, c = ctypes.c_int64(), ctypes.c_int64()
+        N.check(self._lib.vbnmf_engine_reduce_tail(self._h, ctypes.byref(o), ctypes.byref(c)))
+        return o.value, c.value
 
     def reduce_tensor(self):
         """The reduce buffer as a torch CUDA tensor aliasing the engine's memory."""
@@ -636,6 +664,21 @@ class Communicator:
         return {"it": it.value, "lk0": lk0.value, "lkh": lkh.value, "reason": reason.value,
                 "hyper": dict(zip(("aw", "bw", "ah", "bh"), (float(v) for v in hy))),
                 "history": hist[:it.value] if history else None}
+
+    def ml_state_finish(self):
+        N.check(self._lib.vbnmf_group_ml_state_finish(self._h))
+
+    def ml_run(self, Itmax=10000, Tol=1e-5, prior=False, gamma_a=1.0, gamma_b=1.0, history=False):
+        """``VBEngine.ml_run`` under the likelihood criterion for the whole local group (same result dictionary)."""
+        it, reason, lk = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_double()
+        hist = np.empty(int(Itmax)) if history else None
+        N.check(self._lib.vbnmf_group_ml_run(self._h, int(bool(prior)), float(gamma_a), float(gamma_b), int(Itmax), float(Tol),
+                                             ctypes.byref(it), ctypes.byref(lk), ctypes.byref(reason), N.dptr(hist),
+                                             int(Itmax) if history else 0))
+        out = {"it": it.value, "lk": lk.value, "reason": reason.value}
+        if history:
+            out["history"] = hist[:it.value].copy()
+        return out
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:

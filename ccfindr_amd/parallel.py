@@ -558,13 +558,17 @@ class CellPartitionedEngine:
             self._red = engine.reduce_tensor()
         self._stream_ctx = getattr(engine, "stream_context", None)
 
-    def _allreduce(self):
+    def _allreduce(self, tail=False):
+        """Sum the reduce buffer over the partitions, in place; ``tail``: only its last R + 4 doubles (the ML protocol's
+        exchanges behind ``ml_set_state`` and the second ``ml_step_local`` -- the library's own all-reduce knows by itself)."""
         if self.native:
             self.engine.allreduce()
             return
         if self.world == 1:
             return
         red = self._red
+        if tail:
+            red = red[self.engine.reduce_tail()[0]:]
         staged = getattr(red, "is_cuda", False) and self._dist.get_backend(self.group) != "nccl"
         if staged:
             # a backend that cannot reduce device memory (gloo: rehearsals of the multi-process path on one GPU):
@@ -598,6 +602,55 @@ class CellPartitionedEngine:
         if not self.native and not (self.world == 1 and hasattr(self.engine, "run") and self.m == self.m_global):
             raise RuntimeError("the device-driven loop of a partitioned run needs the native (RCCL) communicator")
         return self.engine.run(hyper, **kw)
+
+    # -- ML-NMF (factorize()'s step, reference R/factorize.R:2-27, :40-49) with the cells partitioned -------------------
+    @property
+    def _partitioned(self):
+        return self.world > 1 or (self.native and self.m != self.m_global)
+
+    def ml_set_state(self, w, h):
+        """``h`` is the FULL r x m matrix; this process loads its own block."""
+        cb, ce = self.cols
+        if self._partitioned and not self.native:            # the exchange is torch.distributed's: finish here
+            self.engine.ml_set_state(w, np.asarray(h)[:, cb:ce], finish=False)
+            self._allreduce(tail=True)
+            self.engine.ml_state_finish()
+        else:                                                # unpartitioned, or the library's own all-reduce inside the call
+            self.engine.ml_set_state(w, np.asarray(h)[:, cb:ce])
+
+    def ml_step(self, prior=False, gamma_a=1.0, gamma_b=1.0):
+        """One nmf_updateR step across the partitions -> the likelihood of the updated pair, the same on every process:
+        H update and gene-side sweep, exchange, W update and cell-side sweep, exchange of the tail, likelihood."""
+        if not self._partitioned:
+            return self.engine.ml_step(prior, gamma_a, gamma_b)
+        self.engine.ml_step_local(prior, gamma_a, gamma_b)
+        self._allreduce()
+        self.engine.ml_step_local(prior, gamma_a, gamma_b)
+        self._allreduce(tail=True)
+        return self.engine.ml_step_finish()
+
+    def ml_run(self, Itmax=10000, Tol=1e-5, prior=False, gamma_a=1.0, gamma_b=1.0, history=False, criterion="likelihood", **kw):
+        """The device-driven loop of ``VBEngine.ml_run`` across the partitions under the likelihood criterion (native
+        communicator, or a single process).  ``criterion='connectivity'`` is refused: the label tables of the partitions
+        are not all-reduced -- pass ``device_loop=False`` to ``factorize`` and the host rule reads ``ml_get_state``."""
+        if criterion == "connectivity":
+            raise ValueError("criterion='connectivity' has no device-driven loop on a cell-partitioned engine; "
+                             "use the host rule (factorize(..., device_loop=False))")
+        if criterion != "likelihood":
+            raise ValueError("Unknown stopping criterion.")
+        if self._partitioned and not self.native:
+            raise RuntimeError("the device-driven loop of a partitioned run needs the native (RCCL) communicator")
+        return self.engine.ml_run(Itmax=Itmax, Tol=Tol, prior=prior, gamma_a=gamma_a, gamma_b=gamma_b, history=history, **kw)
+
+    def ml_likelihood(self):
+        return self.engine.ml_likelihood()
+
+    def ml_get_state(self, names=("ew", "eh")):
+        """``ew`` replicated, ``eh`` all-gathered to the full r x m matrix, as ``get_state``."""
+        local = self.engine.ml_get_state(names)
+        if self.world > 1 and "eh" in local:
+            local["eh"] = self._gather_cells(local["eh"])
+        return local
 
     def _gather_cells(self, a):
         """r x m_local blocks -> the full r x m matrix on every process (one tensor all_gather, blocks padded to the

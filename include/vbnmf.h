@@ -378,7 +378,7 @@ int vbnmf_update_csc(int64_t n, int64_t m, int32_t r, const int32_t *p, const in
  * factorize(), reference R/factorize.R:2-27 (nmf_updateR) with its likelihood :40-49
  * (the two are always called together, :195-196).  The factors live on the device
  * between steps; a VB state and an ML state exclude each other (setting one drops the
- * other).  Unpartitioned engines only.
+ * other).  Partitioned engines: see "ML-NMF with the cells partitioned" below.
  *
  *   ml_set_state  w : n x r column-major, h : r x m column-major (init, :30-38)
  *   ml_step       h <- h .* (t(w) %*% (x/(w h))) / colSums(w), clipped at double eps (:8-15);
@@ -428,6 +428,55 @@ int vbnmf_batch_ml_run_connectivity(vbnmf_engine **engines, int32_t count, int32
                                     double *history, int64_t history_rows, int64_t *changes, int64_t changes_rows);
 int vbnmf_engine_ml_likelihood(vbnmf_engine *e, double *lk);
 int vbnmf_engine_ml_get_state(vbnmf_engine *e, double *w, double *h);
+
+/* ---------------------------------------------------------------------------------
+ * ML-NMF with the cells partitioned (engines of vbnmf_engine_create_part; communicators as above).  Partition p holds
+ * its own columns of h and a full copy of w.  One step of nmf_updateR (R/factorize.R:2-27) needs TWO exchanges, because
+ * the W update (:17-24) reads statistics of all cells on the new h and the likelihood (:40-49) needs the new w:
+ *
+ *   h_p <- update (:8-15) on the partition's own statistics, colSums(w) replicated
+ *   exchange 1 : [ (x / (w h_new)) %*% t(h_new) summed over the partition's cells (n x r, index-major, padded rank)
+ *                | rowSums(h_new) (R) | 0 0 ]                     = the reduce buffer's first n*R + R + 2 doubles
+ *   w   <- update (:17-24) on the summed statistics: bit-identical on every partition
+ *   exchange 2 : [ sum x log(w h) | sum_{x>0}(-x log x + x) ] over the partition's cells   (:44-47)
+ *   lk  = ((data - sum_k colSum(w)_k rowSum(h)_k) + const) / n / m_global                  (:48)
+ *
+ * Host-stepped (vbnmf_engine_reduce_buffer names the buffer, n*R + R + 4 doubles; `sum` is vbnmf_engine_allreduce or the
+ * caller's own in-place sum over the partitions):
+ *
+ *   vbnmf_engine_ml_set_state(e, w, h_p)      leaves [rowSums(h_p) (R) | 0 0 | data term | constant] in the buffer's TAIL,
+ *                                             the R + 4 doubles from offset n*R
+ *   sum(tail) ; vbnmf_engine_ml_state_finish(e)                     likelihood of the loaded pair
+ *   vbnmf_engine_ml_step_local(e, ...)        1st call of a step: H update, gene-side sweep, exchange 1 packed into the buffer
+ *   sum(buffer)                               (at least its first n*R + R + 2 doubles)
+ *   vbnmf_engine_ml_step_local(e, ...)        2nd call: W update, cell-side sweep, the TAIL as after ml_set_state
+ *   sum(tail)                                 (summing the whole buffer again is harmless: only the tail is read)
+ *   vbnmf_engine_ml_step_finish(e, &lk)       the likelihood, the same on every partition
+ *
+ * The protocol is "sum the buffer at every exchange"; only the tail is READ behind the exchanges marked sum(tail), so a caller may
+ * send the tail alone there (vbnmf_engine_reduce_tail names it), and vbnmf_engine_allreduce does -- an optimisation that spares a
+ * second n*R all-reduce per step, with the same results as summing everything.  An unpartitioned engine accepts the same calls
+ * (nothing to sum).  vbnmf_engine_ml_step on a partitioned engine is VBNMF_ERR_STATE, as vbnmf_engine_step is;
+ * vbnmf_engine_ml_step_finish without both ml_step_local calls, and ml_state_finish without a pending ml_set_state, too.
+ *
+ * Device-driven (R/factorize.R:194-213, criterion = 'likelihood'): vbnmf_engine_ml_run on an engine with an RCCL
+ * communicator attached, vbnmf_group_ml_run for a local group -- arguments and results as vbnmf_engine_ml_run, history from
+ * partition 0.  Both exchanges are queued by the library, out of place, so the steps queued past the stop change nothing;
+ * the control step reads only reduced values, so every partition stops at the same step.  vbnmf_group_ml_state_finish is
+ * the exchange behind ml_set_state plus ml_state_finish on every member.  Sums run per partition first, then across the
+ * partitions in partition order: results agree with the single engine to rounding, not bit for bit.
+ * vbnmf_engine_ml_get_state / ml_likelihood answer for the partition (its own columns of h; the global likelihood).
+ * criterion = 'connectivity' (vbnmf_engine_ml_run_connectivity, :198-208) stays VBNMF_ERR_STATE on a partitioned engine:
+ * the contingency tables of the labels would need an all-reduce of their own.
+ * --------------------------------------------------------------------------------- */
+/* Where the TAIL of the reduce buffer starts and how many doubles it holds (n*R, R + 4; either pointer may be NULL). */
+int vbnmf_engine_reduce_tail(const vbnmf_engine *e, int64_t *offset, int64_t *count);
+int vbnmf_engine_ml_state_finish(vbnmf_engine *e);
+int vbnmf_engine_ml_step_local(vbnmf_engine *e, int32_t prior, double gamma_a, double gamma_b);
+int vbnmf_engine_ml_step_finish(vbnmf_engine *e, double *lk);
+int vbnmf_group_ml_state_finish(vbnmf_comm *c);
+int vbnmf_group_ml_run(vbnmf_comm *c, int32_t prior, double gamma_a, double gamma_b, int32_t max_it, double tol,
+                       int32_t *it, double *lk, int32_t *reason, double *history, int64_t history_rows);
 /* Stateless forms of the same step: nmf_updateR(x, w, h, n, m, r, prior, gamma.a, gamma.b)
  * followed by likelihood(x, w, h) (R/factorize.R:2-27, :40-49); throw-away engine on device 0 (VBNMF_DEVICE overrides). */
 int vbnmf_ml_update_dense(int64_t n, int64_t m, int32_t r, const double *X,
