@@ -9,7 +9,7 @@ OBJ := build/obj
 CXXFLAGS ?= -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-function -pthread
 HIPFLAGS ?= $(CXXFLAGS) --offload-arch=$(ARCH)
 HOST_HDRS := $(CSRC)/common.h include/vbnmf.h
-DEV_HDRS := $(HOST_HDRS) $(CSRC)/kernels.h $(CSRC)/mlnmf.h $(CSRC)/special.h $(CSRC)/init.h $(CSRC)/comm.h
+DEV_HDRS := $(HOST_HDRS) $(CSRC)/kernels.h $(CSRC)/mlnmf.h $(CSRC)/special.h $(CSRC)/init.h $(CSRC)/consensus.h $(CSRC)/comm.h
 
 all: $(LIB) oracle testlibs
 
@@ -33,11 +33,15 @@ $(OBJ)/order.o: $(CSRC)/order.cpp $(HOST_HDRS)
 	mkdir -p $(OBJ)
 	$(HIPCC) $(CXXFLAGS) -c -o $@ $<
 
+$(OBJ)/consensus.o: $(CSRC)/consensus.cpp $(HOST_HDRS)
+	mkdir -p $(OBJ)
+	$(HIPCC) $(CXXFLAGS) -c -o $@ $<
+
 $(OBJ)/engine.o: $(CSRC)/engine.hip $(DEV_HDRS)
 	mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c -o $@ -x hip $<
 
-$(LIB): $(OBJ)/host.o $(OBJ)/layout.o $(OBJ)/blob.o $(OBJ)/mtx.o $(OBJ)/order.o $(OBJ)/engine.o
+$(LIB): $(OBJ)/host.o $(OBJ)/layout.o $(OBJ)/blob.o $(OBJ)/mtx.o $(OBJ)/order.o $(OBJ)/consensus.o $(OBJ)/engine.o
 	mkdir -p $(dir $(LIB))
 	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) -o $@ $^ -pthread
 

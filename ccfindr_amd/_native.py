@@ -22,6 +22,8 @@ c_double_p = ctypes.POINTER(ctypes.c_double)
 c_int32_p = ctypes.POINTER(ctypes.c_int32)
 c_int64_p = ctypes.POINTER(ctypes.c_int64)
 c_uint32_p = ctypes.POINTER(ctypes.c_uint32)
+c_uint64_p = ctypes.POINTER(ctypes.c_uint64)
+c_uint8_p = ctypes.POINTER(ctypes.c_uint8)
 
 OK, ERR_BAD_ARG, ERR_NO_DEVICE, ERR_HIP, ERR_OOM, ERR_STATE = range(6)
 MAX_RANK = 128
@@ -148,6 +150,17 @@ SIGNATURES = {
     "vbnmf_engine_cluster_ids": (ctypes.c_int, [_VP, c_int32_p]),
     "vbnmf_engine_spmm": (ctypes.c_int, [_VP, _I32, c_double_p, c_double_p]),
     "vbnmf_engine_cluster_changes": (ctypes.c_int, [_VP, c_int64_p, c_int32_p]),
+    "vbnmf_consensus_create": (ctypes.c_int, [_I64, _I32, _I32, _I32, _VPP]),
+    "vbnmf_consensus_destroy": (None, [_VP]),
+    "vbnmf_consensus_reset": (ctypes.c_int, [_VP]),
+    "vbnmf_consensus_add_engine": (ctypes.c_int, [_VP, _VP]),
+    "vbnmf_consensus_add_labels": (ctypes.c_int, [_VP, c_int32_p]),
+    "vbnmf_consensus_sums": (ctypes.c_int, [_VP, c_int32_p, c_uint64_p, c_uint64_p, c_int32_p]),
+    "vbnmf_consensus_dispersion": (ctypes.c_int, [_VP, c_double_p]),
+    "vbnmf_consensus_labels": (ctypes.c_int, [_VP, _I32, c_int32_p]),
+    "vbnmf_cophenetic_grouped": (ctypes.c_int, [_I64, _I32, c_uint8_p, c_int64_p, ctypes.c_char_p, c_double_p]),
+    "vbnmf_consensus_cophenetic": (ctypes.c_int, [_VP, ctypes.c_char_p, _I64, c_double_p, c_int64_p]),
+    "vbnmf_test_cophenetic_dist": (ctypes.c_int, [_I64, c_double_p, c_int64_p, ctypes.c_char_p, c_double_p]),
     "vbnmf_engine_random_state": (ctypes.c_int, [_VP, _D, _D, _D, _D, ctypes.c_uint64]),
     "vbnmf_engine_svd": (ctypes.c_int, [_VP, _I32, _D, _I32, ctypes.c_uint64, c_double_p, c_double_p, c_double_p, c_int32_p]),
     "vbnmf_layout_build": (ctypes.c_int, [_VP, _I64, _I64, _I32, _I32, _VPP, ctypes.POINTER(LayoutView)]),

@@ -20,6 +20,9 @@ void set_error(const char *fmt, ...);
 int fail(int code, const char *fmt, ...);
 int env_int(const char *name, int dflt);    // an integer environment switch (unset or empty: dflt)
 
+// The consensus accumulator's label matrix on the host (engine.hip, for consensus.cpp): labels[run * m + cell], runs rows.
+int consensus_download(vbnmf_consensus *c, std::vector<uint8_t> &labels, int64_t &m, int32_t &runs, int32_t &unlabelled);
+
 // ---- simple fork-join over [0, count) with std::thread (no OpenMP runtime needed) ----
 void parallel_for(int64_t count, const std::function<void(int64_t begin, int64_t end, int tid)> &fn,
                   int max_threads = 0);

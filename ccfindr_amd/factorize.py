@@ -13,12 +13,14 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _native as N
+from .consensus import METHODS as TABLE_LINKAGES
+from .consensus import Consensus
 from .engine import CountMatrix, VBEngine, auto_batch
 
 BATCH_MAX_RANK = 16          # ranks the batch kernels are built for (csrc/engine.hip: kBatchMaxPaddedRank)
 
 # Above this many cell pairs the O(m^2) connectivity vector (R/factorize.R:51-60) is not formed: dispersion
-# and cophenetic are NaN (the reference would try to allocate it).
+# and cophenetic come from the label tables instead (consensus.py; ``factorize(consensus=...)``).
 MAX_PAIRS = 60_000_000
 
 
@@ -126,7 +128,7 @@ class MLResult:
 
 def factorize(mat, ranks=2, nrun=20, randomize=False, nsmpl=1, verbose=2, progress_bar=True, Itmax=10000,
               ncnn_step=40, criterion="likelihood", linkage="average", Tol=1e-5, store_connectivity=False,
-              seed=None, device=0, engine_factory=None, device_loop=True, batch=None):
+              seed=None, device=0, engine_factory=None, device_loop=True, batch=None, consensus=None):
     """Maximum-likelihood NMF of a count matrix on the MI355X engine; reference R/factorize.R:140-320.
 
     ``mat``: genes x cells counts (dense array, scipy sparse, or ``CountMatrix``).  ``seed`` seeds the numpy
@@ -138,7 +140,12 @@ def factorize(mat, ranks=2, nrun=20, randomize=False, nsmpl=1, verbose=2, progre
     the rank is at most 16 and the matrix holds up to 2e7 stored entries) -- on a small matrix one loop cannot fill the GPU.
     Under ``criterion='connectivity'`` restarts are batched only when ``batch > 1`` is passed: a batch's narrower grids
     change the sums' order, and a rounding difference can flip a label and move this rule's stop.
-    The restarts draw their starts from the same stream in the same order either way.  Returns ``MLResult``.
+    The restarts draw their starts from the same stream in the same order either way.  ``consensus``: how dispersion and
+    cophenetic (:218-230) are formed.  ``'pairs'``: the reference's O(m^2) pair vector on the host (NaN above ``MAX_PAIRS``
+    pairs); ``'tables'``: from the runs' label vectors on the device (``Consensus``: contingency tables for the dispersion,
+    the distinct label tuples for the cophenetic; ``linkage`` 'average', 'single' or 'complete'; no ``store_connectivity``);
+    None: ``'pairs'`` up to ``MAX_PAIRS`` pairs, ``'tables'`` above (NaN there without a device or under another ``linkage``).
+    Returns ``MLResult``.
     """
     del progress_bar
     if isinstance(mat, CountMatrix):
@@ -162,6 +169,15 @@ def factorize(mat, ranks=2, nrun=20, randomize=False, nsmpl=1, verbose=2, progre
         raise ValueError("Unknown stopping criterion.")                            # :215
     if randomize and host is None:
         raise ValueError("randomize needs the host matrix, not a CountMatrix")
+    if consensus not in (None, "pairs", "tables"):
+        raise ValueError("consensus must be None, 'pairs' or 'tables'")
+    tables = consensus == "tables" or (consensus is None and not pairs_ok and N.load().vbnmf_device_count() > 0)
+    if tables:
+        pairs_ok = False
+        if consensus == "tables" and linkage not in TABLE_LINKAGES:
+            raise ValueError("consensus='tables' serves the linkages %s" % ", ".join(TABLE_LINKAGES))
+        if consensus == "tables" and store_connectivity:
+            raise ValueError("store_connectivity needs the pair vector: consensus='pairs'")
     rng = np.random.default_rng(seed)
     out = MLResult(ranks=ranks)
     rave, dave, coav = np.zeros(nrank), np.zeros(nrank), np.zeros(nrank)
@@ -174,8 +190,11 @@ def factorize(mat, ranks=2, nrun=20, randomize=False, nsmpl=1, verbose=2, progre
             say(f"Rank {rank}")
         wsum = hsum = None
         rdat, ddat, cdat = [], [], []
+        cons = Consensus(ncol, rank, nrun, device=device) if tables else None
         for ismpl in range(1, nsmpl + 1):
             conav = np.zeros(npair) if pairs_ok else None                          # :174
+            if cons is not None and ismpl > 1:
+                cons.reset()
             if randomize:                                                          # :175-176: shuffle every column
                 A = np.array(host.toarray() if hasattr(host, "toarray") else host, dtype=np.float64)
                 A = np.apply_along_axis(rng.permutation, 0, A)
@@ -256,16 +275,26 @@ def factorize(mat, ranks=2, nrun=20, randomize=False, nsmpl=1, verbose=2, progre
                     if pairs_ok:
                         conav = conav + connectivity(st["eh"])                     # :218-219
                         disp = dispersion(conav / irun, ncol)                      # :220
+                    elif cons is not None:                                         # the same from the label tables
+                        whole = isinstance(eng, VBEngine) and eng.m == eng.m_global
+                        cons.add(eng if whole else cluster_ids(st["eh"]) + 1)
+                        disp = cons.dispersion()
                     if verbose >= 2:
                         say(f"Nsteps = {it} , likelihood = {lk0} , dispersion = {disp}\n")
                     if (irun == 1 or lk0 > rmax) and not np.isnan(lk0):            # :223
                         rmax, wmax, hmax = lk0, st["ew"], st["eh"]
+            except BaseException:
+                if cons is not None:
+                    cons.close()
+                raise
             finally:
                 for be in (batch_engines if batch_engines is not None else [eng]):
                     be.close()
                 if randomize:
                     Ms.close()
             coph = cophenet(conav / nrun, ncol, method=linkage) if pairs_ok else np.nan    # :230
+            if cons is not None and linkage in TABLE_LINKAGES:
+                coph = cons.cophenetic(linkage)
             if verbose >= 1:
                 say(f"Sample# {ismpl} : Max(likelihood) = {rmax} , dispersion = {disp} , cophenetic = {coph}")
             if wmax is None:
@@ -273,6 +302,8 @@ def factorize(mat, ranks=2, nrun=20, randomize=False, nsmpl=1, verbose=2, progre
             wsum = wmax if wsum is None else wsum + wmax                           # :233-245
             hsum = hmax if hsum is None else hsum + hmax
             rdat.append(rmax); ddat.append(disp); cdat.append(coph)
+        if cons is not None:
+            cons.close()
         out.basis.append(wsum / nsmpl)                                             # :247-248
         out.coeff.append(hsum / nsmpl)
         out.nsteps.append(steps)

@@ -502,6 +502,56 @@ int vbnmf_engine_cluster_ids(vbnmf_engine *e, int32_t *ids);
  * ids may be NULL. */
 int vbnmf_engine_cluster_changes(vbnmf_engine *e, int64_t *changed, int32_t *ids);
 
+/* ---------------------------------------------------------------------------------
+ * Consensus measures of factorize() (R/factorize.R:62-78, :218-230) from the label vectors of the runs, never from
+ * the O(m^2) pair vector.  With C_ij = the share of the R runs added so far in which cells i and j carry the same
+ * label, over pairs i < j:
+ *   sum C_ij = S1 / R,      S1 = sum_a sum_k pairs(n_k(a))
+ *   sum C_ij^2 = S2 / R^2,  S2 = sum_{a,b} sum_{k,l} pairs(n_kl(a, b))      (n_kl: contingency table of runs a, b)
+ *   dispersion = 1/m + 8 con / m^2,  con = sum (C_ij - 1/2)^2 = S2/R^2 - S1/R + npair/4
+ * The accumulator keeps the labels of every run on the device ([max_runs][m] uint8: 1..rank, 0 = no label) and the
+ * integer sums S1, S2; every add forms the tables of the new run against all stored runs on the device
+ * (csrc/consensus.h).  One handle serves one thread at a time.
+ * --------------------------------------------------------------------------------- */
+typedef struct vbnmf_consensus vbnmf_consensus;
+
+/* m >= 1 cells, 1 <= rank <= VBNMF_MAX_RANK, max_runs >= 1, on HIP device `device`. */
+int vbnmf_consensus_create(int64_t m, int32_t rank, int32_t max_runs, int32_t device, vbnmf_consensus **c);
+void vbnmf_consensus_destroy(vbnmf_consensus *c);
+/* Forget every run (the next nsmpl sample, the next rank). */
+int vbnmf_consensus_reset(vbnmf_consensus *c);
+/* Adds the arg-max labels of the engine's current coefficients (vbnmf_engine_cluster_ids' rule: ML h or E[H] of a VB
+ * state, first maximum, all-NaN column -> 0) as the next run, device to device on the engine's stream; the engine's own
+ * label state (vbnmf_engine_cluster_changes) is left alone.  VBNMF_ERR_STATE: partitioned engine, or no state loaded;
+ * VBNMF_ERR_BAD_ARG: m, rank or device differ from the handle's, or max_runs runs are held already. */
+int vbnmf_consensus_add_engine(vbnmf_consensus *c, vbnmf_engine *e);
+/* The same from m host labels (1-based, 0 = no label; anything outside 0..rank is VBNMF_ERR_BAD_ARG). */
+int vbnmf_consensus_add_labels(vbnmf_consensus *c, const int32_t *ids);
+/* Runs added, the integer sums, and whether any label so far was 0.  Any output may be NULL. */
+int vbnmf_consensus_sums(vbnmf_consensus *c, int32_t *runs, uint64_t *s1, uint64_t *s2, int32_t *unlabelled);
+/* dispersion(conav / runs, m) (R/factorize.R:62-67) from the integers, evaluated in double; NaN if any label was 0 (the
+ * reference's NA propagates through sum); 1/m for m = 1.  VBNMF_ERR_STATE before the first add. */
+int vbnmf_consensus_dispersion(vbnmf_consensus *c, double *disp);
+/* The labels of run `run` (0-based), m int32. */
+int vbnmf_consensus_labels(vbnmf_consensus *c, int32_t run, int32_t *ids);
+
+/* cophenet(conav / R, m, method) (R/factorize.R:69-78) in grouped form, host only (no GPU needed).  Cells with the same
+ * label in every run are at distance 0 from each other and at equal distance from everything else, so any linkage joins
+ * them first, at height 0; above that level the dendrogram is that of the G distinct label tuples ("groups") with the
+ * group sizes as weights and distance = Hamming distance of the tuples / R.  tuples: [G][R] labels, sizes: [G] cells per
+ * group (>= 1).  method: "average", "single" or "complete".  coph = Pearson correlation of distance and cophenetic
+ * distance over all m (m - 1) / 2 pairs of cells (within a group both are 0); NaN when either has no variance.
+ * Nearest-neighbour chain on a G x G matrix: O(G^2) work and memory.  Ties: among equal nearest neighbours of a group the
+ * chain takes the one it came from, else the lowest group number; a merged cluster keeps the lower number of its two parts. */
+int vbnmf_cophenetic_grouped(int64_t G, int32_t R, const uint8_t *tuples, const int64_t *sizes, const char *method, double *coph);
+/* The same for the runs an accumulator holds: downloads the label matrix, numbers the distinct tuples by their first
+ * cell, and calls the function above.  groups = G; if G > max_groups (<= 0: 4096, a 128 MB matrix) or a label was 0,
+ * coph = NaN. */
+int vbnmf_consensus_cophenetic(vbnmf_consensus *c, const char *method, int64_t max_groups, double *coph, int64_t *groups);
+/* Test hook: the grouped coefficient from real-valued group distances dist[G][G] (symmetric, zero diagonal) instead of
+ * label tuples, so the agglomeration can be checked on tie-free input. */
+int vbnmf_test_cophenetic_dist(int64_t G, const double *dist, const int64_t *sizes, const char *method, double *coph);
+
 /* vb_init(initializer = 'random') on the device (R/bayesian.R:111-115, 162-170): lw = ew ~ Gamma(shape aw, scale
  * bw/aw), lh = eh ~ Gamma(shape ah, scale bh/ah), dw = dh = 0, followed by what set_state does (a partitioned engine
  * needs the state exchange + state_finish).  Philox4x32-10 counters keyed by `seed`, Marsaglia-Tsang rejection; a
