@@ -143,6 +143,8 @@ SIGNATURES = {
     "vbnmf_engine_ml_step_finish": (ctypes.c_int, [_VP, c_double_p]),
     "vbnmf_group_ml_state_finish": (ctypes.c_int, [_VP]),
     "vbnmf_group_ml_run": (ctypes.c_int, [_VP, _I32, _D, _D, _I32, _D, c_int32_p, c_double_p, c_int32_p, c_double_p, _I64]),
+    "vbnmf_group_ml_run_connectivity": (ctypes.c_int, [_VP, _I32, _D, _D, _I32, _I32, c_int32_p, c_double_p, c_int32_p, c_double_p, _I64,
+                                                       c_int64_p, _I64]),
     "vbnmf_ml_update_dense": (ctypes.c_int, [_I64, _I64, _I32, c_double_p, c_double_p, c_double_p, _I32, _D, _D,
                                              c_double_p, c_double_p, c_double_p]),
     "vbnmf_ml_update_csc": (ctypes.c_int, [_I64, _I64, _I32, c_int32_p, c_int32_p, c_double_p, c_double_p, c_double_p,

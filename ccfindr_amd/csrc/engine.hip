@@ -262,7 +262,7 @@ struct vbnmf_engine {
     int ub = kUpdateBlocks;           // blocks of the update kernels (one per CU; VBNMF_UPDATE_BLOCKS for experiments)
     double *red = nullptr;            // [n*R | R+4]  (partitioned engines only use the first part)
     int64_t red_count = 0;
-    bool epart_in_red = false;        // partitioned engines: the evidence partials live behind red[red_count) (kEvSlots + 1 doubles:
+    bool epart_in_red = false;        // partitioned engines: the evidence partials live at red[red_ev_off) (kEvSlots + 1 doubles:
                                       // the second all-reduce of a device-driven step sends them as they are)
     double *red_g = nullptr;          // same shape: receive side of the all-reduce in a device-driven partitioned loop
     const double *red_in = nullptr;   // what the W update and the control kernel read: red (reduced in place by the
@@ -308,11 +308,19 @@ struct vbnmf_engine {
     int64_t sweep_launches = 0;
 };
 
-// doubles behind `red` / `red_g`: the reduce buffer proper (red_count, what the host-stepped exchange carries) and, for a
-// partitioned engine, the evidence slots of the device-driven loop's second all-reduce (kEvSlots partials + sum lgamma(x+1))
+// doubles behind `red` / `red_g`: the reduce buffer proper (red_count, what the host-stepped exchange carries), then
+//   [red_count, red_ev_off)  the (r+1) x (r+1) label table of the connectivity rule as doubles (mlnmf.h: MlConn): directly behind
+//                            the two doubles of the group ML step's second all-reduce, which carries it under that rule (on every
+//                            engine: a group of ONE partition that covers all cells is an unpartitioned engine, and takes that step)
+//   [red_ev_off, ...)        partitioned engines: the evidence slots of the device-driven VB loop's second all-reduce (kEvSlots
+//                            partials + sum lgamma(x+1))
+inline int64_t red_ev_off(const vbnmf_engine *e)
+{
+    return e->red_count + (int64_t)(e->r + 1) * (e->r + 1);
+}
 inline int64_t red_alloc_count(const vbnmf_engine *e)
 {
-    return e->red_count + ((e->partitioned && 2 * (int64_t)e->n_wg <= kEvSlots) ? kEvSlots + 1 : 0);
+    return red_ev_off(e) + ((e->partitioned && 2 * (int64_t)e->n_wg <= kEvSlots) ? kEvSlots + 1 : 0);
 }
 
 namespace {
@@ -1263,7 +1271,7 @@ int state_arrays(vbnmf_engine *e)
         (rc = dev_alloc(&e->bpW, bpn)) || (rc = dev_alloc(&e->bpH, bpn)) ||
         (rc = dev_alloc(&e->red, (size_t)red_alloc_count(e))) || (rc = dev_alloc(&e->d_out, 8)))
         return rc;
-    if (e->partitioned && 2 * (int64_t)e->n_wg <= kEvSlots) { e->epart = e->red + e->red_count; e->epart_in_red = true; }
+    if (e->partitioned && 2 * (int64_t)e->n_wg <= kEvSlots) { e->epart = e->red + red_ev_off(e); e->epart_in_red = true; }
     else if ((rc = dev_alloc(&e->epart, 2 * (size_t)e->n_wg))) return rc;
     hipError_t he;
     if ((he = hipHostMalloc((void **)&e->h_out, kHostOut * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent)) != hipSuccess ||
@@ -1280,7 +1288,7 @@ int state_arrays(vbnmf_engine *e)
         (he = hipMemsetAsync(e->red, 0, (size_t)red_alloc_count(e) * sizeof(double), e->stream)) != hipSuccess)
         return fail(VBNMF_ERR_HIP, "hipMemsetAsync failed: %s", hipGetErrorString(he));
     // (sum lgamma(x + 1) into its slot of the reduce buffer: BEHIND the fill above, on the same stream; e->lgx lives as long as the engine)
-    if (e->epart_in_red && (he = hipMemcpyAsync(e->red + e->red_count + kEvSlots, &e->lgx, sizeof(double), hipMemcpyHostToDevice, e->stream)) != hipSuccess)
+    if (e->epart_in_red && (he = hipMemcpyAsync(e->red + red_ev_off(e) + kEvSlots, &e->lgx, sizeof(double), hipMemcpyHostToDevice, e->stream)) != hipSuccess)
         return fail(VBNMF_ERR_HIP, "hipMemcpyAsync failed: %s", hipGetErrorString(he));
     // creation ends with the engine's buffers in their initial state whatever else the device is doing
     if ((he = hipStreamSynchronize(e->stream)) != hipSuccess) return fail(VBNMF_ERR_HIP, "engine setup failed: %s", hipGetErrorString(he));
@@ -1735,7 +1743,7 @@ int group_tables(vbnmf_comm *c)
         if (int rc = ensure_comm_resources(e)) return rc;
         // second exchange of a device-driven step: the evidence slots behind the reduce buffer (control step folded into
         // the next update), or the two doubles k_tail_data forms (VBNMF_NO_CONTROL_FOLD=1)
-        const size_t off = e->fold ? (size_t)e->red_count : (size_t)e->n * e->R + e->R + 2;
+        const size_t off = e->fold ? (size_t)red_ev_off(e) : (size_t)e->n * e->R + e->R + 2;
         sb[p] = e->red; rb[p] = e->red_g; ss[p] = e->red + off; rs[p] = e->red_g + off;
     }
     dev_free(c->d_send_big); dev_free(c->d_send_small); dev_free(c->d_recv_big); dev_free(c->d_recv_small);
@@ -1851,8 +1859,8 @@ int queue_vb_step(const LoopGroup &G, double fudge, bool hist, int max_it)
             f.bpW_prev = e->bpW; f.nbW = e->ub;
             std::swap(e->bpW, e->bpW_alt);
             f.tail_in = e->red_g + (size_t)e->n * e->R;
-            f.epart = e->red_g + e->red_count; f.nepart = kEvSlots;
-            f.lgx_in = e->red_g + e->red_count + kEvSlots;
+            f.epart = e->red_g + red_ev_off(e); f.nepart = kEvSlots;
+            f.lgx_in = e->red_g + red_ev_off(e) + kEvSlots;
             f.lgx = 0.0; f.n = (double)e->n; f.m_global = (double)e->m_global;
             f.history = hist && p == 0 ? e->h_hist_dev : nullptr; f.out_host = e->h_out_dev;
             f.do_control = t > 1 ? 1 : 0;
@@ -1916,7 +1924,7 @@ int queue_vb_step(const LoopGroup &G, double fudge, bool hist, int max_it)
     hipEvent_t evD = P > 1 ? next_event(L) : nullptr;
     const int64_t nsmall = fold ? kEvSlots + 1 : 2;
     if (c->kind == 0) {
-        const int64_t off = fold ? L->red_count : nbig;
+        const int64_t off = fold ? red_ev_off(L) : nbig;
         if (int rc = rccl_check(rccl_api().AllReduce(L->red + off, L->red_g + off, (size_t)nsmall, ncclDouble, ncclSum, c->nc, L->stream), "ncclAllReduce")) return rc;
     } else {
         for (int p = 1; p < P; p++) HIPCHECK(hipStreamWaitEvent(L->stream, evB[p], 0));
@@ -1933,7 +1941,7 @@ int queue_vb_step(const LoopGroup &G, double fudge, bool hist, int max_it)
             g.prev = e->ctl2 + (e->fold_step & 1); g.next = e->ctl2 + ((e->fold_step + 1) & 1);
             g.bpW_prev = e->bpW; g.nbW = e->ub;
             g.tail_in = e->red_g + (size_t)e->n * e->R;
-            g.epart = e->red_g + e->red_count; g.lgx_in = e->red_g + e->red_count + kEvSlots;
+            g.epart = e->red_g + red_ev_off(e); g.lgx_in = e->red_g + red_ev_off(e) + kEvSlots;
             g.history = hist && p == 0 ? e->h_hist_dev : nullptr; g.out_host = e->h_out_dev;
             if (int rc = launch_update(e, true, 0, 0, fudge, nullptr, &g)) return rc;
         }
@@ -2153,7 +2161,7 @@ MlConn conn_step(const vbnmf_engine *e, int t, bool changes)
     c.tab_zero = e->d_ctab + (size_t)((t + 1) & 3) * q2;
     c.tab_read = e->d_ctab + (size_t)((t - 1) & 3) * q2;
     c.changes = changes ? reinterpret_cast<int64_t *>(e->h_hist_dev + e->chg_off) : nullptr;
-    c.npair = e->m * (e->m - 1) / 2;
+    c.npair = e->m_global * (e->m_global - 1) / 2;                 // (pairs of ALL cells: a partition counts against the summed table)
     return c;
 }
 
@@ -2936,6 +2944,11 @@ int launch_ml_control(vbnmf_engine *e, bool hist, const MlConn &cn, bool reduced
 //                   -> main stream: k_ml_update(W <- the reduced statistics)  k_sweep1(cell side: h_new, w_new)  k_tail_data
 //                   -> main stream: all-reduce [sum x log(wh) | sum_{x>0}(-x log x + x)]           (two doubles)
 //                   -> k_ml_control on the reduced inputs: the same decision on every partition
+//   ... under criterion = 'connectivity' (a.conn): each H update also forms its cells' labels and adds them to its engine's own
+//                   table t & 3 (MlFold without a fold, as the unfolded unpartitioned path below); k_ml_tail_conn in
+//                   k_tail_data's place appends that table as doubles, the second all-reduce is [. | . | table (r+1)^2]
+//                   -- a length fixed by the call's arguments, never by device state -- and k_ml_control counts the changed
+//                   pairs on the SUM: pairs straddle partitions.  No third collective.
 // The W update needs the first exchange, so unlike the VB step nothing runs beside it; it still goes on the comm stream, as
 // queue_vb_step's, so that both loops order their collectives the same way.  The all-reduces are out of place (red -> red_g):
 // behind the stop every kernel returns at once, `red` keeps what the stopping step packed, and the exchanges queued past the
@@ -2985,11 +2998,19 @@ int queue_ml_step(const LoopGroup &G, const MlStepArgs &a)
     vbnmf_comm *c = G.comm;
     const int P = G.count;
     vbnmf_engine *L = G.e[0];                                  // leader: owner of the comm stream used by a local group
-    const int64_t nbig = L->n * L->R + L->R + 2, nsmall = 2;
+    const int64_t nconn = a.conn ? (int64_t)conn_table_count(L) : 0;
+    const int64_t nbig = L->n * L->R + L->R + 2, nsmall = 2 + nconn;
     hipEvent_t evA[64], evB[64];
     for (int p = 0; p < P; p++) {
         vbnmf_engine *e = G.e[p];
-        int rc = launch_ml_update(e, false, a.prior, a.ga, a.gb, eps);          // H: this partition's cells, colSums(w) replicated
+        int rc;                                                                 // H: this partition's cells, colSums(w) replicated
+        if (a.conn) {
+            MlFold f{};
+            f.cn = conn_step(e, ++e->fold_step, a.chg);                         // (no fold: only the rule's step counter here)
+            rc = launch_ml_update(e, false, a.prior, a.ga, a.gb, eps, &f);
+        } else {
+            rc = launch_ml_update(e, false, a.prior, a.ga, a.gb, eps);
+        }
         if (!rc) rc = launch_sweep1(e, true);
         if (!rc) rc = launch_ml_pack(e, &e->ctl->stop);
         if (rc) return rc;
@@ -3012,7 +3033,11 @@ int queue_ml_step(const LoopGroup &G, const MlStepArgs &a)
         int rc = launch_ml_update(e, true, a.prior, a.ga, a.gb, eps);           // W <- red_g (e->red_in), on every partition the same bits
         if (!rc) rc = launch_sweep1(e, false);
         if (rc) return rc;
-        hipLaunchKernelGGL(k_tail_data, dim3(1), dim3(1024), 0, e->stream, e->epart + e->n_wg, (int64_t)e->n_wg, e->xlx, e->red + nbig, &e->ctl->stop);
+        if (a.conn)
+            hipLaunchKernelGGL(k_ml_tail_conn, dim3(1), dim3(1024), 0, e->stream, e->epart + e->n_wg, (int64_t)e->n_wg, e->xlx,
+                               conn_step(e, e->fold_step, false).tab_add, (int)nconn, e->red + nbig, &e->ctl->stop);
+        else
+            hipLaunchKernelGGL(k_tail_data, dim3(1), dim3(1024), 0, e->stream, e->epart + e->n_wg, (int64_t)e->n_wg, e->xlx, e->red + nbig, &e->ctl->stop);
         HIPCHECK(hipGetLastError());
         if (p > 0) {                                           // (only where another stream waits on it)
             evB[p] = next_event(e);
@@ -3025,21 +3050,23 @@ int queue_ml_step(const LoopGroup &G, const MlStepArgs &a)
         if (int rc = rccl_check(rccl_api().AllReduce(L->red + nbig, L->red_g + nbig, (size_t)nsmall, ncclDouble, ncclSum, c->nc, L->stream), "ncclAllReduce")) return rc;
     } else {
         for (int p = 1; p < P; p++) HIPCHECK(hipStreamWaitEvent(L->stream, evB[p], 0));
-        hipLaunchKernelGGL(k_group_sum_at, dim3(1), dim3(256), 0, L->stream, c->d_send_big, c->d_recv_big, P, nbig, nsmall);
+        hipLaunchKernelGGL(k_group_sum_at, dim3((unsigned)((nsmall + 255) / 256)), dim3(256), 0, L->stream, c->d_send_big, c->d_recv_big, P, nbig, nsmall);
         HIPCHECK(hipGetLastError());
     }
     if (evD) HIPCHECK(hipEventRecord(evD, L->stream));
     for (int p = 0; p < P; p++) {
         vbnmf_engine *e = G.e[p];
         if (evD && e->stream != L->stream) HIPCHECK(hipStreamWaitEvent(e->stream, evD, 0));
-        if (int rc = launch_ml_control(e, a.hist && p == 0, MlConn{}, true)) return rc;
+        // (the rule's control step reads the summed table behind the exchange's two doubles, not cn.tab_read)
+        if (int rc = launch_ml_control(e, a.hist && p == 0, a.conn ? conn_step(e, e->fold_step + 1, a.chg) : MlConn{}, true)) return rc;
     }
     return VBNMF_OK;
 }
 
 // The device-driven ML loop under either stopping rule (ncnn_step 0: the likelihood's, with tol) of one unpartitioned engine, or
-// -- the likelihood's rule only -- of the partitions of one factorisation: a local group, or this process's engine with its
-// RCCL communicator.
+// of the partitions of one factorisation: a local group, or this process's engine with its RCCL communicator.  Under the
+// connectivity rule every partition keeps labels and tables of its own cells and writes the per-step counts -- the same on
+// all of them -- to its own history block; the caller's come from partition 0.
 int ml_run_group(const LoopGroup &G, int32_t prior, double gamma_a, double gamma_b, int32_t max_it, double tol, int32_t ncnn_step,
                  int32_t *it_out, double *lk_out, int32_t *reason_out, double *history, int64_t history_rows, int64_t *changes)
 {
@@ -3052,14 +3079,18 @@ int ml_run_group(const LoopGroup &G, int32_t prior, double gamma_a, double gamma
     }
     if (int rc = use_device(e)) return rc;
     if (history || changes) { if (int rc = ensure_history(e, (size_t)max_it * (changes ? 2 : 1))) return rc; }
-    e->chg_off = (size_t)max_it;
-    if (conn) { if (int rc = conn_alloc(e)) return rc; }
+    for (int p = 0; p < G.count; p++) {
+        vbnmf_engine *x = G.e[p];
+        if (changes && p > 0) { if (int rc = ensure_history(x, (size_t)max_it * 2)) return rc; }
+        x->chg_off = (size_t)max_it;
+        if (conn) { if (int rc = conn_alloc(x)) return rc; }
+    }
 
     const MlStepArgs a{prior, gamma_a, gamma_b, history != nullptr, changes != nullptr, conn, max_it};
     RunScope S{G.e, G.count};
     S.plain_ctl = G.comm != nullptr;                               // partitioned: the control step is a kernel of its own, on e->ctl
     int rc = S.begin([&](int) { return conn ? ml_conn_ctl(max_it, ncnn_step) : ml_ctl(tol, max_it); });
-    if (!rc && conn) rc = conn_zero(e);
+    for (int p = 0; p < G.count && conn && !rc; p++) rc = conn_zero(G.e[p]);
     if (G.comm) for (int p = 0; p < G.count; p++) G.e[p]->red_in = G.e[p]->red_g;      // what the W updates read: the receive side
     if (!rc) rc = drive_loop(G.e, 1, true, max_it, !G.comm && e->fold, [&](int) { return queue_ml_step(G, a); });
     rc = S.end(rc);
@@ -3070,7 +3101,10 @@ int ml_run_group(const LoopGroup &G, int32_t prior, double gamma_a, double gamma
             return fail(VBNMF_ERR_STATE, "partition %d ended the loop at step %d (reason %d), partition 0 at step %d (reason %d)", p,
                         (int)G.e[p]->h_out[5], (int)G.e[p]->h_out[6], (int)e->h_out[5], (int)e->h_out[6]);
     read_out(G.e, 1, it_out, nullptr, lk_out, reason_out, nullptr, history, history_rows, 1);
-    if (conn) conn_finish(G.e, 1, changes, max_it);
+    if (conn) {
+        conn_finish(G.e, 1, changes, max_it);
+        conn_finish(G.e + 1, G.count - 1, nullptr, 0);             // (the other partitions: their labels of the last step)
+    }
     return VBNMF_OK;
 }
 
@@ -3136,10 +3170,32 @@ int vbnmf_engine_ml_run_connectivity(vbnmf_engine *e, int32_t prior, double gamm
     if (max_it < 1 || ncnn_step < 1) return fail(VBNMF_ERR_BAD_ARG, "max_it and ncnn_step must be >= 1");
     if (history && history_rows < max_it) return fail(VBNMF_ERR_BAD_ARG, "history needs max_it doubles");
     if (changes && changes_rows < max_it) return fail(VBNMF_ERR_BAD_ARG, "changes needs max_it counts");
-    if (e->partitioned)
-        return fail(VBNMF_ERR_STATE, "criterion = 'connectivity' is not available on a partitioned engine (the label tables are not all-reduced); "
-                                     "run the host rule on ml_get_state, or the likelihood criterion");
     LoopGroup G{&e, 1, nullptr};
+    if (e->partitioned) {                                          // (as vbnmf_engine_ml_run)
+        if (!e->comm || e->comm->kind != 0)
+            return fail(VBNMF_ERR_STATE, "criterion = 'connectivity' on a partitioned engine needs an RCCL communicator (vbnmf_engine_attach_comm), "
+                                         "or vbnmf_group_ml_run_connectivity for a local group");
+        if (int rc = use_device(e)) return rc;
+        if (int rc = ensure_comm_resources(e)) return rc;
+        G.comm = e->comm;
+    }
+    return ml_run_group(G, prior, gamma_a, gamma_b, max_it, 0.0, ncnn_step, it_out, lk_out, reason_out, history, history_rows, changes);
+}
+
+// Local group: the same rule (R/factorize.R:198-208) for the partitions of one factorisation.  A changed pair of cells may lie
+// in two partitions, so the partitions' (r+1) x (r+1) label tables are summed -- inside the step's second exchange -- before
+// nchange is formed; every partition then takes the same decision.  changes: from partition 0; changes[0] = the pairs of ALL cells.
+int vbnmf_group_ml_run_connectivity(vbnmf_comm *c, int32_t prior, double gamma_a, double gamma_b, int32_t max_it, int32_t ncnn_step,
+                                    int32_t *it_out, double *lk_out, int32_t *reason_out, double *history, int64_t history_rows,
+                                    int64_t *changes, int64_t changes_rows)
+{
+    if (max_it < 1 || ncnn_step < 1) return fail(VBNMF_ERR_BAD_ARG, "max_it and ncnn_step must be >= 1");      // (before the handle is read)
+    if (history && history_rows < max_it) return fail(VBNMF_ERR_BAD_ARG, "history needs max_it doubles");
+    if (changes && changes_rows < max_it) return fail(VBNMF_ERR_BAD_ARG, "changes needs max_it counts");
+    LoopGroup G{};
+    if (int rc = group_members(c, G)) return rc;
+    if (int rc = use_device(G.e[0])) return rc;
+    if (int rc = group_tables(c)) return rc;
     return ml_run_group(G, prior, gamma_a, gamma_b, max_it, 0.0, ncnn_step, it_out, lk_out, reason_out, history, history_rows, changes);
 }
 

@@ -13,6 +13,7 @@
 // Cells partitioned over several engines (W replicated, partition p holding its columns of h): the same kernels around two exchanges,
 //   k_ml_update(H) -> k_sweep1(gene) -> k_pack_tail -> ALL-REDUCE [statistics n*R | rowSums(h_new)] -> k_ml_update(W, dense form)
 //   -> k_sweep1(cell) -> k_tail_data -> ALL-REDUCE [sum x log(wh) | constant] -> k_ml_control / k_ml_final on the reduced values
+// (criterion = 'connectivity': k_ml_tail_conn in k_tail_data's place, and the second all-reduce is [. | . | label table (r+1)^2])
 // (engine.hip: queue_ml_step; host-stepped: vbnmf_engine_ml_step_local / ml_step_finish).
 #pragma once
 #include "kernels.h"
@@ -50,17 +51,22 @@ struct MlConn {
 
 // pairs(rows) + pairs(cols) - 2 pairs(cells) of an (r+1) x (r+1) contingency table by the whole block, into *s_out (LDS),
 // complete behind the closing barrier.  64-bit integers throughout; the threads' shares wrap, their total is the count.
-__device__ __forceinline__ void block_label_changes(const unsigned long long *__restrict__ tab, int r, unsigned long long *s_out, int nthreads)
+// T = double: the table summed over the partitions of a cell-partitioned engine (k_ml_tail_conn below) -- every entry a cell
+// count <= m_global < 2^53, so its double and the all-reduce's sum of such doubles are exact in any order, and the conversion
+// back at the load gives every partition the integers of the whole matrix.
+template <class T>
+__device__ __forceinline__ void block_label_changes(const T *__restrict__ tab, int r, unsigned long long *s_out, int nthreads)
 {
     const int t = threadIdx.x, q = r + 1;
     if (t == 0) *s_out = 0ull;
     __syncthreads();
     auto pairs = [](unsigned long long c) { return c * (c - (c > 0 ? 1ull : 0ull)) / 2ull; };
+    auto at = [&](size_t i) { return (unsigned long long)tab[i]; };
     unsigned long long acc = 0ull;
-    for (int i = t; i < q * q; i += nthreads) acc -= 2ull * pairs(tab[i]);
+    for (int i = t; i < q * q; i += nthreads) acc -= 2ull * pairs(at(i));
     for (int a = t; a < q; a += nthreads) {
         unsigned long long rs = 0ull, cs = 0ull;
-        for (int b = 0; b < q; b++) { rs += tab[(size_t)a * q + b]; cs += tab[(size_t)b * q + a]; }
+        for (int b = 0; b < q; b++) { rs += at((size_t)a * q + b); cs += at((size_t)b * q + a); }
         acc += pairs(rs) + pairs(cs);
     }
     if (acc) atomicAdd(s_out, acc);
@@ -368,6 +374,8 @@ __global__ __launch_bounds__(1024) void k_ml_control(const double *__restrict__ 
     // Cell-partitioned engines (tail != null; as k_control, kernels.h): tail = rowSums(h_new) of ALL cells, the reduced tail of
     // the step's first all-reduce; small = [sum x log(wh) | sum_{x>0}(-x log x + x)] summed over the partitions by the second;
     // colSums(w_new) from bpW, replicated; m is the GLOBAL cell count.  Every partition forms the same decision from the same bits.
+    // criterion = 'connectivity' there: the same exchange carries the partitions' label tables, small + 2 = their sum as
+    // (r+1)^2 doubles (k_ml_tail_conn); a changed pair may straddle two partitions, so only the summed table counts them.
     __shared__ double sW[R + 2], sH[R + 2];
     __shared__ double sm[1024];
     __shared__ unsigned long long s_nch;
@@ -381,7 +389,10 @@ __global__ __launch_bounds__(1024) void k_ml_control(const double *__restrict__ 
     bp_colsums2(bpW, bpH, nb, R + 2, sW, sH, 1024);
     }
     if (stopped) return;
-    if (cn.ids_out) block_label_changes(cn.tab_read, r, &s_nch, 1024);   // criterion = 'connectivity': the table this step's H update filled
+    if (cn.ids_out) {                            // criterion = 'connectivity': the table this step's H update filled
+        if (tail) block_label_changes(small + 2, r, &s_nch, 1024);
+        else block_label_changes(cn.tab_read, r, &s_nch, 1024);
+    }
     double data = block_sum(part, sm);           // (its barriers also publish sW / sH)
     if (tail) { data = small[0]; xlx = small[1]; }
     if (threadIdx.x != 0) return;
@@ -408,6 +419,20 @@ __global__ __launch_bounds__(1024) void k_ml_control(const double *__restrict__ 
     __threadfence_system();
     reinterpret_cast<volatile double *>(out_host)[6] = (double)reason;
     reinterpret_cast<volatile double *>(out_host)[7] = (double)it;
+}
+
+// The second exchange of a cell-partitioned step under criterion = 'connectivity' (one block; k_tail_data's two doubles, kernels.h,
+// and behind them the table this step's H update filled, as doubles): out = [sum x log(wh) | sum_{x>0}(-x log x + x) | (r+1)^2
+// counts] of THIS partition.  Steps queued past the stop leave `out` as the stopping step wrote it.
+__global__ __launch_bounds__(1024) void k_ml_tail_conn(const double *__restrict__ epart, int64_t nepart, double xlx,
+                                                       const unsigned long long *__restrict__ tab, int q2,
+                                                       double *__restrict__ out, const int32_t *__restrict__ stop)
+{
+    __shared__ double sm[1024];
+    if (stop && *stop) return;
+    for (int i = threadIdx.x; i < q2; i += 1024) out[2 + i] = (double)tab[i];
+    const double data = block_vec_sum(epart, nepart, sm);
+    if (threadIdx.x == 0) { out[0] = data; out[1] = xlx; }
 }
 
 // which.max(h[, j])[1] for every cell j (reference R/factorize.R:55-56, R/utils.R:906): 1-based index of the first

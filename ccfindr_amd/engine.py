@@ -367,7 +367,9 @@ class VBEngine:
         """factorize()'s inner loop on the resident pair, driven by the device -> ``{"it", "lk", "reason"[, "history"]}``
         (reason 2 converged, 4 Itmax).  ``criterion="likelihood"``: the likelihood's rule with ``Tol`` (R/factorize.R:211-213);
         ``"connectivity"``: stop once the cells' labels have not moved for ``ncnn_step`` steps (:198-208), ``Tol`` unused;
-        ``changes=True`` adds ``"changes"``, the count of changed pairs of every step (the first is m (m - 1) / 2)."""
+        ``changes=True`` adds ``"changes"``, the count of changed pairs of every step (the first is m (m - 1) / 2).
+        A partitioned engine with an RCCL communicator runs either rule for the whole matrix, every process making the same
+        call (the pairs are then those of all m_global cells); a local group's go through ``Communicator``."""
         it, reason, lk = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_double()
         hist = np.empty(int(Itmax)) if history else None
         if criterion == "connectivity":
@@ -678,6 +680,24 @@ class Communicator:
         out = {"it": it.value, "lk": lk.value, "reason": reason.value}
         if history:
             out["history"] = hist[:it.value].copy()
+        return out
+
+    def ml_run_connectivity(self, Itmax=10000, ncnn_step=40, prior=False, gamma_a=1.0, gamma_b=1.0, history=False, changes=False):
+        """``VBEngine.ml_run(criterion="connectivity")`` for the whole local group (same result dictionary; reference
+        R/factorize.R:198-208).  The partitions' label tables are summed inside the step's second exchange, so ``changes``
+        counts the pairs of ALL cells: its first entry is m_global (m_global - 1) / 2."""
+        it, reason, lk = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_double()
+        hist = np.empty(int(Itmax)) if history else None
+        chg = np.empty(int(Itmax), dtype=np.int64) if changes else None
+        N.check(self._lib.vbnmf_group_ml_run_connectivity(
+            self._h, int(bool(prior)), float(gamma_a), float(gamma_b), int(Itmax), int(ncnn_step), ctypes.byref(it), ctypes.byref(lk),
+            ctypes.byref(reason), N.dptr(hist), int(Itmax) if history else 0,
+            chg.ctypes.data_as(N.c_int64_p) if changes else None, int(Itmax) if changes else 0))
+        out = {"it": it.value, "lk": lk.value, "reason": reason.value}
+        if history:
+            out["history"] = hist[:it.value].copy()
+        if changes:
+            out["changes"] = chg[:it.value].copy()
         return out
 
     def close(self):

@@ -135,7 +135,8 @@ def factorize(mat, ranks=2, nrun=20, randomize=False, nsmpl=1, verbose=2, progre
     Generator behind ``init`` and the ``randomize`` permutations.  ``engine_factory(count_matrix, rank)`` replaces
     the engine constructor (the CPU tests of this loop pass a stand-in).  ``device_loop``: with ``verbose < 3`` the inner
     loop (:194-213) runs on the device under either criterion (``vbnmf_engine_ml_run``,
-    ``vbnmf_engine_ml_run_connectivity``) instead of one call per iteration.  ``batch``: how many of a rank's ``nrun`` restarts
+    ``vbnmf_engine_ml_run_connectivity``) instead of one call per iteration -- also over the partitions of a
+    ``CellPartitionedEngine`` (``engine_factory``), whose connectivity loop is its ``ml_run_connectivity``.  ``batch``: how many of a rank's ``nrun`` restarts
     (:181) are stepped by ONE launch (``engine.run_batch_ml``; 1: one at a time; None: up to 16 where the device loop runs,
     the rank is at most 16 and the matrix holds up to 2e7 stored entries) -- on a small matrix one loop cannot fill the GPU.
     Under ``criterion='connectivity'`` restarts are batched only when ``batch > 1`` is passed: a batch's narrower grids
@@ -244,6 +245,9 @@ def factorize(mat, ranks=2, nrun=20, randomize=False, nsmpl=1, verbose=2, progre
                     zstep, lkold, cid0, lk0, it = 0, -np.inf, None, np.nan, 0
                     on_device = device_loop and verbose < 3 and hasattr(eng, "ml_run")
                     if batch_engines is not None:
+                        it, lk0 = run["it"], run["lk"]
+                    elif on_device and criterion == "connectivity" and hasattr(eng, "ml_run_connectivity"):
+                        run = eng.ml_run_connectivity(Itmax=Itmax, ncnn_step=ncnn_step)    # (a cell-partitioned engine's)
                         it, lk0 = run["it"], run["lk"]
                     elif on_device:                                                # the loop below, driven by the device
                         run = eng.ml_run(Itmax=Itmax, Tol=Tol, **rule)

@@ -492,6 +492,16 @@ def vb_factorize_sharded(mat, ranks=2, nrun=1, verbose=0, initializer="random", 
 # ---------------------------------------------------------------------------------------
 # cell-partitioned single factorisation
 # ---------------------------------------------------------------------------------------
+def _which_max(h):
+    """k_argmax's rules on a host r x m matrix: 1-based index of the first maximum, NaN never wins, 0 for a column of NaNs."""
+    h = np.asarray(h, dtype=np.float64)
+    best, bv = np.zeros(h.shape[1], dtype=np.int32), np.zeros(h.shape[1])
+    for k in range(h.shape[0]):
+        win = ~np.isnan(h[k]) & ((best == 0) | (h[k] > bv))
+        best[win], bv[win] = k + 1, h[k][win]
+    return best
+
+
 def cell_partition(m, world):
     """Contiguous, near-equal column blocks: [(begin, end)] * world."""
     return [(m * k // world, m * (k + 1) // world) for k in range(world)]
@@ -631,19 +641,47 @@ class CellPartitionedEngine:
 
     def ml_run(self, Itmax=10000, Tol=1e-5, prior=False, gamma_a=1.0, gamma_b=1.0, history=False, criterion="likelihood", **kw):
         """The device-driven loop of ``VBEngine.ml_run`` across the partitions under the likelihood criterion (native
-        communicator, or a single process).  ``criterion='connectivity'`` is refused: the label tables of the partitions
-        are not all-reduced -- pass ``device_loop=False`` to ``factorize`` and the host rule reads ``ml_get_state``."""
+        communicator, or a single process).  ``criterion='connectivity'`` is refused here: that rule's loop is
+        ``ml_run_connectivity``, which ``factorize`` calls by itself."""
         if criterion == "connectivity":
-            raise ValueError("criterion='connectivity' has no device-driven loop on a cell-partitioned engine; "
-                             "use the host rule (factorize(..., device_loop=False))")
+            raise ValueError("criterion='connectivity' is not ml_run's on a cell-partitioned engine: call ml_run_connectivity "
+                             "(factorize() does)")
         if criterion != "likelihood":
             raise ValueError("Unknown stopping criterion.")
         if self._partitioned and not self.native:
             raise RuntimeError("the device-driven loop of a partitioned run needs the native (RCCL) communicator")
         return self.engine.ml_run(Itmax=Itmax, Tol=Tol, prior=prior, gamma_a=gamma_a, gamma_b=gamma_b, history=history, **kw)
 
+    def ml_run_connectivity(self, Itmax=10000, ncnn_step=40, prior=False, gamma_a=1.0, gamma_b=1.0, history=False, changes=False):
+        """The same loop under ``criterion='connectivity'`` (reference R/factorize.R:198-208; native communicator, or a single
+        process): stop once no pair of cells -- of ALL cells, whichever partitions hold them -- has changed for ``ncnn_step``
+        steps.  Every process calls it with the same arguments and gets the same result, ``VBEngine.ml_run``'s dictionary."""
+        if self._partitioned and not self.native:
+            raise RuntimeError("the device-driven loop of a partitioned run needs the native (RCCL) communicator")
+        return self.engine.ml_run(Itmax=Itmax, prior=prior, gamma_a=gamma_a, gamma_b=gamma_b, history=history,
+                                  criterion="connectivity", ncnn_step=ncnn_step, changes=changes)
+
     def ml_likelihood(self):
         return self.engine.ml_likelihood()
+
+    def cluster_ids(self):
+        """1-based arg-max component (``which.max(h[, j])``) of ALL ``m_global`` cells, on every process: each forms the labels of
+        its own block -- the engine's ``cluster_ids`` where it has one -- and one int32 ``all_gather`` joins them."""
+        if hasattr(self.engine, "cluster_ids"):
+            ids = np.asarray(self.engine.cluster_ids(), dtype=np.int32)
+        else:
+            ids = _which_max(self.engine.ml_get_state(("eh",))["eh"])
+        if self.world == 1:
+            return ids
+        torch, dist = self._torch, self._dist
+        counts = [e - b for b, e in cell_partition(self.m_global, self.world)]
+        on_gpu = dist.get_backend(self.group) == "nccl"
+        dev = torch.device("cuda", self.engine.device) if on_gpu else torch.device("cpu")
+        mine = torch.zeros(max(counts), dtype=torch.int32, device=dev)
+        mine[:ids.shape[0]] = torch.from_numpy(np.ascontiguousarray(ids)).to(dev)
+        parts = [torch.empty_like(mine) for _ in range(self.world)]
+        dist.all_gather(parts, mine, group=self.group)
+        return np.concatenate([p[:c].cpu().numpy() for p, c in zip(parts, counts)])
 
     def ml_get_state(self, names=("ew", "eh")):
         """``ew`` replicated, ``eh`` all-gathered to the full r x m matrix, as ``get_state``."""

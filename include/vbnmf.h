@@ -416,7 +416,10 @@ int vbnmf_batch_ml_run(vbnmf_engine **engines, int32_t count, int32_t prior, dou
  * reported and written to the history every step; it stops nothing (a NaN likelihood included, as in the reference).
  * changes (or NULL): the nchange of every step run, changes_rows >= max_it; changes[0] = npair.  Afterwards the labels of
  * the last step are the engine's previous labels: vbnmf_engine_cluster_changes right behind the run reports 0.
- * VBNMF_ERR_BAD_ARG: NULL handle, max_it < 1, ncnn_step < 1; VBNMF_ERR_STATE: before ml_set_state, partitioned engine. */
+ * A partitioned engine with an RCCL communicator attached runs the rule for the whole matrix (below: "ML-NMF with the cells
+ * partitioned"); changes[0] is then m_global (m_global - 1) / 2.
+ * VBNMF_ERR_BAD_ARG: NULL handle, max_it < 1, ncnn_step < 1; VBNMF_ERR_STATE: before ml_set_state, a partitioned engine
+ * without an RCCL communicator (a local group's member: vbnmf_group_ml_run_connectivity). */
 int vbnmf_engine_ml_run_connectivity(vbnmf_engine *e, int32_t prior, double gamma_a, double gamma_b, int32_t max_it,
                                      int32_t ncnn_step, int32_t *it, double *lk, int32_t *reason, double *history,
                                      int64_t history_rows, int64_t *changes, int64_t changes_rows);
@@ -466,8 +469,16 @@ int vbnmf_engine_ml_get_state(vbnmf_engine *e, double *w, double *h);
  * the exchange behind ml_set_state plus ml_state_finish on every member.  Sums run per partition first, then across the
  * partitions in partition order: results agree with the single engine to rounding, not bit for bit.
  * vbnmf_engine_ml_get_state / ml_likelihood answer for the partition (its own columns of h; the global likelihood).
- * criterion = 'connectivity' (vbnmf_engine_ml_run_connectivity, :198-208) stays VBNMF_ERR_STATE on a partitioned engine:
- * the contingency tables of the labels would need an all-reduce of their own.
+ * criterion = 'connectivity' (:198-208): vbnmf_engine_ml_run_connectivity on an engine with an RCCL communicator attached,
+ * vbnmf_group_ml_run_connectivity for a local group.  The rule counts changed PAIRS of cells and a pair may lie in two
+ * partitions, so each partition's H update counts its own cells into its own (r+1) x (r+1) table of [previous label][new
+ * label], and exchange 2 of the step grows to
+ *   exchange 2 : [ sum x log(w h) | sum_{x>0}(-x log x + x) | the table as (r+1)^2 doubles ]
+ * -- entries are cell counts <= m_global < 2^53, so the doubles and their sum are exact in any order and every partition forms
+ * nchange = pairs(rows) + pairs(cols) - 2 pairs(cells), zstep and the stop from the same integers.  No third exchange; under
+ * the likelihood rule both exchanges keep their lengths.  A local group's member called alone is VBNMF_ERR_STATE.
+ * Afterwards every partition's previous labels are those of its own cells at the last step (vbnmf_engine_cluster_ids);
+ * vbnmf_engine_cluster_changes on a partition still counts the pairs within that partition only.
  * --------------------------------------------------------------------------------- */
 /* Where the TAIL of the reduce buffer starts and how many doubles it holds (n*R, R + 4; either pointer may be NULL). */
 int vbnmf_engine_reduce_tail(const vbnmf_engine *e, int64_t *offset, int64_t *count);
@@ -477,6 +488,12 @@ int vbnmf_engine_ml_step_finish(vbnmf_engine *e, double *lk);
 int vbnmf_group_ml_state_finish(vbnmf_comm *c);
 int vbnmf_group_ml_run(vbnmf_comm *c, int32_t prior, double gamma_a, double gamma_b, int32_t max_it, double tol,
                        int32_t *it, double *lk, int32_t *reason, double *history, int64_t history_rows);
+/* vbnmf_engine_ml_run_connectivity (R/factorize.R:198-208) for the partitions of a local group: arguments and results as
+ * there, history and changes from partition 0, changes[0] = m_global (m_global - 1) / 2.
+ * VBNMF_ERR_BAD_ARG: max_it < 1, ncnn_step < 1, NULL communicator; VBNMF_ERR_STATE: not a local group, members missing. */
+int vbnmf_group_ml_run_connectivity(vbnmf_comm *c, int32_t prior, double gamma_a, double gamma_b, int32_t max_it,
+                                    int32_t ncnn_step, int32_t *it, double *lk, int32_t *reason, double *history,
+                                    int64_t history_rows, int64_t *changes, int64_t changes_rows);
 /* Stateless forms of the same step: nmf_updateR(x, w, h, n, m, r, prior, gamma.a, gamma.b)
  * followed by likelihood(x, w, h) (R/factorize.R:2-27, :40-49); throw-away engine on device 0 (VBNMF_DEVICE overrides). */
 int vbnmf_ml_update_dense(int64_t n, int64_t m, int32_t r, const double *X,
