@@ -51,6 +51,7 @@ class LayoutView(ctypes.Structure):
         ("inv_ptr", c_int32_p), ("inv_task", c_uint32_p),
         ("packed", c_uint32_p), ("wide_idx", c_uint32_p), ("wide_val", c_double_p),
         ("cell_perm", c_int32_p),
+        ("n_rows", ctypes.c_int64), ("row_ptr", c_int32_p), ("row_task", c_uint32_p), ("merge", ctypes.c_int32),
     ]
 
 

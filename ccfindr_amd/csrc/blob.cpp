@@ -24,9 +24,9 @@ using namespace vbnmf;
 namespace {
 
 constexpr int64_t kBlobMagic = 0x56424E4D464C5930LL;      // "VBNMFLY0"
-constexpr int64_t kBlobVersion = 2;
-constexpr int kBlobHeaderWords = 48;
-constexpr int kBlobArrays = 15;
+constexpr int64_t kBlobVersion = 3;                       // 3: the row index (row_ptr / row_task, n_rows, merge)
+constexpr int kBlobHeaderWords = 56;
+constexpr int kBlobArrays = 17;
 
 // THE table of the blob's arrays, in blob order: whoever writes, sizes or reads a blob walks it through here.  The three
 // ExtVec members are the big ones (the entry stream), which may live inside a mapping instead of the library's memory.
@@ -37,6 +37,7 @@ void for_each_blob_array(LayoutT &L, F &&f)
     f(L.seg_block); f(L.wg_seg0); f(L.seg_ptr); f(L.inv_ptr); f(L.inv_task);
     f(L.packed); f(L.wide_idx); f(L.wide_val);
     f(L.cell_perm);
+    f(L.row_ptr); f(L.row_task);
 }
 
 struct BlobArray { const void *src; int64_t bytes; int64_t off; };
@@ -81,6 +82,7 @@ void write_blob_header(int64_t *h, const Layout &L, const LayoutParams &lp, cons
     h[15] = L.n_segs; h[16] = L.nnz;
     h[17] = lp.block_width; h[18] = lp.block_cap; h[19] = lp.max_len; h[20] = lp.n_wg; h[21] = lp.row_slots;
     h[22] = X->M.n; h[23] = X->M.m; h[24] = X->M.nnz;
+    h[25] = L.n_rows; h[26] = L.merge ? 1 : 0; h[27] = lp.merge;
     for (int q = 0; q < kBlobArrays; q++) h[32 + q] = a[q].bytes;
 }
 
@@ -187,6 +189,7 @@ int validate_layout(const Layout &L, const vbnmf_matrix *X)
                     (int64_t)L.block_start.size() == (int64_t)L.n_blocks + 1 && (int64_t)L.seg_block.size() == L.n_segs &&
                     (int64_t)L.wg_seg0.size() == (int64_t)L.n_wg + 1 && (int64_t)L.seg_ptr.size() == L.n_segs + 1 &&
                     (int64_t)L.inv_ptr.size() == L.n_major + 1 && (int64_t)L.inv_task.size() == L.n_tasks &&
+                    (int64_t)L.row_ptr.size() == L.n_major + 1 && (int64_t)L.row_task.size() == L.n_rows && L.n_rows <= L.n_tasks &&
                     (L.wide ? ((int64_t)L.wide_idx.size() == L.n_slots && (int64_t)L.wide_val.size() == L.n_slots)
                              : (int64_t)L.packed.size() == L.n_slots) &&
                     L.n_major == (L.side == 0 ? X->M.n : X->M.m) && L.n_minor == (L.side == 0 ? X->M.m : X->M.n) &&
@@ -218,6 +221,10 @@ int validate_layout(const Layout &L, const vbnmf_matrix *X)
     if (!bad && (L.inv_ptr[0] != 0 || L.inv_ptr[L.n_major] != L.n_tasks)) bad = "inv_ptr";
     for (int64_t q = 0; !bad && q < L.n_major; q++) if (L.inv_ptr[q + 1] < L.inv_ptr[q]) bad = "inv_ptr";
     for (int64_t q = 0; !bad && q < L.n_tasks; q++) if ((int64_t)L.inv_task[q] >= nsl * kLanes) bad = "inv_task";
+    if (!bad && (L.row_ptr[0] != 0 || L.row_ptr[L.n_major] != L.n_rows)) bad = "row_ptr";
+    for (int64_t q = 0; !bad && q < L.n_major; q++) if (L.row_ptr[q + 1] < L.row_ptr[q]) bad = "row_ptr";
+    for (int64_t q = 0; !bad && q < L.n_rows; q++) if ((int64_t)L.row_task[q] >= nsl * kLanes) bad = "row_task";
+    if (!bad && !L.merge && (L.row_ptr != L.inv_ptr || L.row_task != L.inv_task)) bad = "row_task";
     if (bad) return fail(VBNMF_ERR_BAD_ARG, "layout blob: the %s array is inconsistent (another build, or a damaged file?)", bad);
     return VBNMF_OK;
 }
@@ -252,8 +259,10 @@ int load_blob(const vbnmf_matrix *X, const void *buf, int64_t bytes, std::shared
         L->side = (int)h[3]; L->wide = h[4] != 0; L->n_major = h[5]; L->n_minor = h[6]; L->block_width = (int32_t)h[7];
         L->n_blocks = (int32_t)h[8]; L->max_len = (int32_t)h[9]; L->n_wg = (int32_t)h[10]; L->row_slots = (int32_t)h[11];
         L->n_tasks = h[12]; L->n_slices = h[13]; L->n_slots = h[14]; L->n_segs = h[15]; L->nnz = h[16];
+        L->n_rows = h[25]; L->merge = h[26] != 0;
         LayoutParams lp;
         lp.block_width = (int32_t)h[17]; lp.block_cap = (int32_t)h[18]; lp.max_len = (int32_t)h[19]; lp.n_wg = (int32_t)h[20]; lp.row_slots = (int32_t)h[21];
+        lp.merge = (int32_t)h[27];
         int q = 0;
         int64_t o = kBlobHeaderWords * 8;
         int rc = VBNMF_OK;

@@ -148,7 +148,15 @@ struct Layout {
     std::vector<int32_t> wg_seg0;        // n_wg + 1
     std::vector<int32_t> seg_ptr;        // n_segs + 1 : first slice of each segment
     std::vector<int32_t> inv_ptr;        // n_major + 1 : tasks of each major ...
-    std::vector<uint32_t> inv_task;      // n_tasks     : ... as slice*64+lane ids, in (block, position) order
+    std::vector<uint32_t> inv_task;      // n_tasks     : ... as slice*64+lane ids, in (block, first minor) order
+    // The row index: what the updates sum.  A *run* is a maximal stretch of consecutive live lanes of one slice with the same
+    // major; with `merge` the sweep adds a run's partial statistics inside the wave and stores ONE row, at the run's first
+    // lane.  row_task lists those first lanes per major, in inv_task's order.  Without merging every task is its own row
+    // and row_* equals inv_*.
+    bool merge = false;
+    int64_t n_rows = 0;
+    std::vector<int32_t> row_ptr;        // n_major + 1
+    std::vector<uint32_t> row_task;      // n_rows
     std::vector<int32_t> cell_perm;      // cells of the column range in layout order: position -> original local column
                                          // (minors on side 0, majors on side 1; empty = identity).  order.cpp
     ExtVec<uint32_t> packed;             // n_slots (wide == false)
@@ -169,11 +177,12 @@ struct LayoutParams {
     int32_t max_len;       // longest task (entries), multiple of 4
     int32_t n_wg;          // persistent workgroups of the sweep kernel
     int32_t row_slots;     // 16-byte LDS slots per staged factor row at this rank (lds_row_bytes / 16)
+    int32_t merge = 0;     // the pieces of a cut (major, block) pair sit in neighbouring lanes and share one partial row
 };
 // the same geometry: what the layout cache keys on (with the side)
 inline bool operator==(const LayoutParams &a, const LayoutParams &b)
 {
-    return a.block_width == b.block_width && a.block_cap == b.block_cap && a.max_len == b.max_len && a.n_wg == b.n_wg && a.row_slots == b.row_slots;
+    return a.block_width == b.block_width && a.block_cap == b.block_cap && a.max_len == b.max_len && a.n_wg == b.n_wg && a.row_slots == b.row_slots && a.merge == b.merge;
 }
 
 // Padded rank used on the device (even, so a factor row is a whole number of 16-byte LDS reads).

@@ -56,9 +56,9 @@ void dev_free(void *p);             // returns a device buffer to the pool (belo
 // share one of these; the per-engine part is DeviceSide::part.
 struct DeviceArrays {
     int device = 0;
-    uint32_t *packed = nullptr, *widx = nullptr, *task_major = nullptr, *inv_task = nullptr;
+    uint32_t *packed = nullptr, *widx = nullptr, *task_major = nullptr, *row_task = nullptr;
     double *wval = nullptr;
-    int32_t *slice_width = nullptr, *seg_block = nullptr, *seg_ptr = nullptr, *wg_seg0 = nullptr, *inv_ptr = nullptr;
+    int32_t *slice_width = nullptr, *seg_block = nullptr, *seg_ptr = nullptr, *wg_seg0 = nullptr, *row_ptr = nullptr;
     int32_t *slice_fast = nullptr, *block_start = nullptr;
     int64_t *slice_off = nullptr;
     ~DeviceArrays()
@@ -66,8 +66,8 @@ struct DeviceArrays {
         int cur = -1;
         (void)hipGetDevice(&cur);
         (void)hipSetDevice(device);
-        dev_free(packed); dev_free(widx); dev_free(wval); dev_free(task_major); dev_free(inv_task);
-        dev_free(slice_width); dev_free(seg_block); dev_free(seg_ptr); dev_free(wg_seg0); dev_free(inv_ptr);
+        dev_free(packed); dev_free(widx); dev_free(wval); dev_free(task_major); dev_free(row_task);
+        dev_free(slice_width); dev_free(seg_block); dev_free(seg_ptr); dev_free(wg_seg0); dev_free(row_ptr);
         dev_free(slice_off); dev_free(slice_fast); dev_free(block_start);
         if (cur >= 0) (void)hipSetDevice(cur);
     }
@@ -75,15 +75,16 @@ struct DeviceArrays {
 
 struct DeviceSide {
     std::shared_ptr<DeviceArrays> arrays;      // owner of the pointers below (possibly shared with other engines)
-    uint32_t *packed = nullptr, *widx = nullptr, *task_major = nullptr, *inv_task = nullptr;
+    uint32_t *packed = nullptr, *widx = nullptr, *task_major = nullptr, *row_task = nullptr;
     double *wval = nullptr;
-    int32_t *slice_width = nullptr, *seg_block = nullptr, *seg_ptr = nullptr, *wg_seg0 = nullptr, *inv_ptr = nullptr;
+    int32_t *slice_width = nullptr, *seg_block = nullptr, *seg_ptr = nullptr, *wg_seg0 = nullptr, *row_ptr = nullptr;
     int32_t *slice_fast = nullptr, *block_start = nullptr;
     int64_t *slice_off = nullptr;
     double *part = nullptr;                    // this engine's per-task partial statistics
-    int64_t n_major = 0, n_minor = 0, n_tasks = 0, n_slices = 0, n_slots = 0;
+    int64_t n_major = 0, n_minor = 0, n_tasks = 0, n_rows = 0, n_slices = 0, n_slots = 0;
     int32_t block_width = 0, n_blocks = 0, n_wg = 0, row_slots = 0;
     bool wide = false;
+    bool merge = false;                        // the sweep adds the runs of a slice in the wave: one partial row per run (Layout::merge)
 };
 
 // ---- device buffer pool.  An engine owns ~25 device buffers (state, partial rows up to 100 MB a side, reduce buffers);
@@ -385,6 +386,9 @@ int upload_side(const Layout &L, int R, int device, const vbnmf_matrix *X, Devic
     S.n_major = L.n_major; S.n_minor = L.n_minor; S.n_tasks = L.n_tasks; S.n_slices = L.n_slices;
     S.n_slots = L.n_slots; S.block_width = L.block_width; S.n_blocks = L.n_blocks; S.n_wg = L.n_wg; S.wide = L.wide;
     S.row_slots = L.row_slots;
+    S.n_rows = L.n_rows; S.merge = L.merge;
+    if (L.merge && rank_shares(R) != 1)
+        return fail(VBNMF_ERR_BAD_ARG, "a layout with merged pieces serves ranks up to 32 only (padded rank %d)", R);
     if (S.row_slots < R / 2 / rank_shares(R) * rank_shares(R) || !(S.row_slots & 1))
         return fail(VBNMF_ERR_BAD_ARG, "layout row stride of %d slots cannot hold rows of padded rank %d", S.row_slots, R);
     std::shared_ptr<DeviceArrays> A;
@@ -409,14 +413,14 @@ int upload_side(const Layout &L, int R, int device, const vbnmf_matrix *X, Devic
         if (int rc = dev_upload(&A->seg_block, L.seg_block)) return rc;
         if (int rc = dev_upload(&A->seg_ptr, L.seg_ptr)) return rc;
         if (int rc = dev_upload(&A->wg_seg0, L.wg_seg0)) return rc;
-        if (int rc = dev_upload(&A->inv_ptr, L.inv_ptr)) return rc;
-        if (int rc = dev_upload(&A->inv_task, L.inv_task)) return rc;
+        if (int rc = dev_upload(&A->row_ptr, L.row_ptr)) return rc;
+        if (int rc = dev_upload(&A->row_task, L.row_task)) return rc;
         if (X) store_device_copy(X, &L, device, A);
     }
     S.arrays = A;
-    S.packed = A->packed; S.widx = A->widx; S.wval = A->wval; S.task_major = A->task_major; S.inv_task = A->inv_task;
+    S.packed = A->packed; S.widx = A->widx; S.wval = A->wval; S.task_major = A->task_major; S.row_task = A->row_task;
     S.slice_width = A->slice_width; S.seg_block = A->seg_block; S.seg_ptr = A->seg_ptr; S.wg_seg0 = A->wg_seg0;
-    S.inv_ptr = A->inv_ptr; S.slice_off = A->slice_off; S.slice_fast = A->slice_fast; S.block_start = A->block_start;
+    S.row_ptr = A->row_ptr; S.slice_off = A->slice_off; S.slice_fast = A->slice_fast; S.block_start = A->block_start;
     if (with_part) { if (int rc = dev_alloc(&S.part, (size_t)L.n_slices * kLanes * R)) return rc; }
     return VBNMF_OK;
 }
@@ -453,6 +457,7 @@ SweepSide sweep_side_args(const vbnmf_engine *e, bool gene_side)
     P.csl = gene_side ? e->csl : nullptr; P.csum = gene_side ? e->csum : nullptr;      // (the pair form's column sums: gene side only)
     P.n_minor = (int32_t)S.n_minor; P.block_start = S.block_start;
     P.row_slots = S.row_slots;
+    P.merge = S.merge ? 1 : 0;
     {
         // The youngest third of the workgroup's waves pull slices from the SHORT end of a segment's list (kernels.h:
         // take_ticket_ends).  Measured per side, interleaved, on two boxes (k_sweep us, rank 10, 768 threads: neither side /
@@ -601,7 +606,7 @@ int launch_sweep(vbnmf_engine *e)
 // step with it).  `dense`: the partitioned gene side, whose statistics are already summed into `red` -- no index to stage.
 int stage_ids(const DeviceSide &S, unsigned grid, bool dense = false)
 {
-    return !dense && S.n_tasks >= (int64_t)256 * grid ? 1 : 0;
+    return !dense && S.n_rows >= (int64_t)256 * grid ? 1 : 0;
 }
 
 // ctl != nullptr: device-driven loop, the hyper-parameters are read from the control block on the device
@@ -617,14 +622,14 @@ int launch_update(vbnmf_engine *e, bool gene_side, double a, double b, double fu
     const bool dense = gene_side && e->partitioned;               // statistics already summed into `red`
     const double *redin = e->red_in ? e->red_in : e->red;
     const double *acc = dense ? redin : S.part;
-    const int32_t *inv_ptr = dense ? nullptr : S.inv_ptr;
-    const uint32_t *inv_task = dense ? nullptr : S.inv_task;
+    const int32_t *row_ptr = dense ? nullptr : S.row_ptr;
+    const uint32_t *row_task = dense ? nullptr : S.row_task;
     const double *other = dense ? redin + (size_t)e->n * e->R : nullptr;
     const double *other_bp = dense ? nullptr : v.other_bp;
     const int other_nb = dense ? 0 : e->ub;
     const int stage = stage_ids(S, grid, dense);
     return with_rank(e->R, [&](auto rt) {
-        return launch_kernel<k_update<rt()>>(e, dim3(grid), kUpdateThreads, 0, acc, inv_ptr, inv_task, v.nmaj, e->r, other, other_bp,
+        return launch_kernel<k_update<rt()>>(e, dim3(grid), kUpdateThreads, 0, acc, row_ptr, row_task, v.nmaj, e->r, other, other_bp,
                                              other_nb, a, b, lga, fudge, v.l, v.ll, v.e, v.d, v.bp, ctl, v.idx, fold, stage);
     });
 }
@@ -647,6 +652,9 @@ bool build_update_table(const Layout &LA, const Layout &LB, int ub, int R, std::
     std::vector<Plan> plans(ub);
     // (a thread per 16 K majors: on a small matrix starting threads costs more than the table -- 1 ms of a 1.7 ms engine creation)
     const int table_threads = (int)std::max<int64_t>(1, std::min<int64_t>(host_threads(), (nm[0] + nm[1]) >> 14));
+    // The plan over an index of the layouts: the row index (what the kernel walks), or the inverse index (every task).
+    auto plan_over = [&](bool by_rows, int64_t &stride_out, int64_t &vis_words_out) {
+    for (Plan &P : plans) P = Plan();
     parallel_for(ub, [&](int64_t b0, int64_t b1, int) {
         std::vector<Item> items;
         for (int64_t b = b0; b < b1; b++) {
@@ -655,7 +663,8 @@ bool build_update_table(const Layout &LA, const Layout &LB, int ub, int R, std::
             for (int sd = 0; sd < 2; sd++) {
                 const int64_t m0 = std::min(nm[sd], b * per[sd]), m1 = std::min(nm[sd], m0 + per[sd]);
                 for (int64_t M = m0; M < m1; M++) {
-                    const int32_t cnt = Ls[sd]->inv_ptr[M + 1] - Ls[sd]->inv_ptr[M];
+                    const std::vector<int32_t> &ptr = by_rows ? Ls[sd]->row_ptr : Ls[sd]->inv_ptr;
+                    const int32_t cnt = ptr[M + 1] - ptr[M];
                     items.push_back({cnt + 4, ((uint32_t)sd << 31) | (uint32_t)(M - m0), cnt});
                     P.ids += cnt;
                 }
@@ -679,8 +688,17 @@ bool build_update_table(const Layout &LA, const Layout &LB, int ub, int R, std::
     int64_t max_ids = 0;
     V = 1;
     for (const Plan &P : plans) { max_ids = std::max(max_ids, P.ids); V = std::max(V, (int32_t)P.vmax); }
-    const int64_t vis_words = ((int64_t)RB * V * 3 + 3) & ~(int64_t)3;
-    const int64_t stride = (vis_words + max_ids + 3) & ~(int64_t)3;
+    vis_words_out = ((int64_t)RB * V * 3 + 3) & ~(int64_t)3;
+    stride_out = (vis_words_out + max_ids + 3) & ~(int64_t)3;
+    };
+    // Which form an engine takes stays a function of its TASKS, as before the pieces were merged (a table of rows is never
+    // longer than the table of tasks): the table is sized over the inverse index first, then cut over the row index.
+    int64_t stride = 0, vis_words = 0;
+    if (LA.merge || LB.merge) {
+        plan_over(false, stride, vis_words);
+        if (stride > kUpdTabWords) return false;
+    }
+    plan_over(true, stride, vis_words);
     if (stride > kUpdTabWords) return false;
     ids_off = (int32_t)vis_words;
     stride4 = (int32_t)(stride / 4);
@@ -695,7 +713,7 @@ bool build_update_table(const Layout &LA, const Layout &LB, int ub, int R, std::
                 first[sd].assign((size_t)(m1 - m0) + 1, 0);
                 for (int64_t M = m0; M < m1; M++) {
                     first[sd][M - m0] = q;
-                    for (int32_t u = Ls[sd]->inv_ptr[M]; u < Ls[sd]->inv_ptr[M + 1]; u++) row[ids_off + q++] = Ls[sd]->inv_task[u];
+                    for (int32_t u = Ls[sd]->row_ptr[M]; u < Ls[sd]->row_ptr[M + 1]; u++) row[ids_off + q++] = Ls[sd]->row_task[u];
                 }
                 first[sd][m1 - m0] = q;
             }
@@ -764,7 +782,7 @@ int launch_final(vbnmf_engine *e)
 int launch_pack(vbnmf_engine *e)
 {
     const int64_t cnt = e->n * e->R;
-    hipLaunchKernelGGL(k_pack, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, e->stream, e->A.part, e->A.inv_ptr, e->A.inv_task, e->n, e->R, e->red);
+    hipLaunchKernelGGL(k_pack, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, e->stream, e->A.part, e->A.row_ptr, e->A.row_task, e->n, e->R, e->red);
     HIPCHECK(hipGetLastError());
     hipLaunchKernelGGL(k_tail, dim3(1), dim3(1024), 0, e->stream, e->bpH, e->ub, e->R, e->epart,
                        2 * (int64_t)e->n_wg, e->lgx, e->red + cnt);
@@ -818,12 +836,12 @@ int launch_ml_update(vbnmf_engine *e, bool gene_side, int prior, double ga, doub
     const bool dense = gene_side && e->partitioned;
     const double *redin = e->red_in ? e->red_in : e->red;
     const double *part = dense ? redin : S.part;
-    const int32_t *inv_ptr = dense ? nullptr : S.inv_ptr;
-    const uint32_t *inv_task = dense ? nullptr : S.inv_task;
+    const int32_t *row_ptr = dense ? nullptr : S.row_ptr;
+    const uint32_t *row_task = dense ? nullptr : S.row_task;
     const double *other_bp = dense ? redin + (size_t)e->n * e->R : v.other_bp;
     const int other_nb = dense ? 1 : e->ub;
     return with_rank(e->R, [&](auto rt) {
-        return launch_kernel<k_ml_update<rt()>>(e, dim3(grid), kUpdateThreads, 0, part, inv_ptr, inv_task, v.nmaj, e->r,
+        return launch_kernel<k_ml_update<rt()>>(e, dim3(grid), kUpdateThreads, 0, part, row_ptr, row_task, v.nmaj, e->r,
                                                 other_bp, other_nb, prior, ga, gb, eps, v.l, v.bp, stop, fold,
                                                 stage_ids(S, grid, dense));
     });
@@ -854,7 +872,7 @@ int launch_ml_tail(vbnmf_engine *e)
 int launch_ml_pack(vbnmf_engine *e, const int32_t *stop)
 {
     const int64_t cnt = e->n * e->R;
-    hipLaunchKernelGGL(k_pack_tail, dim3((unsigned)((cnt + 255) / 256) + 1), dim3(256), 0, e->stream, e->A.part, e->A.inv_ptr, e->A.inv_task, e->n, e->R, e->red,
+    hipLaunchKernelGGL(k_pack_tail, dim3((unsigned)((cnt + 255) / 256) + 1), dim3(256), 0, e->stream, e->A.part, e->A.row_ptr, e->A.row_task, e->n, e->R, e->red,
                        e->bpH, e->ub, stop);
     HIPCHECK(hipGetLastError());
     return VBNMF_OK;
@@ -1887,7 +1905,7 @@ int queue_vb_step(const LoopGroup &G, double fudge, bool hist, int max_it)
         // the final build that is slower for a local group of eight as well, 0.373-0.376 against 0.370-0.371 ms per
         // partition step on the same box.
         const int64_t cnt = e->n * e->R;
-        hipLaunchKernelGGL(k_pack_tail, dim3((unsigned)((cnt + 255) / 256) + 1), dim3(256), 0, e->stream, e->A.part, e->A.inv_ptr, e->A.inv_task, e->n, e->R, e->red,
+        hipLaunchKernelGGL(k_pack_tail, dim3((unsigned)((cnt + 255) / 256) + 1), dim3(256), 0, e->stream, e->A.part, e->A.row_ptr, e->A.row_task, e->n, e->R, e->red,
                            e->bpH, e->ub, stop);
         HIPCHECK(hipGetLastError());
         evA[p] = next_event(e);
@@ -2452,7 +2470,7 @@ int batch_ml_run(vbnmf_engine **engs, int32_t count, int32_t prior, double gamma
         for (int v = 0; v < NV; v++) {
             const int t = v == 0 ? 1 : conn ? 4 + (v - 1) : (v == 1 ? 3 : 2);          // a step of that variant
             MlUpdJob &J = jh[(size_t)v * B + b];
-            J.part = e->B.part; J.inv_ptr = e->B.inv_ptr; J.inv_task = e->B.inv_task; J.nmaj = e->m;
+            J.part = e->B.part; J.row_ptr = e->B.row_ptr; J.row_task = e->B.row_task; J.nmaj = e->m;
             J.other_bp = e->bpW; J.f = e->lh; J.bp = Ht[t & 1]; J.stop = nullptr;
             J.ga = gamma_a; J.gb = gamma_b; J.eps = eps;
             J.r = e->r; J.other_nb = e->ub; J.prior = prior;
@@ -2463,7 +2481,7 @@ int batch_ml_run(vbnmf_engine **engs, int32_t count, int32_t prior, double gamma
         for (int par = 0; par < 2; par++) {                                      // step t of parity par = t & 1
             const int32_t *stop = &(e->ctl2 + par)->stop;                        // what that step's H update left
             MlUpdJob &J = jw[(size_t)par * B + b];
-            J.part = e->A.part; J.inv_ptr = e->A.inv_ptr; J.inv_task = e->A.inv_task; J.nmaj = e->n;
+            J.part = e->A.part; J.row_ptr = e->A.row_ptr; J.row_task = e->A.row_task; J.nmaj = e->n;
             J.other_bp = Ht[par]; J.f = e->lw; J.bp = e->bpW; J.stop = stop;
             J.ga = gamma_a; J.gb = gamma_b; J.eps = eps;
             J.r = e->r; J.other_nb = e->ub; J.prior = prior;
@@ -3485,7 +3503,7 @@ int spmm_device(vbnmf_engine *e, bool gene_side, double *target)
     if (int rc = launch_spmm(e, a)) return rc;
     const SideView v = side_view(e, gene_side);
     const int64_t cnt = v.nmaj * e->R;
-    return launch_kernel<k_pack>(e, dim3((unsigned)((cnt + 255) / 256)), 256, 0, v.S.part, v.S.inv_ptr, v.S.inv_task, v.nmaj, e->R, target);
+    return launch_kernel<k_pack>(e, dim3((unsigned)((cnt + 255) / 256)), 256, 0, v.S.part, v.S.row_ptr, v.S.row_task, v.nmaj, e->R, target);
 }
 
 // work space of the truncated SVD: [gram partials kGramBlocks * R*R | S (R*R) | S2 (R*R) | vals (R)]

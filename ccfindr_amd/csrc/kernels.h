@@ -60,6 +60,8 @@ struct SweepSide {
     int32_t n_minor;
     int32_t row_slots;             // LDS row stride of the staged factor block in 16-byte slots (odd; >= R / 2: the stride of the
                                    // layout's rank class, which may be wider than this rank's own rows -- common.h, rank classes)
+    int32_t merge;                 // SP = 1: the runs of a slice (consecutive lanes of one major: the pieces of a cut pair, laid side
+                                   // by side by the layout) are added up in the wave and stored as ONE partial row, the first lane's
     int32_t logterm;               // this side also accumulates sum x*log(wth)
     int32_t n_wg;
     const LogTabEntry *logtab;     // [128] ln table (staged at the front of LDS)
@@ -652,13 +654,40 @@ __device__ __forceinline__ void sweep_side(const SweepSide &S, double2 *__restri
                 }
             }
 
-            // partial statistics of this task and the lane's evidence contribution
-            {
+            // Merged pieces (SweepSide::merge): a run's first lane -- its leader -- takes the sum of the run's accumulators and
+            // of its sum x log(wth); only leaders store a row and count towards the evidence and the column sums.  A
+            // segmented sum over lane distances 1, 2, 4, ... : at distance d a lane adds the lane d above it if that lane is in
+            // its run (`same`, from the ballot of the leaders, so wave-uniform like the trip count: as many steps as the
+            // longest run of the slice needs, none in a slice without runs).  The tree depends on lane positions alone.
+            bool lead = true;
+            if constexpr (SP == 1) {
+                if (S.merge) {
+                    const uint32_t Mprev = (uint32_t)__shfl_up((int)M, 1, 64);
+                    lead = lane == 0 || M != Mprev || M == kIdle;
+                    unsigned long long same = ~__ballot(lead) >> 1;       // bit l: lane l + 1 is in lane l's run
+#pragma unroll 1
+                    for (int d = 1; same != 0; d <<= 1) {
+                        const bool take = (same >> lane) & 1ull;
+#pragma unroll
+                        for (int k = 0; k < R; k++) {
+                            const double up = __shfl_down(T.acc[k], d, 64);
+                            T.acc[k] = take ? T.acc[k] + up : T.acc[k];
+                        }
+                        if (LOGTERM) {
+                            const double up = __shfl_down(T.lsum, d, 64);
+                            T.lsum = take ? T.lsum + up : T.lsum;
+                        }
+                        same &= same >> d;                                // bit l: lanes l + 1 .. l + 2 d are in lane l's run
+                    }
+                }
+            }
+            // partial statistics of this task (of its run) and the lane's evidence contribution
+            if (lead) {
                 double2 *P = reinterpret_cast<double2 *>(S.part + ((size_t)s * 64 + tlane) * RT + hp * R);
 #pragma unroll
                 for (int kk = 0; kk < R / 2; kk++) st_part(P + kk, make_double2(T.acc[2 * kk], T.acc[2 * kk + 1]));
             }
-            if (EV == 1 && M != kIdle) {
+            if (EV == 1 && M != kIdle && lead) {
                 const double2 *L2 = reinterpret_cast<const double2 *>(S.llF + (size_t)M * RT + hp * R);
                 double evt = 0.0;
 #pragma unroll
@@ -670,11 +699,11 @@ __device__ __forceinline__ void sweep_side(const SweepSide &S, double2 *__restri
                 if (hp == 0) evt -= T.lsum;               // every lane of the group holds the task's sum x log(wth)
                 ev += evt;
             }
-            if (EV == 2 && M != kIdle && hp == 0) ev += T.lsum;
+            if (EV == 2 && M != kIdle && hp == 0 && lead) ev += T.lsum;
             if (CS && cs_on) {                             // column sums of F .* acc over the sub-slice's tasks
                 double c[R];
 #pragma unroll
-                for (int k = 0; k < R; k++) c[k] = (M != kIdle) ? T.F[k] * T.acc[k] : 0.0;
+                for (int k = 0; k < R; k++) c[k] = (M != kIdle && lead) ? T.F[k] * T.acc[k] : 0.0;
                 double o0, o1;
                 colsum_fold<R, 32, SP>(c, lane, 0, R, o0, o1, cs_base, cs_nv);
                 cs0 += o0; cs1 += o1;
@@ -765,7 +794,7 @@ __global__ __launch_bounds__(NT) void k_spmm(const SweepSide S)
 #ifndef VBNMF_GATHER_WIDTH
 #define VBNMF_GATHER_WIDTH 16
 #endif
-__device__ __forceinline__ double task_sum(const double *__restrict__ part, const uint32_t *__restrict__ inv_task,
+__device__ __forceinline__ double task_sum(const double *__restrict__ part, const uint32_t *__restrict__ row_task,
                                            int q0, int q1, int R, int k)
 {
     double s = 0.0;
@@ -774,7 +803,7 @@ __device__ __forceinline__ double task_sum(const double *__restrict__ part, cons
         uint32_t id[NF];
         double v[NF];
 #pragma unroll
-        for (int u = 0; u < NF; u++) id[u] = inv_task[min(q + u, q1 - 1)];
+        for (int u = 0; u < NF; u++) id[u] = row_task[min(q + u, q1 - 1)];
 #pragma unroll
         for (int u = 0; u < NF; u++) v[u] = ld_part(part + (size_t)id[u] * R + k);
 #pragma unroll
@@ -854,7 +883,7 @@ __device__ __forceinline__ void bp_colsums3(const double *__restrict__ bpA, cons
 // ------------------------------------------------------------------------------------
 // Posterior update of one factor (both sides share it).  256 persistent blocks; thread
 // (row_sub, k) walks its block's majors with a fixed k.
-//   s   = acc[major][k] (dense), or the sum of the major's task partials (inv_ptr != null)
+//   s   = acc[major][k] (dense), or the sum of the major's task partials (row_ptr != null)
 //   al  = a + l_old * s                     :38-39 / :48-49
 //   be  = a/b + other[k]                    :40-43 (rowSums of the incoming eh) / :50-53 (colSums of the NEW ew)
 //   e   = al/be ; d = al/be/be              :44,46 / :54,56
@@ -925,7 +954,7 @@ __device__ unsigned long long g_upd_stamps[2 * kUpdateBlocks * 12];
 
 template <int R>
 __global__ __launch_bounds__(kUpdateThreads) void k_update(
-    const double *__restrict__ acc, const int32_t *__restrict__ inv_ptr, const uint32_t *__restrict__ inv_task,
+    const double *__restrict__ acc, const int32_t *__restrict__ row_ptr, const uint32_t *__restrict__ row_task,
     int64_t nmaj, int r, const double *__restrict__ other, const double *__restrict__ other_bp, int other_nb,
     double a, double b, double lga, double fudge,
     double *__restrict__ l, double *__restrict__ ll, double *__restrict__ e, double *__restrict__ d, double *__restrict__ bp,
@@ -945,13 +974,13 @@ __global__ __launch_bounds__(kUpdateThreads) void k_update(
     const int64_t bm0 = (int64_t)blockIdx.x * per0, bm1 = min(nmaj, bm0 + per0);
     int q_lo = 0;
     bool staged = false;
-    if (stage_ids && inv_ptr && !fold.control_only && bm0 < bm1 && bm1 - bm0 < kStagePtr) {
-        q_lo = inv_ptr[bm0];
-        const int q_hi = inv_ptr[bm1];
+    if (stage_ids && row_ptr && !fold.control_only && bm0 < bm1 && bm1 - bm0 < kStagePtr) {
+        q_lo = row_ptr[bm0];
+        const int q_hi = row_ptr[bm1];
         staged = q_hi - q_lo <= kStageIds;               // (block-uniform)
         if (staged) {
-            for (int q = t; q <= (int)(bm1 - bm0); q += kUpdateThreads) s_ptr[q] = inv_ptr[bm0 + q];
-            for (int q = q_lo + t; q < q_hi; q += kUpdateThreads) s_ids[q - q_lo] = inv_task[q];
+            for (int q = t; q <= (int)(bm1 - bm0); q += kUpdateThreads) s_ptr[q] = row_ptr[bm0 + q];
+            for (int q = q_lo + t; q < q_hi; q += kUpdateThreads) s_ids[q - q_lo] = row_task[q];
         }
     }
     UPD_STAMP(1);
@@ -1068,9 +1097,9 @@ __global__ __launch_bounds__(kUpdateThreads) void k_update(
 #ifdef VBNMF_ABL_NOGATHER                                    /* ablation builds only (profiles/ubench/r04/upd_ablate.sh) */
                 const double s = 1.0 + 1e-9 * (double)k;
 #else
-                const double s = !inv_ptr ? acc[o]
+                const double s = !row_ptr ? acc[o]
                                  : staged ? task_sum_lds(acc, s_ids, s_ptr[M - bm0] - q_lo, s_ptr[M - bm0 + 1] - q_lo, R, k)
-                                          : task_sum(acc, inv_task, inv_ptr[M], inv_ptr[M + 1], R, k);
+                                          : task_sum(acc, row_task, row_ptr[M], row_ptr[M + 1], R, k);
 #endif
                 const double al = a + l[o] * s;
                 const double ev = al / be;
@@ -1442,20 +1471,20 @@ __global__ __launch_bounds__(kUpdateThreads) void k_prime(int64_t nmaj, int r, c
 // reduce buffer [swsum n*R | tail R+4] that the caller all-reduces.
 // ------------------------------------------------------------------------------------
 // out[major][k] = sum of the major's task partials, fixed order.
-__global__ __launch_bounds__(256) void k_pack(const double *__restrict__ part, const int32_t *__restrict__ inv_ptr,
-                                              const uint32_t *__restrict__ inv_task, int64_t nmaj, int R,
+__global__ __launch_bounds__(256) void k_pack(const double *__restrict__ part, const int32_t *__restrict__ row_ptr,
+                                              const uint32_t *__restrict__ row_task, int64_t nmaj, int R,
                                               double *__restrict__ out)
 {
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (e >= nmaj * R) return;
     const int64_t M = e / R;
     const int k = (int)(e - M * R);
-    out[e] = task_sum(part, inv_task, inv_ptr[M], inv_ptr[M + 1], R, k);
+    out[e] = task_sum(part, row_task, row_ptr[M], row_ptr[M + 1], R, k);
 }
 
 // k_pack and k_tail_h in one launch (the device-driven partitioned loop): one extra block forms the cell side's column sums.
-__global__ __launch_bounds__(256) void k_pack_tail(const double *__restrict__ part, const int32_t *__restrict__ inv_ptr,
-                                                   const uint32_t *__restrict__ inv_task, int64_t nmaj, int R,
+__global__ __launch_bounds__(256) void k_pack_tail(const double *__restrict__ part, const int32_t *__restrict__ row_ptr,
+                                                   const uint32_t *__restrict__ row_task, int64_t nmaj, int R,
                                                    double *__restrict__ out, const double *__restrict__ bpH, int nbH,
                                                    const int32_t *__restrict__ stop)
 {
@@ -1468,7 +1497,7 @@ __global__ __launch_bounds__(256) void k_pack_tail(const double *__restrict__ pa
     if (e >= nmaj * R) return;
     const int64_t M = e / R;
     const int k = (int)(e - M * R);
-    out[e] = task_sum(part, inv_task, inv_ptr[M], inv_ptr[M + 1], R, k);
+    out[e] = task_sum(part, row_task, row_ptr[M], row_ptr[M + 1], R, k);
 }
 
 // Device-driven loop of a cell-partitioned engine: the reduce buffer is sent in two pieces.  The first,

@@ -39,7 +39,8 @@ LayoutParams default_layout_params(int64_t n_major, int64_t n_minor, int R, int 
     // Longest task.  A lane walks its task serially (~0.15 us per entry when its wave is alone on a SIMD), so on a
     // small matrix 256-entry tasks leave a handful of waves running for 40 us while the rest of the chip idles:
     // tasks are cut short enough that every wave of every workgroup can have work, up to the 256 that the
-    // headline size wants (shorter tasks there only add partial rows).  VBNMF_MAX_LEN overrides.
+    // headline size wants (192 measures the same there and 128 slower with merged pieces, profiles/piece_merge_ab.txt).
+    // VBNMF_MAX_LEN overrides.
     int ml = env_int("VBNMF_MAX_LEN", 0);
     if (ml <= 0) {
         const int64_t waves = (int64_t)n_wg * (sweep_threads(R) / kLanes);
@@ -70,6 +71,9 @@ LayoutParams default_layout_params(int64_t n_major, int64_t n_minor, int R, int 
     lp.n_wg = n_wg;
     lp.max_len = ml;
     lp.row_slots = lds_row_bytes(R) / 16;
+    // One lane per task of the sweep (ranks up to 32): the pieces of a cut pair are laid in neighbouring lanes and the wave
+    // adds them up before anything is stored (cut_tasks).  VBNMF_MERGE_PIECES=0/1 forces it off / on.
+    lp.merge = (rank_shares(R) == 1 && env_int("VBNMF_MERGE_PIECES", 1) != 0) ? 1 : 0;
     return lp;
 }
 
@@ -219,9 +223,20 @@ std::vector<int64_t> block_positions(const MajorView &V, const std::vector<int64
     return bpos;
 }
 
-// A task: `len` entries of `major` from position `pos` of the view on; n1 / n2 of them have the value 1 / 2 (the fill places
-// the ones first, then the twos).
-struct Task { uint32_t major; int32_t len; int64_t pos; int32_t n1, n2; };
+// phase 0 = the task's entries of value 1 (placed first, see cut_tasks), 1 = those of value 2, 2 = the others
+// (every entry when the fast stretch is off)
+constexpr int kPhases = 3;
+inline int phase_of(double v, bool fast_ones) { return !fast_ones ? 2 : (v == 1.0 ? 0 : (v == 2.0 ? 1 : 2)); }
+
+// A task: `len` entries of `major`; n1 / n2 of them have the value 1 / 2 (the fill places the ones first, then the twos).
+// opos < 0: the entries are positions [pos, pos + len) of the view.  Otherwise the task is a piece of a cut pair whose
+// entries were dealt over its pieces: entry u is position pos + ord[opos + u], pos the pair's first position.
+// first: the smallest minor among its entries.
+struct Task { uint32_t major; int32_t len; int64_t pos; int32_t n1, n2; int64_t opos; int32_t first; };
+struct BlockTasks {
+    std::vector<Task> tasks;
+    std::vector<uint32_t> ord;          // the dealt pairs' entries, piece by piece, relative to the pair's first position
+};
 
 // tasks per block: (major, block) runs longer than max_len are cut in near-equal pieces
 // n1 = the task's entries of value exactly 1: they are placed first in the task, so that the sweep can run the
@@ -229,33 +244,89 @@ struct Task { uint32_t major; int32_t len; int64_t pos; int32_t n1, n2; };
 // count conversion, and on the gene side a running product in place of a logarithm per entry, kernels.h).
 // Tasks are therefore grouped by padded length first and, within a length class, by n1: the 64 tasks of a slice
 // then agree on how long that leading stretch is.
-std::vector<std::vector<Task>> cut_tasks(const MajorView &V, const std::vector<int64_t> &bpos, int32_t nblk, int32_t max_len, bool fast_ones)
+// merge: the pieces of a pair form a GROUP that is sorted as one unit and so lands in consecutive lanes; the sweep adds
+// the pieces' statistics inside the wave and the pair costs one partial row (two where it straddles a slice border).
+// The order of a pair's entries is free, so they are dealt round the pieces -- the ones first, then the twos, then the
+// rest: the pieces' lengths, ones and ones-or-twos differ by at most one.  The number of pieces is raised until all of
+// them fall in ONE padded length (a group whose pieces differed there could not be placed in a list sorted by it).
+std::vector<BlockTasks> cut_tasks(const MajorView &V, const std::vector<int64_t> &bpos, int32_t nblk, int32_t max_len, bool fast_ones, bool merge)
 {
-    std::vector<std::vector<Task>> btasks(nblk);
+    std::vector<BlockTasks> btasks(nblk);
     parallel_for(nblk, [&](int64_t b0, int64_t b1, int) {
+        struct Unit { int32_t t0, cnt, pad, n1; };           // tasks [t0, t0 + cnt) of T: a group, or a task alone
+        std::vector<Unit> units;
+        std::vector<uint32_t> dealt;
+        auto padded = [](int64_t len) { return (int32_t)((len + kWidthQuantum - 1) / kWidthQuantum); };
         for (int64_t blk = b0; blk < b1; blk++) {
-            std::vector<Task> &T = btasks[blk];
+            std::vector<Task> &T = btasks[blk].tasks;
+            std::vector<uint32_t> &O = btasks[blk].ord;
+            units.clear();
             for (int64_t M = 0; M < V.n_major; M++) {
                 const int64_t *bp = &bpos[(size_t)M * (nblk + 1)];
                 int64_t q0 = bp[blk], cnt = bp[blk + 1] - q0;
                 if (cnt <= 0) continue;
                 int64_t pieces = (cnt + max_len - 1) / max_len;
-                for (int64_t pc = 0; pc < pieces; pc++) {
-                    int64_t s = cnt * pc / pieces, t = cnt * (pc + 1) / pieces;
-                    int32_t n1 = 0, n2 = 0;
-                    if (fast_ones) for (int64_t q = q0 + s; q < q0 + t; q++) { n1 += (V.val[q] == 1.0); n2 += (V.val[q] == 2.0); }
-                    T.push_back({(uint32_t)M, (int32_t)(t - s), q0 + s, n1, n2});
+                if (!merge || pieces == 1) {
+                    for (int64_t pc = 0; pc < pieces; pc++) {
+                        int64_t s = cnt * pc / pieces, t = cnt * (pc + 1) / pieces;
+                        int32_t n1 = 0, n2 = 0;
+                        if (fast_ones) for (int64_t q = q0 + s; q < q0 + t; q++) { n1 += (V.val[q] == 1.0); n2 += (V.val[q] == 2.0); }
+                        units.push_back({(int32_t)T.size(), 1, padded(t - s), n1});
+                        T.push_back({(uint32_t)M, (int32_t)(t - s), q0 + s, n1, n2, -1, V.idx[q0 + s]});
+                    }
+                    continue;
                 }
+                // Every piece in one padded length: with P pieces of w quanta the lengths cnt / P (+ 1) must all lie in
+                // (4 (w - 1), 4 w].  Among the counts from the fewest the cap allows to half as many again, the one that
+                // costs least: its slots, padding included, plus six slots per piece (3 000 x 6 000 at a cap of 16: fewer,
+                // longer pieces keep more of the leading stretch of ones, more, shorter ones pad less).  More pieces cost
+                // no more rows.
+                {
+                    int64_t best = 0, best_cost = 0;
+                    for (int64_t P = pieces; P <= std::min<int64_t>(cnt, pieces + pieces / 2 + 2) || !best; P++) {
+                        const int64_t w = (cnt + kWidthQuantum * P - 1) / (kWidthQuantum * P);
+                        if (cnt < P * (kWidthQuantum * (w - 1) + 1)) continue;
+                        const int64_t cost = kWidthQuantum * w * P + 6 * P;
+                        if (!best || cost < best_cost) { best = P; best_cost = cost; }
+                    }
+                    pieces = best;
+                }
+                dealt.clear();
+                int64_t n1t = 0, n12t = 0;
+                for (int ph = fast_ones ? 0 : 2; ph < kPhases; ph++) {
+                    for (int64_t u = 0; u < cnt; u++) if (phase_of(V.val[q0 + u], fast_ones) == ph) dealt.push_back((uint32_t)u);
+                    if (ph == 0) n1t = (int64_t)dealt.size();
+                    if (ph == 1) n12t = (int64_t)dealt.size();
+                }
+                int32_t gmin1 = INT32_MAX;
+                const int32_t t0 = (int32_t)T.size();
+                for (int64_t pc = 0; pc < pieces; pc++) {                  // piece pc takes entries pc, pc + pieces, ... of the deal
+                    const int64_t len = cnt / pieces + (pc < cnt % pieces ? 1 : 0);
+                    const int32_t n1 = (int32_t)(n1t > pc ? (n1t - pc + pieces - 1) / pieces : 0);
+                    const int32_t n12 = (int32_t)(n12t > pc ? (n12t - pc + pieces - 1) / pieces : 0);
+                    const int64_t opos = (int64_t)O.size();
+                    int32_t first = INT32_MAX;
+                    for (int64_t j = 0; j < len; j++) {
+                        const uint32_t u = dealt[pc + j * pieces];
+                        O.push_back(u);
+                        first = std::min(first, V.idx[q0 + u]);
+                    }
+                    gmin1 = std::min(gmin1, n1);
+                    T.push_back({(uint32_t)M, (int32_t)len, q0, n1, n12 - n1, opos, first});
+                }
+                units.push_back({t0, (int32_t)pieces, padded(cnt / pieces + (cnt % pieces ? 1 : 0)), gmin1});
             }
-            auto padded = [](int32_t len) { return (len + kWidthQuantum - 1) / kWidthQuantum; };
-            std::stable_sort(T.begin(), T.end(), [&](const Task &a, const Task &c2) {
-                const int32_t pa = padded(a.len), pc2 = padded(c2.len);
-                if (pa != pc2) return pa > pc2;
+            std::stable_sort(units.begin(), units.end(), [&](const Unit &a, const Unit &c2) {
+                if (a.pad != c2.pad) return a.pad > c2.pad;
                 // inside a length class by the number of ones -- descending in even classes, ascending in odd ones, so
                 // that the slice that straddles two classes joins tasks with ALIKE counts (its leading stretch is the
                 // minimum over its lanes): gene side of the headline matrix, stretch 48.0 -> 53.9 % of the slots
-                return (pa & 1) ? a.n1 < c2.n1 : a.n1 > c2.n1;
+                return (a.pad & 1) ? a.n1 < c2.n1 : a.n1 > c2.n1;
             });
+            std::vector<Task> sorted;
+            sorted.reserve(T.size());
+            for (const Unit &u : units) sorted.insert(sorted.end(), T.begin() + u.t0, T.begin() + u.t0 + u.cnt);
+            T.swap(sorted);
         }
     });
     return btasks;
@@ -275,24 +346,31 @@ void permute_rows(V &v, const std::vector<int32_t> &order, size_t width)
 // else 0).  `major` is the layout's own task_major (the one column the device reads); the others serve the builder only.
 struct TaskTable {
     std::vector<uint32_t> &major;
-    std::vector<int64_t> pos;
-    std::vector<int32_t> len, n1, n2;
+    std::vector<int64_t> pos, opos;
+    std::vector<int32_t> len, n1, n2, first;
+    BigVec<uint32_t> ord;                   // the dealt pairs' entries (Task::opos points in here), all blocks
     explicit TaskTable(Layout &L) : major(L.task_major) {}
-    void assign(size_t rows) { major.assign(rows, kIdleLane); pos.assign(rows, 0); len.assign(rows, 0); n1.assign(rows, 0); n2.assign(rows, 0); }
+    void assign(size_t rows)
+    {
+        major.assign(rows, kIdleLane); pos.assign(rows, 0); opos.assign(rows, -1); len.assign(rows, 0); n1.assign(rows, 0); n2.assign(rows, 0);
+        first.assign(rows, 0);
+    }
     void permute(const std::vector<int32_t> &order)
     {
-        permute_rows(major, order, kLanes); permute_rows(pos, order, kLanes); permute_rows(len, order, kLanes);
-        permute_rows(n1, order, kLanes); permute_rows(n2, order, kLanes);
+        permute_rows(major, order, kLanes); permute_rows(pos, order, kLanes); permute_rows(opos, order, kLanes); permute_rows(len, order, kLanes);
+        permute_rows(n1, order, kLanes); permute_rows(n2, order, kLanes); permute_rows(first, order, kLanes);
     }
+    // position in the view of entry u of task id
+    int64_t at(size_t id, int64_t u) const { return opos[id] < 0 ? pos[id] + u : pos[id] + (int64_t)ord[(size_t)(opos[id] + u)]; }
 };
 
 // slices: 64 consecutive tasks of a block; blocks in index order.  bslice0[b]: the first slice of block b.
-int form_slices(const std::vector<std::vector<Task>> &btasks, Layout &L, TaskTable &tasks, std::vector<int64_t> &bslice0)
+int form_slices(const std::vector<BlockTasks> &btasks, Layout &L, TaskTable &tasks, std::vector<int64_t> &bslice0)
 {
     const int32_t nblk = (int32_t)btasks.size();
     bslice0.assign(nblk + 1, 0);
     for (int32_t blk = 0; blk < nblk; blk++)
-        bslice0[blk + 1] = bslice0[blk] + ((int64_t)btasks[blk].size() + kLanes - 1) / kLanes;
+        bslice0[blk + 1] = bslice0[blk] + ((int64_t)btasks[blk].tasks.size() + kLanes - 1) / kLanes;
     L.n_slices = bslice0[nblk];
     if (L.n_slices > 0x7FFFFFF0LL / kLanes) return fail(VBNMF_ERR_BAD_ARG, "too many tasks for 32-bit task ids");
     tasks.assign((size_t)L.n_slices * kLanes);
@@ -300,12 +378,18 @@ int form_slices(const std::vector<std::vector<Task>> &btasks, Layout &L, TaskTab
     L.slice_block.assign(L.n_slices, 0);
     L.slice_fast.assign(L.n_slices, 0);
     L.n_tasks = 0;
+    size_t nord = 0;
+    for (int32_t blk = 0; blk < nblk; blk++) nord += btasks[blk].ord.size();
+    tasks.ord.reserve(nord);
     for (int32_t blk = 0; blk < nblk; blk++) {
-        const std::vector<Task> &T = btasks[blk];
+        const std::vector<Task> &T = btasks[blk].tasks;
+        const int64_t ord0 = (int64_t)tasks.ord.size();
+        tasks.ord.insert(tasks.ord.end(), btasks[blk].ord.begin(), btasks[blk].ord.end());
         L.n_tasks += (int64_t)T.size();
         for (size_t q = 0; q < T.size(); q++) {
             size_t id = (size_t)bslice0[blk] * kLanes + q;
             tasks.major[id] = T[q].major; tasks.pos[id] = T[q].pos; tasks.len[id] = T[q].len; tasks.n1[id] = T[q].n1; tasks.n2[id] = T[q].n2;
+            tasks.opos[id] = T[q].opos < 0 ? -1 : ord0 + T[q].opos; tasks.first[id] = T[q].first;
         }
         for (int64_t s = bslice0[blk]; s < bslice0[blk + 1]; s++) {
             int32_t w = tasks.len[(size_t)s * kLanes];           // sorted by padded length: the first lane's is the largest
@@ -468,8 +552,8 @@ void renumber_slices(Layout &L, TaskTable &tasks, const std::vector<int32_t> &or
     L.n_slots = off;
 }
 
-// inverse index: the tasks of each major in (block, position) order -- the fixed order in
-// which their partial statistics are summed (built once the slices have their final numbers)
+// inverse index: the tasks of each major in (block, position) order -- the pieces of a dealt pair by their first minor --:
+// the fixed order in which their partial statistics are summed (built once the slices have their final numbers)
 void build_inverse(Layout &L, const TaskTable &tasks)
 {
     const int64_t nmaj = L.n_major;
@@ -479,15 +563,15 @@ void build_inverse(Layout &L, const TaskTable &tasks)
     for (int64_t M = 0; M < nmaj; M++) L.inv_ptr[M + 1] += L.inv_ptr[M];
     L.inv_task.assign(L.n_tasks, 0);
     std::vector<int32_t> cur(L.inv_ptr.begin(), L.inv_ptr.end() - 1);
-    std::vector<int64_t> key(L.n_tasks);
+    std::vector<std::pair<int64_t, int32_t>> key(L.n_tasks);
     for (size_t id = 0; id < tasks.major.size(); id++) {
         uint32_t M = tasks.major[id];
         if (M == kIdleLane) continue;
         int32_t o = cur[M]++;
-        L.inv_task[o] = (uint32_t)id; key[o] = tasks.pos[id];
+        L.inv_task[o] = (uint32_t)id; key[o] = {tasks.pos[id], tasks.first[id]};
     }
     parallel_for(nmaj, [&](int64_t b, int64_t e, int) {
-        std::vector<std::pair<int64_t, uint32_t>> t2;      // (position, id) per major
+        std::vector<std::pair<std::pair<int64_t, int32_t>, uint32_t>> t2;      // ((position, first minor), id) per major
         for (int64_t M = b; M < e; M++) {
             int32_t s = L.inv_ptr[M], t = L.inv_ptr[M + 1];
             if (t - s < 2) continue;
@@ -497,6 +581,22 @@ void build_inverse(Layout &L, const TaskTable &tasks)
             for (int32_t q = s; q < t; q++) L.inv_task[q] = t2[q - s].second;
         }
     });
+}
+
+// row index: the first lanes of the runs (common.h) of each major, in the inverse index's order
+void build_rows(Layout &L)
+{
+    if (!L.merge) { L.row_ptr = L.inv_ptr; L.row_task = L.inv_task; L.n_rows = L.n_tasks; return; }
+    const std::vector<uint32_t> &major = L.task_major;
+    auto leads = [&](uint32_t id) { return (id % kLanes) == 0 || major[id] != major[id - 1]; };
+    L.row_ptr.assign(L.n_major + 1, 0);
+    L.row_task.clear();
+    for (int64_t M = 0; M < L.n_major; M++) {
+        for (int32_t q = L.inv_ptr[M]; q < L.inv_ptr[M + 1]; q++)
+            if (leads(L.inv_task[q])) L.row_task.push_back(L.inv_task[q]);
+        L.row_ptr[M + 1] = (int32_t)L.row_task.size();
+    }
+    L.n_rows = (int64_t)L.row_task.size();
 }
 
 // ---- fill: slot(t, lane) = off + (t/4)*256 + lane*4 + t%4 ; padding slots are {minor 0, value 0}.
@@ -528,11 +628,6 @@ struct SliceWriter {
     }
 };
 
-// phase 0 = the task's entries of value 1 (placed first, see cut_tasks), 1 = those of value 2, 2 = the others
-// (every entry when the fast stretch is off)
-constexpr int kPhases = 3;
-inline int phase_of(double v, bool fast_ones) { return !fast_ones ? 2 : (v == 1.0 ? 0 : (v == 2.0 ? 1 : 2)); }
-
 // per worker thread, allocated once: the fill must not allocate per slice
 struct GroupScratch {
     std::vector<int32_t> sorted[16];                   // per lane of the group: entry positions by (phase, residue, minor)
@@ -548,7 +643,7 @@ void fill_in_order(const MajorView &V, const TaskTable &tasks, int64_t s, bool f
         if (tasks.major[id] != kIdleLane)
             for (int ph = 0; ph < kPhases; ph++)
                 for (int64_t u = 0; u < tasks.len[id]; u++)
-                    if (phase_of(V.val[tasks.pos[id] + u], fast_ones) == ph) out.put(lane, t++, tasks.pos[id] + u);
+                    if (phase_of(V.val[tasks.at(id, u)], fast_ones) == ph) out.put(lane, t++, tasks.at(id, u));
         out.pad(lane, t);
     }
 }
@@ -580,18 +675,21 @@ void schedule_group(const MajorView &V, const TaskTable &tasks, int64_t s, const
     uint16_t avail[16][kPhases] = {};               // residues with entries left, as a bit mask
     int32_t rem[16][kPhases] = {}, step[16] = {};
     int64_t base[16];
+    const uint32_t *dealt[16];                      // a piece of a dealt pair: its entries relative to base (TaskTable::at)
+    auto at = [&](int j, int32_t t) { return dealt[j] ? base[j] + (int64_t)dealt[j][t] : base[j] + t; };
     int T = 0;
     for (int j = 0; j < 16; j++) {
         const size_t id = (size_t)s * kLanes + lanes[j];
-        base[j] = 0;
+        base[j] = 0; dealt[j] = nullptr;
         if (tasks.major[id] == kIdleLane) continue;
         const int64_t q0 = tasks.pos[id];
         const int32_t len = tasks.len[id];
         base[j] = q0;
+        if (tasks.opos[id] >= 0) dealt[j] = tasks.ord.data() + tasks.opos[id];
         scratch.bucket_of.resize(len);
         int32_t cnt[kPhases * 16] = {};
         for (int32_t t = 0; t < len; t++) {    // one pass over the task: phase and residue of every entry
-            const int b = phase_of(V.val[q0 + t], fast_ones) * 16 + ((idx[q0 + t] - m0) & 15);
+            const int b = phase_of(V.val[at(j, t)], fast_ones) * 16 + ((idx[at(j, t)] - m0) & 15);
             scratch.bucket_of[t] = (uint8_t)b;
             cnt[b]++;
         }
@@ -609,7 +707,7 @@ void schedule_group(const MajorView &V, const TaskTable &tasks, int64_t s, const
             scratch.sorted[j][w[scratch.bucket_of[t]]++] = t;
         for (int ph = 0; ph < kPhases; ph++)
             for (int r = 0; r < 16; r++)
-                nrow[j][ph][r] = (key[j][ph][r] >> 4) ? (int32_t)(idx[q0 + scratch.sorted[j][nxt[j][ph][r]]] - m0) : -1;
+                nrow[j][ph][r] = (key[j][ph][r] >> 4) ? (int32_t)(idx[at(j, scratch.sorted[j][nxt[j][ph][r]])] - m0) : -1;
         T = std::max(T, len);
     }
     for (int t = 0; t < T; t++) {
@@ -650,7 +748,7 @@ void schedule_group(const MajorView &V, const TaskTable &tasks, int64_t s, const
                     if (best < 0 || usedcnt[r] < usedcnt[best] || (usedcnt[r] == usedcnt[best] && k[r] > k[best])) best = r;
                 }
             }
-            out.put(lanes[j], step[j]++, base[j] + scratch.sorted[j][nxt[j][ph][best]++]);
+            out.put(lanes[j], step[j]++, at(j, scratch.sorted[j][nxt[j][ph][best]++]));
             if (ride < 0) {
                 if (!((used >> best) & 1u)) row_of[best] = nrow[j][ph][best];
                 used |= 1u << best; usedcnt[best]++;
@@ -658,7 +756,7 @@ void schedule_group(const MajorView &V, const TaskTable &tasks, int64_t s, const
             rem[j][ph]--;
             key[j][ph][best] -= 16;
             if ((key[j][ph][best] >> 4) == 0) { avail[j][ph] &= (uint16_t)~(1u << best); nrow[j][ph][best] = -1; }
-            else nrow[j][ph][best] = (int32_t)(idx[base[j] + scratch.sorted[j][nxt[j][ph][best]]] - m0);
+            else nrow[j][ph][best] = (int32_t)(idx[at(j, scratch.sorted[j][nxt[j][ph][best]])] - m0);
         }
     }
     for (int j = 0; j < 16; j++) out.pad(lanes[j], step[j]);
@@ -730,6 +828,7 @@ int build_layout(const Matrix &X, int64_t cb, int64_t ce, int side, const Layout
     L.max_len = lp.max_len;
     L.n_wg = lp.n_wg;
     L.row_slots = lp.row_slots;
+    L.merge = lp.merge != 0;
     if (!L.wide && X.max_val > kPackedCountMax) split_large_counts(V);
 
     L.block_start = cut_blocks(V, lp);
@@ -740,7 +839,7 @@ int build_layout(const Matrix &X, int64_t cb, int64_t ce, int side, const Layout
     std::vector<int64_t> bpos = block_positions(V, L.block_start);
     lap("bpos");
     const bool fast_ones = !L.wide && env_int("VBNMF_NO_FAST_ONES", 0) == 0;
-    std::vector<std::vector<Task>> btasks = cut_tasks(V, bpos, L.n_blocks, lp.max_len, fast_ones);
+    std::vector<BlockTasks> btasks = cut_tasks(V, bpos, L.n_blocks, lp.max_len, fast_ones, L.merge);
     lap("tasks");
     TaskTable tasks(L);
     std::vector<int64_t> bslice0;
@@ -750,6 +849,7 @@ int build_layout(const Matrix &X, int64_t cb, int64_t ce, int side, const Layout
     renumber_slices(L, tasks, share_out(L, bslice0));
     lap("shares");
     build_inverse(L, tasks);
+    build_rows(L);
     lap("inverse");
     try {
         // not zero-filled (the fill below writes every slot, padding included: first touch by the thread that fills)
@@ -958,6 +1058,7 @@ int vbnmf_layout_build(const vbnmf_matrix *X, int64_t col_begin, int64_t col_end
     view->wide_idx = L.wide ? L.wide_idx.data() : nullptr;
     view->wide_val = L.wide ? L.wide_val.data() : nullptr;
     view->cell_perm = L.cell_perm.empty() ? nullptr : L.cell_perm.data();
+    view->n_rows = L.n_rows; view->row_ptr = L.row_ptr.data(); view->row_task = L.row_task.data(); view->merge = L.merge ? 1 : 0;
     *out = H;
     return VBNMF_OK;
 }

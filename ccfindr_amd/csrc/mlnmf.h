@@ -98,7 +98,7 @@ struct MlFold {
 
 template <int R>
 __device__ __forceinline__ void ml_update_body(
-    const double *__restrict__ part, const int32_t *__restrict__ inv_ptr, const uint32_t *__restrict__ inv_task,
+    const double *__restrict__ part, const int32_t *__restrict__ row_ptr, const uint32_t *__restrict__ row_task,
     int64_t nmaj, int r, const double *__restrict__ other_bp, int other_nb, int prior, double ga, double gb, double eps,
     double *__restrict__ f, double *__restrict__ bp, const int32_t *__restrict__ stop, const MlFold &fold, int stage_ids)
 {
@@ -116,19 +116,19 @@ __device__ __forceinline__ void ml_update_body(
     // Cell-partitioned engines, W side (the twin of k_update's dense form, kernels.h): `part` holds the statistics already summed
     // over a gene's tasks AND over the partitions -- the reduce buffer behind the all-reduce, [nmaj][R] -- and other_bp is ONE
     // row, its reduced tail rowSums(h_new) of all cells.  No inverse index: nothing to stage, no further LDS.
-    const bool dense = inv_ptr == nullptr;               // (uniform over the launch)
+    const bool dense = row_ptr == nullptr;               // (uniform over the launch)
     // the block's stretch of the inverse index into LDS, first thing (as k_update, kernels.h)
     const int64_t per0 = (nmaj + gridDim.x - 1) / gridDim.x;
     const int64_t bm0 = (int64_t)blockIdx.x * per0, bm1 = min(nmaj, bm0 + per0);
     int q_lo = 0;
     bool staged = false;
     if (stage_ids && !dense && !fold.control_only && bm0 < bm1 && bm1 - bm0 < kStagePtr) {
-        q_lo = inv_ptr[bm0];
-        const int q_hi = inv_ptr[bm1];
+        q_lo = row_ptr[bm0];
+        const int q_hi = row_ptr[bm1];
         staged = q_hi - q_lo <= kStageIds;               // (block-uniform)
         if (staged) {
-            for (int q = t; q <= (int)(bm1 - bm0); q += kUpdateThreads) s_ptr[q] = inv_ptr[bm0 + q];
-            for (int q = q_lo + t; q < q_hi; q += kUpdateThreads) s_ids[q - q_lo] = inv_task[q];
+            for (int q = t; q <= (int)(bm1 - bm0); q += kUpdateThreads) s_ptr[q] = row_ptr[bm0 + q];
+            for (int q = q_lo + t; q < q_hi; q += kUpdateThreads) s_ids[q - q_lo] = row_task[q];
         }
     }
     if (fold.prev) {
@@ -221,7 +221,7 @@ __device__ __forceinline__ void ml_update_body(
                 if (k < r) {
                     const double s = staged ? task_sum_lds(part, s_ids, s_ptr[M - bm0] - q_lo, s_ptr[M - bm0 + 1] - q_lo, R, k)
                                    : dense  ? part[o]
-                                            : task_sum(part, inv_task, inv_ptr[M], inv_ptr[M + 1], R, k);
+                                            : task_sum(part, row_task, row_ptr[M], row_ptr[M + 1], R, k);
                     double up = f[o] * s;
                     if (prior) up = up + ga - 1.0;
                     v = up / down;
@@ -262,7 +262,7 @@ __device__ __forceinline__ void ml_update_body(
             if (k < r) {
                 const double s = staged ? task_sum_lds(part, s_ids, s_ptr[M - bm0] - q_lo, s_ptr[M - bm0 + 1] - q_lo, R, k)
                                : dense  ? part[o]
-                                        : task_sum(part, inv_task, inv_ptr[M], inv_ptr[M + 1], R, k);
+                                        : task_sum(part, row_task, row_ptr[M], row_ptr[M + 1], R, k);
                 double up = f[o] * s;
                 if (prior) up = up + ga - 1.0;   // :11,20
                 double v = up / down;
@@ -288,19 +288,19 @@ __device__ __forceinline__ void ml_update_body(
 
 template <int R>
 __global__ __launch_bounds__(kUpdateThreads) void k_ml_update(
-    const double *__restrict__ part, const int32_t *__restrict__ inv_ptr, const uint32_t *__restrict__ inv_task,
+    const double *__restrict__ part, const int32_t *__restrict__ row_ptr, const uint32_t *__restrict__ row_task,
     int64_t nmaj, int r, const double *__restrict__ other_bp, int other_nb, int prior, double ga, double gb, double eps,
     double *__restrict__ f, double *__restrict__ bp, const int32_t *__restrict__ stop, const MlFold fold, int stage_ids)
 {
-    ml_update_body<R>(part, inv_ptr, inv_task, nmaj, r, other_bp, other_nb, prior, ga, gb, eps, f, bp, stop, fold, stage_ids);
+    ml_update_body<R>(part, row_ptr, row_task, nmaj, r, other_bp, other_nb, prior, ga, gb, eps, f, bp, stop, fold, stage_ids);
 }
 
 // A BATCH of engines stepped by one launch (kernels.h: k_update2_batch; here the restarts of factorize(), reference
 // R/factorize.R:181: `for(irun in seq_len(nrun))`): blockIdx.y picks the engine's argument block, the body is the single engine's.
 struct MlUpdJob {
     const double *part;
-    const int32_t *inv_ptr;
-    const uint32_t *inv_task;
+    const int32_t *row_ptr;
+    const uint32_t *row_task;
     int64_t nmaj;
     const double *other_bp;
     double *f, *bp;
@@ -314,7 +314,7 @@ template <int R>
 __global__ __launch_bounds__(kUpdateThreads) void k_ml_update_batch(const MlUpdJob *__restrict__ jobs)
 {
     const MlUpdJob J = jobs[blockIdx.y];
-    ml_update_body<R>(J.part, J.inv_ptr, J.inv_task, J.nmaj, J.r, J.other_bp, J.other_nb, J.prior, J.ga, J.gb, J.eps, J.f, J.bp, J.stop,
+    ml_update_body<R>(J.part, J.row_ptr, J.row_task, J.nmaj, J.r, J.other_bp, J.other_nb, J.prior, J.ga, J.gb, J.eps, J.f, J.bp, J.stop,
                       J.fold, J.stage_ids);
 }
 

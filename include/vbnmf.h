@@ -639,6 +639,13 @@ typedef struct {
                                       (minors on side 0, majors on side 1): position -> column relative to col_begin.
                                       NULL = as stored.  Cells with alike gene support are stored next to each other, so
                                       a gene's entries fall into fewer cell blocks (csrc/order.cpp; VBNMF_CELL_ORDER=0/1). */
+    /* The row index: the partial rows the sweep stores and the updates sum.  A run is a maximal stretch of consecutive live
+       lanes of one slice with the same major; with merge == 1 the sweep adds a run's statistics inside the wave and stores
+       one row, at the run's first lane (ranks <= 32; VBNMF_MERGE_PIECES=0/1).  merge == 0: row_* equals inv_*. */
+    int64_t n_rows;
+    const int32_t *row_ptr;        /* [n_major + 1] */
+    const uint32_t *row_task;      /* [n_rows] first lanes of the runs of each major, as slice*64+lane ids, in inv_task's order */
+    int32_t merge;
 } vbnmf_layout_view;
 
 int vbnmf_layout_build(const vbnmf_matrix *X, int64_t col_begin, int64_t col_end, int32_t side,
