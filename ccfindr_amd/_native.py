@@ -164,6 +164,9 @@ SIGNATURES = {
     "vbnmf_cophenetic_grouped": (ctypes.c_int, [_I64, _I32, c_uint8_p, c_int64_p, ctypes.c_char_p, c_double_p]),
     "vbnmf_consensus_cophenetic": (ctypes.c_int, [_VP, ctypes.c_char_p, _I64, c_double_p, c_int64_p]),
     "vbnmf_test_cophenetic_dist": (ctypes.c_int, [_I64, c_double_p, c_int64_p, ctypes.c_char_p, c_double_p]),
+    "vbnmf_cophenetic_grouped_device": (ctypes.c_int, [_I32, _I64, _I32, c_uint8_p, c_int64_p, ctypes.c_char_p, c_double_p]),
+    "vbnmf_consensus_cophenetic_on": (ctypes.c_int, [_VP, ctypes.c_char_p, _I64, _I32, c_double_p, c_int64_p]),
+    "vbnmf_test_cophenetic_trace": (ctypes.c_int, [_I32, _I32, _I64, c_double_p, c_int64_p, ctypes.c_char_p, c_double_p, c_int64_p, c_double_p]),
     "vbnmf_engine_random_state": (ctypes.c_int, [_VP, _D, _D, _D, _D, ctypes.c_uint64]),
     "vbnmf_engine_svd": (ctypes.c_int, [_VP, _I32, _D, _I32, ctypes.c_uint64, c_double_p, c_double_p, c_double_p, c_int32_p]),
     "vbnmf_layout_build": (ctypes.c_int, [_VP, _I64, _I64, _I32, _I32, _VPP, ctypes.POINTER(LayoutView)]),

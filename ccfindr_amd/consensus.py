@@ -1,7 +1,8 @@
 """Consensus measures of ``factorize()`` (reference R/factorize.R:62-78, :218-230) from the label vectors of the runs,
 at any cell count: the device accumulator behind ``vbnmf_consensus_*`` (include/vbnmf.h, csrc/consensus.h) keeps the
 labels of every run and the integer sums the dispersion follows from; the cophenetic correlation is computed on the
-distinct label tuples (csrc/consensus.cpp).  The O(m^2) pair vector of the reference is never formed.
+distinct label tuples, on the host (csrc/consensus.cpp) up to ``DEFAULT_MAX_GROUPS`` of them and on the device
+(csrc/cophenet.h) up to ``DEVICE_MAX_GROUPS``.  The O(m^2) pair vector of the reference is never formed.
 """
 from __future__ import annotations
 
@@ -13,12 +14,16 @@ from . import _native as N
 from .engine import VBEngine
 
 METHODS = ("average", "single", "complete")     # the linkages the grouped cophenetic serves
-DEFAULT_MAX_GROUPS = 4096                       # distinct label tuples: a 128 MB distance matrix
+DEFAULT_MAX_GROUPS = 4096                       # distinct label tuples served on the host: a 128 MB distance matrix
+DEVICE_MAX_GROUPS = 32768                       # ... on the device: two matrices, 17 GB of device memory
+WHERE = {None: -1, "auto": -1, "host": 0, "device": 1}
 
 
-def cophenetic_grouped(tuples, sizes, method="average"):
+def cophenetic_grouped(tuples, sizes, method="average", device=None):
     """Cophenetic correlation of ``G`` groups of cells: ``tuples`` [G][R] labels of each group in the R runs, ``sizes`` [G]
-    cells per group; distance = Hamming distance of the tuples / R.  Host only.  NaN when either side has no variance."""
+    cells per group; distance = Hamming distance of the tuples / R.  ``device``: None = on the host, else the HIP device
+    that runs the agglomeration (the host's dendrogram, up to ``DEVICE_MAX_GROUPS`` groups).  NaN when either side has no
+    variance."""
     L = N.load()
     T = np.ascontiguousarray(tuples, dtype=np.uint8)
     if T.ndim != 2:
@@ -27,8 +32,11 @@ def cophenetic_grouped(tuples, sizes, method="average"):
     if s.shape != (T.shape[0],):
         raise ValueError("sizes must hold one count per group")
     out = ctypes.c_double()
-    N.check(L.vbnmf_cophenetic_grouped(T.shape[0], T.shape[1], T.ctypes.data_as(N.c_uint8_p), s.ctypes.data_as(N.c_int64_p),
-                                       str(method).encode(), ctypes.byref(out)))
+    args = (T.shape[0], T.shape[1], T.ctypes.data_as(N.c_uint8_p), s.ctypes.data_as(N.c_int64_p), str(method).encode(), ctypes.byref(out))
+    if device is None:
+        N.check(L.vbnmf_cophenetic_grouped(*args))
+    else:
+        N.check(L.vbnmf_cophenetic_grouped_device(int(device), *args))
     return out.value
 
 
@@ -67,11 +75,17 @@ class Consensus:
         N.check(self._lib.vbnmf_consensus_dispersion(self._h, ctypes.byref(out)))
         return out.value
 
-    def cophenetic(self, method="average", max_groups=DEFAULT_MAX_GROUPS, with_groups=False):
-        """``cophenet(conav / runs, m, method)`` (R/factorize.R:69-78) on the distinct label tuples; NaN past
-        ``max_groups`` of them.  ``with_groups``: return ``(coefficient, number of groups)``."""
+    def cophenetic(self, method="average", max_groups=None, with_groups=False, where=None):
+        """``cophenet(conav / runs, m, method)`` (R/factorize.R:69-78) on the distinct label tuples.  ``where``: 'host',
+        'device', or None = by size: up to ``DEFAULT_MAX_GROUPS`` groups on the host, above that on the accumulator's
+        device.  NaN past ``max_groups`` groups (None: ``DEFAULT_MAX_GROUPS`` on the host, ``DEVICE_MAX_GROUPS``
+        otherwise; the device never serves more than ``DEVICE_MAX_GROUPS``).  ``with_groups``: return ``(coefficient,
+        number of groups)``."""
+        if where not in WHERE:
+            raise ValueError("where must be None, 'host' or 'device'")
         out, groups = ctypes.c_double(), ctypes.c_int64()
-        N.check(self._lib.vbnmf_consensus_cophenetic(self._h, str(method).encode(), int(max_groups), ctypes.byref(out), ctypes.byref(groups)))
+        N.check(self._lib.vbnmf_consensus_cophenetic_on(self._h, str(method).encode(), 0 if max_groups is None else int(max_groups),
+                                                        WHERE[where], ctypes.byref(out), ctypes.byref(groups)))
         return (out.value, groups.value) if with_groups else out.value
 
     def labels(self, run):

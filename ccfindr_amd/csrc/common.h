@@ -21,7 +21,22 @@ int fail(int code, const char *fmt, ...);
 int env_int(const char *name, int dflt);    // an integer environment switch (unset or empty: dflt)
 
 // The consensus accumulator's label matrix on the host (engine.hip, for consensus.cpp): labels[run * m + cell], runs rows.
-int consensus_download(vbnmf_consensus *c, std::vector<uint8_t> &labels, int64_t &m, int32_t &runs, int32_t &unlabelled);
+// device (when not null): the HIP device the accumulator lives on.
+int consensus_download(vbnmf_consensus *c, std::vector<uint8_t> &labels, int64_t &m, int32_t &runs, int32_t &unlabelled, int32_t *device = nullptr);
+
+// The grouped cophenetic on the device (cophenet.h, compiled into engine.hip), as consensus.cpp's host glue sees it:
+// plain device buffers and three launches.  Every function returns a status and leaves the message set.
+constexpr int64_t kCophMaxGroups = 32768;   // the chain kernel's activity flags fill 32 KB of LDS; W and S take 16 G^2 bytes
+constexpr int kCophOut = 10;                // doubles in the chain kernel's result block (cophenet.h: k_coph_chain)
+enum { kCophOk = 0, kCophNotFinite = 1, kCophBound = 2 };    // its status word
+int coph_dev_use(int device);               // the device exists, is a gfx950, and is current
+int coph_dev_alloc(void **p, size_t bytes, const char *what);    // VBNMF_ERR_OOM names the byte count
+void coph_dev_free(void *p);
+int coph_dev_upload(void *dst, const void *src, size_t bytes);
+int coph_dev_download(void *dst, const void *src, size_t bytes);
+int coph_dev_setup_tuples(const uint8_t *tuples, const int64_t *sizes, int G, int R, double *W, double *S, double *weight, unsigned long long *isum, double *mm);
+int coph_dev_setup_dist(const double *dist, const int64_t *sizes, int G, double *W, double *S, double *weight, double *fsum, double *mm);
+int coph_dev_chain(double *W, double *S, double *weight, int *chain, int G, int link, long long *merges, double *heights, double *out);
 
 // ---- simple fork-join over [0, count) with std::thread (no OpenMP runtime needed) ----
 void parallel_for(int64_t count, const std::function<void(int64_t begin, int64_t end, int tid)> &fn,

@@ -37,6 +37,7 @@
 #include "mlnmf.h"
 #include "init.h"
 #include "consensus.h"
+#include "cophenet.h"
 
 using namespace vbnmf;
 
@@ -3348,12 +3349,22 @@ int consensus_count_row(vbnmf_consensus *c, hipStream_t stream)
 }  // namespace
 
 namespace vbnmf {
-int consensus_download(vbnmf_consensus *c, std::vector<uint8_t> &labels, int64_t &m, int32_t &runs, int32_t &unlabelled)
+int consensus_download(vbnmf_consensus *c, std::vector<uint8_t> &labels, int64_t &m, int32_t &runs, int32_t &unlabelled, int32_t *device)
 {
     if (int rc = consensus_use(c)) return rc;
+    if (device) *device = c->device;
     m = c->m; runs = c->runs; unlabelled = (int32_t)(c->h_sums[2] != 0);
     try { labels.resize((size_t)c->runs * c->m); } catch (const std::bad_alloc &) { return fail(VBNMF_ERR_OOM, "out of host memory for the label matrix"); }
     if (!labels.empty()) HIPCHECK(hipMemcpy(labels.data(), c->labels, labels.size(), hipMemcpyDeviceToHost));
+    return VBNMF_OK;
+}
+}  // namespace vbnmf
+
+namespace vbnmf {
+int coph_dev_use(int device)
+{
+    if (int rc = check_device(device)) return rc;
+    HIPCHECK(hipSetDevice(device));
     return VBNMF_OK;
 }
 }  // namespace vbnmf

@@ -144,7 +144,8 @@ def factorize(mat, ranks=2, nrun=20, randomize=False, nsmpl=1, verbose=2, progre
     The restarts draw their starts from the same stream in the same order either way.  ``consensus``: how dispersion and
     cophenetic (:218-230) are formed.  ``'pairs'``: the reference's O(m^2) pair vector on the host (NaN above ``MAX_PAIRS``
     pairs); ``'tables'``: from the runs' label vectors on the device (``Consensus``: contingency tables for the dispersion,
-    the distinct label tuples for the cophenetic; ``linkage`` 'average', 'single' or 'complete'; no ``store_connectivity``);
+    the distinct label tuples for the cophenetic -- agglomerated on the host up to 4096 of them, on the device up to 32768, NaN
+    past that; ``linkage`` 'average', 'single' or 'complete'; no ``store_connectivity``);
     None: ``'pairs'`` up to ``MAX_PAIRS`` pairs, ``'tables'`` above (NaN there without a device or under another ``linkage``).
     Returns ``MLResult``.
     """

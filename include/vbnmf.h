@@ -559,7 +559,8 @@ int vbnmf_consensus_labels(vbnmf_consensus *c, int32_t run, int32_t *ids);
  * group (>= 1).  method: "average", "single" or "complete".  coph = Pearson correlation of distance and cophenetic
  * distance over all m (m - 1) / 2 pairs of cells (within a group both are 0); NaN when either has no variance.
  * Nearest-neighbour chain on a G x G matrix: O(G^2) work and memory.  Ties: among equal nearest neighbours of a group the
- * chain takes the one it came from, else the lowest group number; a merged cluster keeps the lower number of its two parts. */
+ * chain takes the one it came from, else the lowest group number; a merged cluster keeps the lower number of its two parts.
+ * The sums over the pairs are long double; above 4096 groups (G^2 / 2 terms) they are compensated sums. */
 int vbnmf_cophenetic_grouped(int64_t G, int32_t R, const uint8_t *tuples, const int64_t *sizes, const char *method, double *coph);
 /* The same for the runs an accumulator holds: downloads the label matrix, numbers the distinct tuples by their first
  * cell, and calls the function above.  groups = G; if G > max_groups (<= 0: 4096, a 128 MB matrix) or a label was 0,
@@ -568,6 +569,31 @@ int vbnmf_consensus_cophenetic(vbnmf_consensus *c, const char *method, int64_t m
 /* Test hook: the grouped coefficient from real-valued group distances dist[G][G] (symmetric, zero diagonal) instead of
  * label tuples, so the agglomeration can be checked on tie-free input. */
 int vbnmf_test_cophenetic_dist(int64_t G, const double *dist, const int64_t *sizes, const char *method, double *coph);
+
+/* cophenet(conav / R, m, method) (R/factorize.R:69-78) in grouped form with the agglomeration on HIP device `device`
+ * (csrc/cophenet.h), for more groups than the host form is meant for.  Arguments and result as
+ * vbnmf_cophenetic_grouped; the dendrogram is the host's, merge for merge (the same rule on the same bits, ties
+ * included); the coefficient differs from the host's by the rounding of its sums only (per-merge terms in compensated
+ * double there, a long double walk over member pairs here).  Limits, each a status checked before anything is launched:
+ *   G >= 1 (G = 1: NaN), 1 <= R <= 65535, every size >= 1                                   VBNMF_ERR_BAD_ARG
+ *   G <= 32768: the kernel keeps its activity flags in LDS                                  VBNMF_ERR_BAD_ARG
+ *   cells^2 * R / 2 < 2^53, cells = sum of the sizes: the weighted distance sums stay exact VBNMF_ERR_BAD_ARG
+ *   no usable device                                                                        VBNMF_ERR_NO_DEVICE
+ *   device memory: 16 G^2 bytes (two G x G matrices of doubles: 17 GB at G = 32768); a failed allocation is
+ *   VBNMF_ERR_OOM with the byte count in the message.  Everything allocated is freed on every return path. */
+int vbnmf_cophenetic_grouped_device(int32_t device, int64_t G, int32_t R, const uint8_t *tuples, const int64_t *sizes, const char *method, double *coph);
+/* vbnmf_consensus_cophenetic (R/factorize.R:69-78) with the place of the agglomeration chosen: where = 0 host, 1 the
+ * accumulator's device, -1 by size (up to 4096 groups on the host, bit for bit as vbnmf_consensus_cophenetic; above, on
+ * the device).  The label tuples are grouped on the host either way.  coph = NaN if a label was 0, if G > max_groups
+ * (<= 0: 4096 for where = 0, else 32768), or if the device would have to serve more than 32768 groups. */
+int vbnmf_consensus_cophenetic_on(vbnmf_consensus *c, const char *method, int64_t max_groups, int32_t where, double *coph, int64_t *groups);
+/* Test hook (R/factorize.R:69-78): vbnmf_test_cophenetic_dist with the dendrogram as a further output, from the host
+ * core (where = 0) or the device path (where = 1; -1: by size, as above; `device` is ignored on the host).  merges:
+ * [G-1][2], per merge the number of the cluster kept (the lower) and of the cluster dropped; heights: [G-1]; either may
+ * be NULL.  On the device a non-finite distance is VBNMF_ERR_BAD_ARG, found before the launch; the limits of
+ * vbnmf_cophenetic_grouped_device hold with R = 1. */
+int vbnmf_test_cophenetic_trace(int32_t where, int32_t device, int64_t G, const double *dist, const int64_t *sizes, const char *method, double *coph,
+                                int64_t *merges, double *heights);
 
 /* vb_init(initializer = 'random') on the device (R/bayesian.R:111-115, 162-170): lw = ew ~ Gamma(shape aw, scale
  * bw/aw), lh = eh ~ Gamma(shape ah, scale bh/ah), dw = dh = 0, followed by what set_state does (a partitioned engine
