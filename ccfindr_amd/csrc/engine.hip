@@ -35,6 +35,7 @@
 #include "comm.h"
 #include "kernels.h"
 #include "mlnmf.h"
+#include "project.h"
 #include "init.h"
 #include "consensus.h"
 #include "cophenet.h"
@@ -3997,6 +3998,148 @@ int vbnmf_ml_update_csc(int64_t n, int64_t m, int32_t r, const int32_t *p, const
 {
     if (!w_in || !h_in) return fail(VBNMF_ERR_BAD_ARG, "w or h is NULL");
     return with_csc(n, m, r, p, i, x, [&](vbnmf_engine *e) { return ml_update_once(e, w_in, h_in, prior, gamma_a, gamma_b, w, h, lk); });
+}
+
+}  // extern "C"
+
+// ---- projection of new cells onto a fitted basis (project.h): no layout, no engine -- the column range's compressed columns,
+// the basis and the start go up once, one launch takes every cell to its own stop.
+namespace {
+
+thread_local double tl_project_kernel_ms = 0.0;
+
+struct ProjectDevice {
+    int64_t *colptr = nullptr;
+    int32_t *row = nullptr, *it = nullptr, *reason = nullptr;
+    double *val = nullptr, *W = nullptr, *cw = nullptr, *H = nullptr, *lk = nullptr;
+    unsigned int *ticket = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    bool queued = false;
+    int caller_device = -1;               // the device that was current when the call came in: current again when it returns
+    ~ProjectDevice()
+    {
+        if (queued) (void)hipStreamSynchronize(nullptr);
+        dev_free(colptr); dev_free(row); dev_free(it); dev_free(reason); dev_free(val); dev_free(W); dev_free(cw); dev_free(H);
+        dev_free(lk); dev_free(ticket);
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+        if (caller_device >= 0) (void)hipSetDevice(caller_device);
+    }
+};
+
+int project_columns(const Matrix &M, int64_t cb, int64_t ce, int32_t r, const double *w, double *h, int32_t prior, double ga, double gb,
+                    int32_t max_it, double tol, int32_t device, double *lk_cell, int32_t *it_cell, int32_t *reason_cell)
+{
+    const int64_t n = M.n, nc = ce - cb;
+    const int R = padded_rank(r);
+    ProjectDevice D;
+    (void)hipGetDevice(&D.caller_device);
+    HIPCHECK(hipSetDevice(device));
+    // the basis by rows, R wide (what a cell gathers), colSums(w) (R/factorize.R:9; every column added gene by gene, in order)
+    // and the start, cell by cell -- on the library's host threads
+    std::vector<double> Wp((size_t)n * R, 0.0), cw((size_t)R, 0.0), Hp((size_t)nc * R, 0.0);
+    parallel_for(n, [&](int64_t b, int64_t e, int) {
+        for (int64_t i = b; i < e; i++)
+            for (int k = 0; k < r; k++) Wp[(size_t)i * R + k] = w[(size_t)k * n + i];
+    });
+    parallel_for(r, [&](int64_t b, int64_t e, int) {
+        for (int64_t k = b; k < e; k++) {
+            double s = 0.0;
+            for (int64_t i = 0; i < n; i++) s += w[(size_t)k * n + i];
+            cw[k] = s;
+        }
+    });
+    parallel_for(nc, [&](int64_t b, int64_t e, int) {
+        for (int64_t j = b; j < e; j++)
+            for (int k = 0; k < r; k++) Hp[(size_t)j * R + k] = h[(size_t)j * r + k];
+    });
+    const int64_t e0 = M.colptr[cb], ne = M.colptr[ce] - e0;
+
+    if (int rc = dev_alloc(&D.colptr, (size_t)nc + 1)) return rc;
+    if (int rc = dev_alloc(&D.row, (size_t)ne)) return rc;
+    if (int rc = dev_alloc(&D.val, (size_t)ne)) return rc;
+    if (int rc = dev_alloc(&D.W, Wp.size())) return rc;
+    if (int rc = dev_alloc(&D.cw, cw.size())) return rc;
+    if (int rc = dev_alloc(&D.H, Hp.size())) return rc;
+    if (int rc = dev_alloc(&D.lk, (size_t)nc)) return rc;
+    if (int rc = dev_alloc(&D.it, (size_t)nc)) return rc;
+    if (int rc = dev_alloc(&D.reason, (size_t)nc)) return rc;
+    if (int rc = dev_alloc(&D.ticket, 1)) return rc;
+    HIPCHECK(hipMemcpy(D.colptr, M.colptr.data() + cb, ((size_t)nc + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
+    if (ne > 0) {
+        HIPCHECK(hipMemcpy(D.row, M.row.data() + e0, (size_t)ne * sizeof(int32_t), hipMemcpyHostToDevice));
+        HIPCHECK(hipMemcpy(D.val, M.val.data() + e0, (size_t)ne * sizeof(double), hipMemcpyHostToDevice));
+    }
+    HIPCHECK(hipMemcpy(D.W, Wp.data(), Wp.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHECK(hipMemcpy(D.cw, cw.data(), cw.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHECK(hipMemcpy(D.H, Hp.data(), Hp.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHECK(hipMemsetAsync(D.ticket, 0, sizeof(unsigned int), nullptr));
+
+    ProjectArgs a;
+    a.colptr = D.colptr; a.base = e0; a.row = D.row; a.val = D.val; a.W = D.W; a.cw = D.cw; a.H = D.H; a.lk = D.lk; a.it = D.it;
+    a.reason = D.reason; a.ticket = D.ticket; a.ncell = nc; a.r = r; a.prior = prior ? 1 : 0; a.max_it = max_it;
+    a.ga = ga; a.gb = gb; a.tol = tol; a.eps = 2.220446049250313e-16;
+    // a persistent grid: as many workgroups as a CU holds threads for (the kernel's few KB of LDS do not bound it)
+    int cus = 0;
+    HIPCHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
+    if (cus <= 0) cus = 256;
+    const unsigned grid = (unsigned)std::min<int64_t>(nc, (int64_t)cus * (2048 / kProjThreads));
+    HIPCHECK(hipEventCreate(&D.ev0));
+    HIPCHECK(hipEventCreate(&D.ev1));
+    HIPCHECK(hipEventRecord(D.ev0, nullptr));
+    D.queued = true;
+    int rc = with_rank(R, [&](auto rt) {
+        hipLaunchKernelGGL((k_project<rt()>), dim3(grid), dim3(kProjThreads), 0, nullptr, a);
+        HIPCHECK(hipGetLastError());
+        return (int)VBNMF_OK;
+    });
+    if (rc) return rc;
+    HIPCHECK(hipEventRecord(D.ev1, nullptr));
+    HIPCHECK(hipMemcpy(Hp.data(), D.H, Hp.size() * sizeof(double), hipMemcpyDeviceToHost));
+    float ms = 0.0f;
+    HIPCHECK(hipEventElapsedTime(&ms, D.ev0, D.ev1));
+    tl_project_kernel_ms = ms;
+    parallel_for(nc, [&](int64_t b, int64_t e, int) {
+        for (int64_t j = b; j < e; j++)
+            for (int k = 0; k < r; k++) h[(size_t)j * r + k] = Hp[(size_t)j * R + k];
+    });
+    if (lk_cell) HIPCHECK(hipMemcpy(lk_cell, D.lk, (size_t)nc * sizeof(double), hipMemcpyDeviceToHost));
+    if (it_cell) HIPCHECK(hipMemcpy(it_cell, D.it, (size_t)nc * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (reason_cell) HIPCHECK(hipMemcpy(reason_cell, D.reason, (size_t)nc * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return VBNMF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vbnmf_matrix_project(const vbnmf_matrix *X, int64_t col_begin, int64_t col_end, int32_t r, const double *w, double *h,
+                         int32_t prior, double gamma_a, double gamma_b, int32_t max_it, double tol, int32_t device,
+                         double *lk_cell, int32_t *it_cell, int32_t *reason_cell)
+{
+    if (!X || !w || !h) return fail(VBNMF_ERR_BAD_ARG, "NULL argument");
+    if (X->M.shell) return fail(VBNMF_ERR_BAD_ARG, "a shell matrix holds no entries: project needs the compressed columns");
+    if (r < 1 || r > VBNMF_MAX_RANK) return fail(VBNMF_ERR_BAD_ARG, "rank %d is outside [1, %d]", r, VBNMF_MAX_RANK);
+    if (col_begin < 0 || col_end > X->M.m || col_begin >= col_end)
+        return fail(VBNMF_ERR_BAD_ARG, "column range [%lld, %lld) is empty or outside the matrix's %lld columns", (long long)col_begin,
+                    (long long)col_end, (long long)X->M.m);
+    if (max_it < 1) return fail(VBNMF_ERR_BAD_ARG, "max_it must be >= 1");
+    if (int rc = check_device(device)) return rc;
+    try {
+        return project_columns(X->M, col_begin, col_end, r, w, h, prior, gamma_a, gamma_b, max_it, tol, device, lk_cell, it_cell, reason_cell);
+    } catch (const std::bad_alloc &) {
+        return fail(VBNMF_ERR_OOM, "out of host memory for the projection's staging arrays");
+    } catch (const std::exception &ex) {
+        return fail(VBNMF_ERR_HIP, "vbnmf_matrix_project: %s", ex.what());
+    }
+}
+
+int vbnmf_project_info(int32_t r, int32_t *pass_entries, double *last_kernel_ms)
+{
+    if (r < 1 || r > VBNMF_MAX_RANK) return fail(VBNMF_ERR_BAD_ARG, "rank %d is outside [1, %d]", r, VBNMF_MAX_RANK);
+    if (pass_entries) *pass_entries = proj_pass_entries(padded_rank(r));
+    if (last_kernel_ms) *last_kernel_ms = tl_project_kernel_ms;
+    return VBNMF_OK;
 }
 
 }  // extern "C"

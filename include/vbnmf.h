@@ -505,6 +505,29 @@ int vbnmf_ml_update_csc(int64_t n, int64_t m, int32_t r, const int32_t *p, const
                         int32_t prior, double gamma_a, double gamma_b,
                         double *w, double *h, double *lk);
 
+/* ---------------------------------------------------------------------------------
+ * Projection of new cells onto a fitted basis: the H half of nmf_updateR (R/factorize.R:8-15) iterated with w
+ * untouched, every cell (column) on its own, until that cell's likelihood (:40-49, this column, not divided by n m)
+ * meets factorize()'s test abs(lkold - lk) < Tol * abs(lkold) (:208; lkold = -Inf before the first step):
+ *   h_kj <- max((h_kj * sum_i w_ik x_ij / (w h)_ij [+ gamma_a - 1]) / (colSums(w)_k [+ gamma_a / gamma_b]), DBL_EPSILON)
+ * Reads the handle's canonical compressed columns (what vbnmf_matrix_csc exposes) for cells [col_begin, col_end): no layout
+ * is cut and no engine is created; the column range, the basis and the start go to HIP device `device` once and ONE launch
+ * takes every cell to its stop (csrc/project.h).  w: n x r column-major, non-negative; h: r x (col_end - col_begin)
+ * column-major, in: the start, out: the result.  lk_cell, it_cell, reason_cell (each may be NULL), one value per cell: its
+ * likelihood, its iteration count and why it stopped -- 1 converged, 3 NaN likelihood, 4 max_it reached.  A cell's result
+ * does not depend on the other cells of the call, bit for bit.  An all-zero column is legal here (its h goes to DBL_EPSILON,
+ * or to the prior's mode), and so is an all-zero gene row.
+ * VBNMF_ERR_BAD_ARG: a shell matrix (it holds no columns), r < 1 or > VBNMF_MAX_RANK, an empty or outside column range,
+ * NULL w or h, max_it < 1; VBNMF_ERR_NO_DEVICE: no gfx950 device. */
+int vbnmf_matrix_project(const vbnmf_matrix *X, int64_t col_begin, int64_t col_end, int32_t r,
+                         const double *w, double *h, int32_t prior, double gamma_a, double gamma_b,
+                         int32_t max_it, double tol, int32_t device,
+                         double *lk_cell, int32_t *it_cell, int32_t *reason_cell);
+/* Constants of that kernel at rank r (host only; any out pointer may be NULL): the stored entries of a cell that the
+ * workgroup's threads take in one pass (256 up to rank 32, 128 up to 64, 64 above: longer columns go round again), and the
+ * kernel time in ms of the calling thread's most recent vbnmf_matrix_project. */
+int vbnmf_project_info(int32_t r, int32_t *pass_entries, double *last_kernel_ms);
+
 /* Cluster of every cell from the coefficients the engine holds:
  * ids[j] = which.max(h[, j])[1], 1-based, first maximum on ties (R/factorize.R:55-56 inside
  * connectivity(), R/utils.R:906 cluster_id); h = the ML coefficient matrix, or E[H] of a VB
