@@ -176,6 +176,10 @@ SIGNATURES = {
     "vbnmf_layout_destroy": (None, [_VP]),
     "vbnmf_test_special_host": (ctypes.c_int, [_I32, _I64, c_double_p, c_double_p]),
     "vbnmf_test_special_device": (ctypes.c_int, [_I32, _I64, c_double_p, c_double_p]),
+    "vbnmf_test_svd_gram": (ctypes.c_int, [_I32, _I64, c_double_p, c_double_p]),
+    "vbnmf_test_svd_small": (ctypes.c_int, [_I32, _I32, _I32, _I32, c_double_p, _D, c_double_p, c_double_p, c_double_p, c_double_p, c_int32_p]),
+    "vbnmf_test_svd_apply": (ctypes.c_int, [_I32, _I64, c_double_p, c_double_p, _I32, c_double_p]),
+    "vbnmf_test_svd_normal": (ctypes.c_int, [_I64, _I32, _I32, ctypes.c_uint64, c_double_p]),
     "vbnmf_test_stream_sleep": (ctypes.c_int, [_VP, _D]),
     "vbnmf_test_hash_bytes": (ctypes.c_uint64, [_VP, _I64, ctypes.c_uint64]),
 }

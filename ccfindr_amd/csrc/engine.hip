@@ -3725,6 +3725,162 @@ int vbnmf_test_special_device(int32_t kind, int64_t n, const double *x, double *
     return rc;
 }
 
+}  // extern "C"
+
+namespace {
+
+// What a dense-SVD test hook holds on the device (and pinned): released on every return path.
+struct HookBuffers {
+    std::vector<void *> dev;
+    void *pinned = nullptr;
+    ~HookBuffers()
+    {
+        for (void *p : dev) dev_free(p);
+        if (pinned) (void)hipHostFree(pinned);
+    }
+    int alloc(double **p, size_t count)
+    {
+        if (int rc = dev_alloc(p, count)) return rc;
+        dev.push_back(*p);
+        return VBNMF_OK;
+    }
+    int upload(double **p, const double *src, size_t count)
+    {
+        if (int rc = alloc(p, count)) return rc;
+        HIPCHECK(hipMemcpy(*p, src, count * sizeof(double), hipMemcpyHostToDevice));
+        return VBNMF_OK;
+    }
+};
+
+int download(double *dst, const double *src, size_t count)
+{
+    HIPCHECK(hipMemcpy(dst, src, count * sizeof(double), hipMemcpyDeviceToHost));
+    return VBNMF_OK;
+}
+
+// R must be a width the dense kernels are instantiated for
+int hook_width(int32_t R)
+{
+    return with_rank_up_to_64(R, [](auto) { return (int)VBNMF_OK; });
+}
+
+// device 0 for a test hook, looked for after the arguments have passed
+int hook_device()
+{
+    if (int rc = check_device(0)) return rc;
+    HIPCHECK(hipSetDevice(0));
+    return VBNMF_OK;
+}
+
+constexpr int64_t kHookMaxRows = (int64_t)1 << 24;           // 8 GB of doubles at R = 64: a test has no use for more
+
+}  // namespace
+
+extern "C" {
+
+// ---- test hooks into the dense kernels of the truncated SVD (init.h), each with the launch geometry of
+// vbnmf_engine_svd: upload, one launch of the product's kernel on the null stream, download
+int vbnmf_test_svd_gram(int32_t R, int64_t N, const double *A, double *gp)
+{
+    if (!A || !gp || N < 1 || N > kHookMaxRows) return fail(VBNMF_ERR_BAD_ARG, "NULL argument or N outside [1, 2^24]");
+    if (int rc = hook_width(R)) return rc;
+    if (int rc = hook_device()) return rc;
+    HookBuffers hb;
+    double *dA = nullptr, *dgp = nullptr;
+    const size_t RR = (size_t)R * R;
+    if (int rc = hb.upload(&dA, A, (size_t)N * R)) return rc;
+    if (int rc = hb.alloc(&dgp, (size_t)kGramBlocks * RR)) return rc;
+    HIPCHECK(hipMemset(dgp, 0xFF, (size_t)kGramBlocks * RR * sizeof(double)));       // NaN: the kernel writes every partial
+    if (int rc = with_rank_up_to_64(R, [&](auto rt) {
+            hipLaunchKernelGGL(k_gram<rt()>, dim3(kGramBlocks), dim3(1024), 0, nullptr, (const double *)dA, N, dgp);
+            HIPCHECK(hipGetLastError());
+            return (int)VBNMF_OK;
+        })) return rc;
+    return download(gp, dgp, (size_t)kGramBlocks * RR);
+}
+
+int vbnmf_test_svd_small(int32_t R, int32_t k, int32_t mode, int32_t nb, const double *gp, double seq, double *S, double *S2,
+                         double *vals, double *vals_host, int32_t *status)
+{
+    if (!gp || !S || !vals || !status) return fail(VBNMF_ERR_BAD_ARG, "NULL argument");
+    if (mode != 0 && mode != 1) return fail(VBNMF_ERR_BAD_ARG, "mode must be 0 (Cholesky) or 1 (Jacobi)");
+    if (nb < 1 || nb > 65536) return fail(VBNMF_ERR_BAD_ARG, "nb must be in [1, 65536]");
+    if (int rc = hook_width(R)) return rc;
+    if (k < 1 || k > R) return fail(VBNMF_ERR_BAD_ARG, "k must be in [1, R]");
+    if (int rc = hook_device()) return rc;
+    HookBuffers hb;
+    const size_t RR = (size_t)R * R;
+    double *dgp = nullptr, *dS = nullptr, *dS2 = nullptr, *dvals = nullptr, *dstat = nullptr, *hv = nullptr, *hv_dev = nullptr;
+    if (int rc = hb.upload(&dgp, gp, (size_t)nb * RR)) return rc;
+    if (int rc = hb.alloc(&dS, RR)) return rc;
+    if (S2) { if (int rc = hb.alloc(&dS2, RR)) return rc; }
+    if (int rc = hb.alloc(&dvals, (size_t)R)) return rc;
+    if (int rc = hb.alloc(&dstat, 1)) return rc;                               // (8 bytes: the status is its first 4)
+    HIPCHECK(hipMemset(dS, 0xFF, RR * sizeof(double)));
+    if (dS2) HIPCHECK(hipMemset(dS2, 0xFF, RR * sizeof(double)));
+    HIPCHECK(hipMemset(dvals, 0, (size_t)R * sizeof(double)));
+    HIPCHECK(hipMemset(dstat, 0, sizeof(double)));
+    if (vals_host) {                                                           // pinned and device-visible, as the engine's history block
+        hipError_t he = hipHostMalloc(&hb.pinned, ((size_t)R + 2) * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent);
+        if (he != hipSuccess) { (void)hipGetLastError(); hb.pinned = nullptr; return fail(VBNMF_ERR_OOM, "pinned values block: %s", hipGetErrorString(he)); }
+        hv = static_cast<double *>(hb.pinned);
+        for (int q = 0; q <= R; q++) hv[q] = 0.0;
+        HIPCHECK(hipHostGetDevicePointer((void **)&hv_dev, hv, 0));
+    }
+    if (int rc = with_rank_up_to_64(R, [&](auto rt) {
+            hipLaunchKernelGGL(k_small<rt()>, dim3(1), dim3(1024), 0, nullptr, (const double *)dgp, (int)nb, (int)k, (int)mode, dS, dS2, dvals,
+                               hv_dev, seq, reinterpret_cast<int32_t *>(dstat));
+            HIPCHECK(hipGetLastError());
+            return (int)VBNMF_OK;
+        })) return rc;
+    HIPCHECK(hipDeviceSynchronize());
+    if (int rc = download(S, dS, RR)) return rc;
+    if (S2) { if (int rc = download(S2, dS2, RR)) return rc; }
+    if (int rc = download(vals, dvals, (size_t)R)) return rc;
+    HIPCHECK(hipMemcpy(status, dstat, sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (vals_host) { const volatile double *v = hv; for (int q = 0; q <= R; q++) vals_host[q] = v[q]; }
+    return VBNMF_OK;
+}
+
+int vbnmf_test_svd_apply(int32_t R, int64_t N, const double *A, const double *S, int32_t in_place, double *B)
+{
+    if (!A || !S || !B || N < 1 || N > kHookMaxRows) return fail(VBNMF_ERR_BAD_ARG, "NULL argument or N outside [1, 2^24]");
+    if (int rc = hook_width(R)) return rc;
+    if (int rc = hook_device()) return rc;
+    HookBuffers hb;
+    double *dA = nullptr, *dS = nullptr, *dB = nullptr;
+    if (int rc = hb.upload(&dA, A, (size_t)N * R)) return rc;
+    if (int rc = hb.upload(&dS, S, (size_t)R * R)) return rc;
+    if (in_place) dB = dA;
+    else {
+        if (int rc = hb.alloc(&dB, (size_t)N * R)) return rc;
+        HIPCHECK(hipMemset(dB, 0xFF, (size_t)N * R * sizeof(double)));
+    }
+    if (int rc = with_rank_up_to_64(R, [&](auto rt) {
+            hipLaunchKernelGGL(k_apply<rt()>, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, nullptr, (const double *)dA, (const double *)dS, N, dB);
+            HIPCHECK(hipGetLastError());
+            return (int)VBNMF_OK;
+        })) return rc;
+    return download(B, dB, (size_t)N * R);
+}
+
+int vbnmf_test_svd_normal(int64_t nmaj, int32_t r, int32_t R, uint64_t seed, double *g)
+{
+    if (!g || nmaj < 1 || nmaj > kHookMaxRows) return fail(VBNMF_ERR_BAD_ARG, "NULL argument or nmaj outside [1, 2^24]");
+    if (int rc = hook_width(R)) return rc;
+    if (r < 1 || r > R) return fail(VBNMF_ERR_BAD_ARG, "r must be in [1, R]");
+    if (int rc = hook_device()) return rc;
+    HookBuffers hb;
+    double *dg = nullptr;
+    const int64_t cnt = nmaj * R;
+    if (int rc = hb.alloc(&dg, (size_t)cnt)) return rc;
+    HIPCHECK(hipMemset(dg, 0xFF, (size_t)cnt * sizeof(double)));
+    hipLaunchKernelGGL(k_normal_init, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, nullptr, dg, nmaj, (int)r, (int)R, (uint32_t)seed,
+                       (uint32_t)(seed >> 32));
+    HIPCHECK(hipGetLastError());
+    return download(g, dg, (size_t)cnt);
+}
+
 // Test hook: a host function that sleeps `seconds` is enqueued on the engine's stream, so everything queued behind it
 // waits that long without the GPU being busy or hung (tests/test_gpu_timeouts.py: the bounded waits).
 static void sleep_host_fn(void *arg)

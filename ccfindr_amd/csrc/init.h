@@ -239,18 +239,27 @@ __global__ __launch_bounds__(1024) void k_small(const double *__restrict__ gp, i
         return;
     }
     // cyclic Jacobi on the k x k symmetric G; rotations applied by the 32 lanes of row 0 of the block (lane j: columns j, j + 32)
-    __shared__ double off;
+    // Stopping rule: sum over p < q of G[p][q]^2 <= 1e-30 tr^2, tr = sum |G[p][p]|, on G 2^-ex, ex = the binary exponent
+    // of the largest |G[p][p]|.  Scaling by a power of two is exact, so the test is the same for G and for any power-of-two
+    // multiple of G whose entries are finite normal numbers, bit for bit -- neither the squares nor the sum of the diagonal
+    // can overflow, and what vanishes is below 1e-30 tr^2 anyway.  (The squares of the unscaled entries overflow or vanish
+    // from |G| ~ 1e+-154 on, and the rule then held before the first sweep.)
+    __shared__ int done;
     for (int sweep = 0; sweep < 30; sweep++) {
         __syncthreads();
         if (threadIdx.x == 0) {
-            double o = 0.0;
-            for (int p = 0; p < k; p++) for (int q = p + 1; q < k; q++) o += G[p][q] * G[p][q];
-            off = o;
+            double dmax = 0.0;
+            for (int p = 0; p < k; p++) dmax = fmax(dmax, fabs(G[p][p]));
+            int ex = 0;
+            (void)frexp(dmax, &ex);                           // (0 for dmax = 0)
+            double tr = 0.0, o = 0.0;
+            for (int p = 0; p < k; p++) tr += ldexp(fabs(G[p][p]), -ex);
+            for (int p = 0; p < k; p++)
+                for (int q = p + 1; q < k; q++) { const double rel = ldexp(G[p][q], -ex); o += rel * rel; }
+            done = o <= 1e-30 * tr * tr;
         }
         __syncthreads();
-        double tr = 0.0;
-        for (int p = 0; p < k; p++) tr += fabs(G[p][p]);
-        if (off <= 1e-30 * tr * tr) break;
+        if (done) break;
         for (int p = 0; p < k - 1; p++)
             for (int q = p + 1; q < k; q++) {
                 const double apq = G[p][q];

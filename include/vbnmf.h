@@ -710,6 +710,24 @@ void vbnmf_layout_destroy(vbnmf_layout *L);
  * --------------------------------------------------------------------------------- */
 int vbnmf_test_special_host(int32_t kind, int64_t n, const double *x, double *y);
 int vbnmf_test_special_device(int32_t kind, int64_t n, const double *x, double *y);
+/* Test hooks into the dense kernels of the device-resident truncated SVD (csrc/init.h: k_gram, k_small, k_apply,
+ * k_normal_init), one launch each with the geometry vbnmf_engine_svd uses, on device 0: host arrays are uploaded, the
+ * product's own kernel runs, the results are downloaded (tests/test_gpu_svd_dense.py).  R is the padded width of the
+ * blocks, one of the widths the kernels are compiled for (2..32 by 2, 40..64 by 8); anything else, a NULL array or a
+ * count outside its range is VBNMF_ERR_BAD_ARG, found before a device is looked for.  Everything allocated is freed on
+ * every return path.
+ *   gram:   A[N][R] in, the raw block partials gp[256][R*R] of t(A) A out (the caller adds them); all R columns count.
+ *   small:  gp[nb][R*R] in (nb = 1: an exact G), k columns in use (1 <= k <= R), mode 0 = Cholesky / 1 = Jacobi.  Out:
+ *           S[R*R], S2[R*R] (mode 1; may be NULL), vals[R], status (1 = not positive definite, mode 0), and, if not
+ *           NULL, vals_host[R+1]: what the kernel wrote through a pinned device-visible block -- the values and, in
+ *           slot R, the sequence number `seq` (mode 1).
+ *   apply:  B[N][R] = A[N][R] S[R*R]; in_place != 0 runs the kernel with B = A on the device.
+ *   normal: the standard normal block g[nmaj][R] of the range finder, columns r..R-1 zero, keyed by `seed`. */
+int vbnmf_test_svd_gram(int32_t R, int64_t N, const double *A, double *gp);
+int vbnmf_test_svd_small(int32_t R, int32_t k, int32_t mode, int32_t nb, const double *gp, double seq, double *S, double *S2,
+                         double *vals, double *vals_host, int32_t *status);
+int vbnmf_test_svd_apply(int32_t R, int64_t N, const double *A, const double *S, int32_t in_place, double *B);
+int vbnmf_test_svd_normal(int64_t nmaj, int32_t r, int32_t R, uint64_t seed, double *g);
 /* Test hook for the bounded waits: enqueues a host function that sleeps `seconds` (<= 60) on the engine's stream, so
  * the steps queued behind it are late without the GPU being busy.  The waits of vbnmf_engine_step / _run / _ml_run are
  * bounded by VBNMF_WAIT_TIMEOUT_S (seconds of wall clock, default 300): past it the call returns VBNMF_ERR_HIP with a

@@ -59,6 +59,17 @@ def gamma_draws(a, scale, element, factor, seed):
     return g * scale
 
 
+def normal_draws(nmaj, r, seed):
+    """The [nmaj, r] standard normal block of the truncated SVD's range finder (k_normal_init): element el = M r + k uses
+    the single counter (el lo, el hi, 7, 0); Box-Muller's cosine branch from the uniforms of words (0, 1) and (2, 3)."""
+    el = np.arange(nmaj, dtype=np.uint64)[:, None] * np.uint64(r) + np.arange(r, dtype=np.uint64)[None, :]
+    el = el.ravel()
+    k0, k1 = np.uint64(seed & 0xFFFFFFFF), np.uint64(seed >> 32)
+    q = philox4x32(el & _MASK, el >> _S32, np.full(el.size, 7, dtype=np.uint64), np.zeros(el.size, dtype=np.uint64), k0, k1)
+    x = np.sqrt(-2.0 * np.log(u53(q[0], q[1]))) * np.cos(6.283185307179586476925 * u53(q[2], q[3]))
+    return x.reshape(nmaj, r)
+
+
 def random_state(n, m, r, hyper, seed, col_begin=0):
     """(W [n, r], H [r, m]) the engine's ``random_state(hyper, seed)`` draws; H holds the cells col_begin .. col_begin + m - 1."""
     i = np.arange(n, dtype=np.uint64)[:, None] * np.uint64(r) + np.arange(r, dtype=np.uint64)[None, :]
