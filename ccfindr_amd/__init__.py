@@ -13,7 +13,7 @@ from .bayesian import (VBResult, hyper_update, vb_factorize, vb_init, vb_iterate
 from .io import CountData, read_10x, remove_zeros, write_10x  # noqa: F401
 from .post import cluster_id  # noqa: F401
 from .factorize import MLResult, factorize, likelihood, nmf_update  # noqa: F401
-from .project import Projection, project  # noqa: F401
+from .project import Projection, VBProjection, posterior_basis, project, vb_project  # noqa: F401
 from .consensus import Consensus, cophenetic_grouped  # noqa: F401
 
 __version__ = "0.1.0"

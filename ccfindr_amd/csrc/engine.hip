@@ -36,6 +36,7 @@
 #include "kernels.h"
 #include "mlnmf.h"
 #include "project.h"
+#include "vbproject.h"
 #include "init.h"
 #include "consensus.h"
 #include "cophenet.h"
@@ -4168,6 +4169,7 @@ struct ProjectDevice {
     int64_t *colptr = nullptr;
     int32_t *row = nullptr, *it = nullptr, *reason = nullptr;
     double *val = nullptr, *W = nullptr, *cw = nullptr, *H = nullptr, *lk = nullptr;
+    double *eh = nullptr, *dh = nullptr;  // (the VB projection's further results)
     unsigned int *ticket = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool queued = false;
@@ -4176,7 +4178,7 @@ struct ProjectDevice {
     {
         if (queued) (void)hipStreamSynchronize(nullptr);
         dev_free(colptr); dev_free(row); dev_free(it); dev_free(reason); dev_free(val); dev_free(W); dev_free(cw); dev_free(H);
-        dev_free(lk); dev_free(ticket);
+        dev_free(lk); dev_free(eh); dev_free(dh); dev_free(ticket);
         if (ev0) (void)hipEventDestroy(ev0);
         if (ev1) (void)hipEventDestroy(ev1);
         if (caller_device >= 0) (void)hipSetDevice(caller_device);
@@ -4265,6 +4267,107 @@ int project_columns(const Matrix &M, int64_t cb, int64_t ce, int32_t r, const do
     return VBNMF_OK;
 }
 
+// ---- the same for a VB fit's posterior basis (vbproject.h): the table lw | lw log lw by rows, colSums(ew) and the start go
+// up once, one launch takes every cell to its own stop.
+thread_local double tl_vb_project_kernel_ms = 0.0;
+
+int vb_project_columns(const Matrix &M, int64_t cb, int64_t ce, int32_t r, const double *lw, const double *ew, double ah, double bh,
+                       double fudge, double *lh, double *eh, double *dh, int32_t max_it, double tol, int32_t device, double *ev_cell,
+                       int32_t *it_cell, int32_t *reason_cell)
+{
+    const int64_t n = M.n, nc = ce - cb;
+    const int R = padded_rank(r);
+    ProjectDevice D;
+    (void)hipGetDevice(&D.caller_device);
+    HIPCHECK(hipSetDevice(device));
+    // what a cell gathers per gene, 2 R wide: lw_i. | (lw log lw)_i. (R/bayesian.R:90; padding columns 0), colSums(ew) (:80;
+    // every column added gene by gene, in order) and the start, cell by cell -- on the library's host threads
+    std::vector<double> Tp((size_t)n * 2 * R, 0.0), cew((size_t)R, 0.0), Hp((size_t)nc * R, 0.0);
+    parallel_for(n, [&](int64_t b, int64_t e, int) {
+        for (int64_t i = b; i < e; i++)
+            for (int k = 0; k < r; k++) {
+                const double v = lw[(size_t)k * n + i];
+                Tp[(size_t)i * 2 * R + k] = v;
+                Tp[(size_t)i * 2 * R + R + k] = v * std::log(v);
+            }
+    });
+    parallel_for(r, [&](int64_t b, int64_t e, int) {
+        for (int64_t k = b; k < e; k++) {
+            double s = 0.0;
+            for (int64_t i = 0; i < n; i++) s += ew[(size_t)k * n + i];
+            cew[k] = s;
+        }
+    });
+    parallel_for(nc, [&](int64_t b, int64_t e, int) {
+        for (int64_t j = b; j < e; j++)
+            for (int k = 0; k < r; k++) Hp[(size_t)j * R + k] = lh[(size_t)j * r + k];
+    });
+    const int64_t e0 = M.colptr[cb], ne = M.colptr[ce] - e0;
+
+    if (int rc = dev_alloc(&D.colptr, (size_t)nc + 1)) return rc;
+    if (int rc = dev_alloc(&D.row, (size_t)ne)) return rc;
+    if (int rc = dev_alloc(&D.val, (size_t)ne)) return rc;
+    if (int rc = dev_alloc(&D.W, Tp.size())) return rc;
+    if (int rc = dev_alloc(&D.cw, cew.size())) return rc;
+    if (int rc = dev_alloc(&D.H, Hp.size())) return rc;
+    if (int rc = dev_alloc(&D.eh, Hp.size())) return rc;
+    if (int rc = dev_alloc(&D.dh, Hp.size())) return rc;
+    if (int rc = dev_alloc(&D.lk, (size_t)nc)) return rc;
+    if (int rc = dev_alloc(&D.it, (size_t)nc)) return rc;
+    if (int rc = dev_alloc(&D.reason, (size_t)nc)) return rc;
+    if (int rc = dev_alloc(&D.ticket, 1)) return rc;
+    HIPCHECK(hipMemcpy(D.colptr, M.colptr.data() + cb, ((size_t)nc + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
+    if (ne > 0) {
+        HIPCHECK(hipMemcpy(D.row, M.row.data() + e0, (size_t)ne * sizeof(int32_t), hipMemcpyHostToDevice));
+        HIPCHECK(hipMemcpy(D.val, M.val.data() + e0, (size_t)ne * sizeof(double), hipMemcpyHostToDevice));
+    }
+    HIPCHECK(hipMemcpy(D.W, Tp.data(), Tp.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHECK(hipMemcpy(D.cw, cew.data(), cew.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHECK(hipMemcpy(D.H, Hp.data(), Hp.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHECK(hipMemsetAsync(D.ticket, 0, sizeof(unsigned int), nullptr));
+
+    VbProjectArgs a;
+    a.colptr = D.colptr; a.base = e0; a.row = D.row; a.val = D.val; a.T = D.W; a.cew = D.cw; a.LH = D.H; a.EH = D.eh; a.DH = D.dh;
+    a.ev = D.lk; a.it = D.it; a.reason = D.reason; a.ticket = D.ticket; a.ncell = nc; a.r = r; a.max_it = max_it;
+    a.ah = ah; a.bh = bh; a.tol = tol; a.fudge = fudge;
+    // a persistent grid, as project_columns'
+    int cus = 0;
+    HIPCHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
+    if (cus <= 0) cus = 256;
+    const unsigned grid = (unsigned)std::min<int64_t>(nc, (int64_t)cus * (2048 / kProjThreads));
+    HIPCHECK(hipEventCreate(&D.ev0));
+    HIPCHECK(hipEventCreate(&D.ev1));
+    HIPCHECK(hipEventRecord(D.ev0, nullptr));
+    D.queued = true;
+    int rc = with_rank(R, [&](auto rt) {
+        hipLaunchKernelGGL((k_vb_project<rt()>), dim3(grid), dim3(kProjThreads), 0, nullptr, a);
+        HIPCHECK(hipGetLastError());
+        return (int)VBNMF_OK;
+    });
+    if (rc) return rc;
+    HIPCHECK(hipEventRecord(D.ev1, nullptr));
+    std::vector<double> back(Hp.size());
+    double *const outs[3] = {lh, eh, dh};
+    const double *const srcs[3] = {D.H, D.eh, D.dh};
+    for (int q = 0; q < 3; q++) {
+        if (!outs[q]) continue;
+        HIPCHECK(hipMemcpy(back.data(), srcs[q], back.size() * sizeof(double), hipMemcpyDeviceToHost));
+        double *out = outs[q];
+        parallel_for(nc, [&](int64_t b, int64_t e, int) {
+            for (int64_t j = b; j < e; j++)
+                for (int k = 0; k < r; k++) out[(size_t)j * r + k] = back[(size_t)j * R + k];
+        });
+    }
+    float ms = 0.0f;
+    HIPCHECK(hipEventSynchronize(D.ev1));
+    HIPCHECK(hipEventElapsedTime(&ms, D.ev0, D.ev1));
+    tl_vb_project_kernel_ms = ms;
+    if (ev_cell) HIPCHECK(hipMemcpy(ev_cell, D.lk, (size_t)nc * sizeof(double), hipMemcpyDeviceToHost));
+    if (it_cell) HIPCHECK(hipMemcpy(it_cell, D.it, (size_t)nc * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (reason_cell) HIPCHECK(hipMemcpy(reason_cell, D.reason, (size_t)nc * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return VBNMF_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -4295,6 +4398,37 @@ int vbnmf_project_info(int32_t r, int32_t *pass_entries, double *last_kernel_ms)
     if (r < 1 || r > VBNMF_MAX_RANK) return fail(VBNMF_ERR_BAD_ARG, "rank %d is outside [1, %d]", r, VBNMF_MAX_RANK);
     if (pass_entries) *pass_entries = proj_pass_entries(padded_rank(r));
     if (last_kernel_ms) *last_kernel_ms = tl_project_kernel_ms;
+    return VBNMF_OK;
+}
+
+int vbnmf_matrix_vb_project(const vbnmf_matrix *X, int64_t col_begin, int64_t col_end, int32_t r, const double *lw, const double *ew,
+                            double ah, double bh, double fudge, double *lh, double *eh, double *dh, int32_t max_it, double tol,
+                            int32_t device, double *ev_cell, int32_t *it_cell, int32_t *reason_cell)
+{
+    if (!X || !lw || !ew || !lh) return fail(VBNMF_ERR_BAD_ARG, "NULL argument");
+    if (X->M.shell) return fail(VBNMF_ERR_BAD_ARG, "a shell matrix holds no entries: vb_project needs the compressed columns");
+    if (r < 1 || r > VBNMF_MAX_RANK) return fail(VBNMF_ERR_BAD_ARG, "rank %d is outside [1, %d]", r, VBNMF_MAX_RANK);
+    if (col_begin < 0 || col_end > X->M.m || col_begin >= col_end)
+        return fail(VBNMF_ERR_BAD_ARG, "column range [%lld, %lld) is empty or outside the matrix's %lld columns", (long long)col_begin,
+                    (long long)col_end, (long long)X->M.m);
+    if (max_it < 1) return fail(VBNMF_ERR_BAD_ARG, "max_it must be >= 1");
+    if (!(ah > 0.0) || !(bh > 0.0)) return fail(VBNMF_ERR_BAD_ARG, "ah and bh must be > 0 (got %g, %g)", ah, bh);
+    if (int rc = check_device(device)) return rc;
+    try {
+        return vb_project_columns(X->M, col_begin, col_end, r, lw, ew, ah, bh, fudge, lh, eh, dh, max_it, tol, device, ev_cell, it_cell,
+                                  reason_cell);
+    } catch (const std::bad_alloc &) {
+        return fail(VBNMF_ERR_OOM, "out of host memory for the projection's staging arrays");
+    } catch (const std::exception &ex) {
+        return fail(VBNMF_ERR_HIP, "vbnmf_matrix_vb_project: %s", ex.what());
+    }
+}
+
+int vbnmf_vb_project_info(int32_t r, int32_t *pass_entries, double *last_kernel_ms)
+{
+    if (r < 1 || r > VBNMF_MAX_RANK) return fail(VBNMF_ERR_BAD_ARG, "rank %d is outside [1, %d]", r, VBNMF_MAX_RANK);
+    if (pass_entries) *pass_entries = proj_pass_entries(padded_rank(r));
+    if (last_kernel_ms) *last_kernel_ms = tl_vb_project_kernel_ms;
     return VBNMF_OK;
 }
 

@@ -4,6 +4,10 @@ The mathematics is the reference's own: the H half of ``nmf_updateR`` (reference
 untouched, ``likelihood`` (:40-49) taken column by column, and ``factorize()``'s stopping test (:208) applied to every cell on
 its own -- with W fixed nothing couples two cells.  The kernel (csrc/project.h) reads the matrix's compressed columns as they
 are: no tiled layout is cut and no engine is created.  No CPU fallback: without the HIP library every call raises.
+
+``vb_project`` is the same for a variational-Bayes fit (``vbnmf_matrix_vb_project``, csrc/vbproject.h): the H half of
+``vbnmf_updateR`` (reference R/bayesian.R:71-95) under the fitted posterior q(W) and the fitted hyper-parameters, giving E[H],
+sd[H] and an evidence term per cell.
 """
 from __future__ import annotations
 
@@ -132,3 +136,160 @@ def project(mat, basis, rank=None, prior=False, gamma_a=1.0, gamma_b=1.0, Itmax=
             M.close()
     return Projection(ranks=[r], basis=[W], coeff=[H], cell_likelihood=lk, nsteps=it, reason=why,
                       likelihood=float(lk.sum() / n / m))
+
+
+# ---- the same for a VB fit: the H half of the VB update under the fitted posterior q(W) (vbnmf_matrix_vb_project) -----------
+@dataclass
+class VBProjection:
+    """Posterior of the projected cells' coefficients; ``ranks`` / ``coeff`` / ``dcoeff`` as in ``VBResult``, so
+    ``cluster_id(p, rank=r)`` reads it."""
+    ranks: list = field(default_factory=list)
+    basis: list = field(default_factory=list)       # E[W] of the posterior the cells were placed on, n x r
+    dbasis: list = field(default_factory=list)      # sd[W]
+    coeff: list = field(default_factory=list)       # E[H], r x m
+    dcoeff: list = field(default_factory=list)      # sd[H] = sqrt(dh)
+    lcoeff: list = field(default_factory=list)      # lh = exp(E[log H]): pass it as lh0= to resume
+    cell_evidence: np.ndarray = None                # the cell's columns of U1 + U3 (R/bayesian.R:90-91, :94-95), not / (n m)
+    nsteps: np.ndarray = None                       # iterations of every cell
+    reason: np.ndarray = None                       # why every cell stopped: 1 converged, 3 NaN evidence, 4 Itmax
+    hyper: dict = field(default_factory=dict)       # ah, bh the cells were placed under
+    lml_cells: float = float("nan")                 # sum(cell_evidence) / (n m)
+
+
+def vb_pass_entries(rank):
+    """Stored entries of one cell that the VB kernel's workgroup takes in one pass of its threads at ``rank``
+    (``vbnmf_vb_project_info``)."""
+    v = ctypes.c_int32()
+    N.check(N.load().vbnmf_vb_project_info(int(rank), ctypes.byref(v), None))
+    return v.value
+
+
+def vb_last_kernel_ms():
+    """Kernel time of this thread's most recent ``vb_project`` call, in ms."""
+    v = ctypes.c_double()
+    N.check(N.load().vbnmf_vb_project_info(1, None, ctypes.byref(v)))
+    return v.value
+
+
+def _posterior_parts(res, rank, hyper):
+    """-> (ew, sd, ah, bh) of a ``VBResult`` at ``rank`` or of an ``(ew, sd)`` pair, vetted."""
+    if hasattr(res, "ranks") and hasattr(res, "basis"):
+        if not hasattr(res, "dbasis"):
+            raise ValueError("a VB projection needs a VBResult (basis and dbasis); an MLResult holds a point estimate: use project()")
+        if rank is None:
+            if len(res.ranks) != 1:
+                raise ValueError("rank= is needed to pick one basis of a result that holds several ranks")
+            rank = res.ranks[0]
+        hits = [i for i, r in enumerate(res.ranks) if r == rank]
+        if not hits:
+            raise IndexError("subscript out of bounds")
+        i = hits[0]
+        if len(res.dbasis) <= i or res.dbasis[i] is None:
+            raise ValueError(f"the result holds no dbasis for rank {rank}")
+        ew, sd = res.basis[i], res.dbasis[i]
+        measure = getattr(res, "measure", None) or {}
+        own = {k: measure[k][i] for k in ("ah", "bh") if k in measure and len(measure[k]) > i}
+        hyper = {**own, **(hyper or {})}
+    else:
+        try:
+            ew, sd = res
+        except (TypeError, ValueError):
+            raise ValueError("a VBResult or an (ew, sd) pair of n x r arrays is needed") from None
+    if hyper is None or "ah" not in hyper or "bh" not in hyper:
+        raise ValueError('hyper={"ah": .., "bh": ..} is needed: the pair, or the result\'s measure, holds none')
+    ew = np.asarray(ew, dtype=np.float64)
+    sd = np.asarray(sd, dtype=np.float64)
+    if ew.ndim != 2 or ew.shape != sd.shape:
+        raise ValueError(f"ew {ew.shape} and sd {sd.shape} must be n x r matrices of one shape")
+    if rank is not None and int(rank) != ew.shape[1]:
+        raise ValueError(f"rank={rank} does not match the basis' {ew.shape[1]} columns")
+    if not (np.all(ew > 0) and np.all(sd > 0)):
+        raise ValueError("ew and sd must be positive everywhere (mean and sd of Gamma posteriors)")
+    ah, bh = float(hyper["ah"]), float(hyper["bh"])
+    if not (ah > 0 and bh > 0):
+        raise ValueError("ah and bh must be > 0")
+    return ew, sd, ah, bh
+
+
+def posterior_basis(result_or_pair, rank=None, hyper=None, fudge=EPS):
+    """What the H half of the VB update reads of a fitted q(W) -> ``(lw, ew, ah, bh)``.
+
+    q(W_ik) is Gamma with shape ``alw`` and scale ``bew``; a fit stores ``ew = alw bew`` (its ``basis``) and
+    ``sd = sqrt(alw) bew`` (its ``dbasis``; reference R/bayesian.R:75-77, :102, :380-382), so ``bew = sd^2 / ew``,
+    ``alw = (ew / sd)^2`` and ``lw = exp(digamma(alw)) bew`` (:83).  ``result_or_pair``: a ``VBResult`` (its ``basis``,
+    ``dbasis`` and the ``ah``, ``bh`` of ``measure`` at ``rank``), or an ``(ew, sd)`` pair of n x r arrays together with
+    ``hyper={"ah": .., "bh": ..}``.  With a result, ``hyper`` overrides its own ``ah`` / ``bh``.  ``fudge``: the floor the fit
+    held ``lw`` at (:85-86).  (n r values of digamma, once per fit, on the host: the per-cell iteration is the device's.)"""
+    lw, ew, _sd, ah, bh = _posterior(result_or_pair, rank, hyper, fudge)
+    return lw, ew, ah, bh
+
+
+def _posterior(res, rank, hyper, fudge):
+    """-> (lw, ew, sd, ah, bh): ``posterior_basis`` together with the sd it was rebuilt from."""
+    from scipy.special import digamma
+    ew, sd, ah, bh = _posterior_parts(res, rank, hyper)
+    q = ew / sd
+    lw = np.exp(digamma(q * q)) * (sd * sd / ew)             # :83 with alw = (ew / sd)^2, bew = sd^2 / ew
+    lw[lw < fudge] = fudge                                   # :86
+    return lw, ew, sd, ah, bh
+
+
+def vb_project_columns(M, lw, ew, lh, ah, bh, col_begin, col_end, fudge=EPS, Itmax=10000, Tol=1e-5, device=0):
+    """``vbnmf_matrix_vb_project`` on cells ``[col_begin, col_end)`` of the ``CountMatrix`` ``M``: ``lh`` (r x cells, the
+    start) -> ``(lh, eh, dh, cell_evidence, nsteps, reason)``.  No argument is vetted here beyond what the library checks
+    itself."""
+    lw, ew = N.fcol(lw), N.fcol(ew)
+    r = lw.shape[1]
+    nc = int(col_end) - int(col_begin)
+    lh = np.array(lh, dtype=np.float64, order="F", copy=True)
+    eh, dh = np.zeros_like(lh, order="F"), np.zeros_like(lh, order="F")
+    ev = np.empty(max(nc, 0))
+    it = np.zeros(max(nc, 0), dtype=np.int32)
+    why = np.zeros(max(nc, 0), dtype=np.int32)
+    N.check(N.load().vbnmf_matrix_vb_project(M._h, int(col_begin), int(col_end), int(r), N.dptr(lw), N.dptr(ew), float(ah), float(bh),
+                                             float(fudge), N.dptr(lh), N.dptr(eh), N.dptr(dh), int(Itmax), float(Tol), int(device),
+                                             N.dptr(ev), it.ctypes.data_as(N.c_int32_p), why.ctypes.data_as(N.c_int32_p)))
+    return lh, eh, dh, ev, it, why
+
+
+def vb_project(mat, result, rank=None, hyper=None, Itmax=10000, Tol=1e-5, fudge=EPS, lh0=None, device=0):
+    """Posterior of the coefficients of the cells of ``mat`` under a fitted q(W), every cell iterated to its own stop on
+    the device.
+
+    ``mat``: genes x new cells (dense array, scipy sparse, or ``CountMatrix``), the genes of the fit in the fit's order.
+    ``result``: a ``VBResult`` (its ``basis``, ``dbasis`` and hyper-parameters of ``rank``) or an ``(ew, sd)`` pair with
+    ``hyper={"ah": .., "bh": ..}`` (``posterior_basis``).  ``Itmax``, ``Tol``: the bounds of R/bayesian.R:345-347, per cell
+    (without the ``lkh >= lk0`` clause).  ``lh0``: the start, r x m, clipped at ``fudge``; None:
+    ``lh_kj = sum_i x_ij / sum_k colSums(ew)_k`` for every k.  Returns ``VBProjection``.
+    """
+    lw, ew, sd, ah, bh = _posterior(result, rank, hyper, fudge)
+    n, r = ew.shape
+    own = not isinstance(mat, CountMatrix)
+    M = CountMatrix(mat) if own else mat
+    try:
+        if M.is_shell:
+            raise ValueError("a shell matrix holds no entries: vb_project needs the matrix itself")
+        nrow, m = M.shape
+        if nrow != n:
+            raise ValueError(f"mat has {nrow} rows (genes) but the basis has {n}")
+        if r > n:
+            raise ValueError(f"rank {r} exceeds the number of rows {n}")
+        if r < 1 or r > N.MAX_RANK:
+            raise ValueError(f"rank {r} is outside [1, {N.MAX_RANK}]")
+        if int(Itmax) < 1:
+            raise ValueError("Itmax must be at least 1")
+        if M.empty_counts()[1] > 0:
+            raise ValueError("Input matrix contains empty columns")                # R/bayesian.R:247
+        if lh0 is None:
+            lh = default_start(M, ew)                                               # (on E[W])
+        else:
+            lh = np.array(lh0, dtype=np.float64, copy=True)
+            if lh.shape != (r, m):
+                raise ValueError(f"lh0 must be {r} x {m}")
+        lh[lh < fudge] = fudge                                                     # (NaN stays NaN)
+        lh, eh, dh, ev, it, why = vb_project_columns(M, lw, ew, lh, ah, bh, 0, m, fudge, Itmax, Tol, device)
+    finally:
+        if own:
+            M.close()
+    return VBProjection(ranks=[r], basis=[ew], dbasis=[sd], coeff=[eh], dcoeff=[np.sqrt(dh)], lcoeff=[lh], cell_evidence=ev,
+                        nsteps=it, reason=why, hyper={"ah": ah, "bh": bh}, lml_cells=float(ev.sum() / n / m))

@@ -528,6 +528,40 @@ int vbnmf_matrix_project(const vbnmf_matrix *X, int64_t col_begin, int64_t col_e
  * kernel time in ms of the calling thread's most recent vbnmf_matrix_project. */
 int vbnmf_project_info(int32_t r, int32_t *pass_entries, double *last_kernel_ms);
 
+/* ---------------------------------------------------------------------------------
+ * Projection of new cells onto a VB fit's posterior basis: the H half of vbnmf_updateR (R/bayesian.R:71-95) iterated with
+ * q(W) -- lw and ew -- untouched, every cell (column) on its own:
+ *   lambda_ij = (lw lh)_ij                                                          (:71, stored entries only)
+ *   alh_kj = ah + lh_kj * sum_i lw_ik x_ij / lambda_ij                              (:73, :79)
+ *   beh_k  = 1 / (ah / bh + colSums(ew)_k)                                          (:80, the given ew: one value per k)
+ *   eh_kj  = alh_kj beh_k ;  dh_kj = alh_kj beh_k^2                                 (:81, :103)
+ *   lh_kj  = max(exp(digamma(alh_kj)) beh_k, fudge)                                 (:84, :87)
+ * until the cell's evidence at the new lh -- its column of U1 (:90-91) plus its column of U3 (:94-95), not divided by n m;
+ * U2 belongs to W and is no part of it --
+ *   ev_j = - sum_k colSums(ew)_k eh_kj - sum_i lgamma(x_ij + 1)
+ *          - sum_i x_ij [ (((lw log lw) lh)_ij + (lw (lh log lh))_ij) / lambda_ij - log lambda_ij ]
+ *          + sum_k [ -(ah/bh) eh_kj - lgamma(ah) + ah log(ah/bh) + alh_kj (1 + log beh_k) + lgamma(alh_kj) ]
+ * meets vb_iterate's test (:345-347) for that cell: ev NaN (reason 3); after step it > 1, abs(1 - ev / lk0) < tol (reason 1;
+ * lk0 = the previous step's ev); max_it reached (reason 4).  The reference's clause `lkh >= lk0` is NOT applied (the
+ * evidence is not monotone under this update and the clause would make a cell's stop hang on rounding, DESIGN.md section
+ * 5g), nor is the hyper.update.n0 gate (no hyper-parameter is updated here).
+ * Reads the handle's canonical compressed columns for cells [col_begin, col_end) as vbnmf_matrix_project does: no layout, no
+ * engine, ONE launch (csrc/vbproject.h).  lw, ew: n x r column-major (lw > 0: lw = exp(digamma(alw)) bew of the fit,
+ * :83).  lh: r x (col_end - col_begin) column-major, in: the start, out: the result; eh, dh (each may be NULL): E[H] and
+ * Var[H] of the same shape.  ev_cell, it_cell, reason_cell (each may be NULL), one value per cell.  A cell's result does
+ * not depend on the other cells of the call, bit for bit.  An all-zero column is legal here (alh = ah).
+ * VBNMF_ERR_BAD_ARG: a shell matrix, r < 1 or > VBNMF_MAX_RANK, an empty or outside column range, NULL lw, ew or lh,
+ * max_it < 1, ah or bh not > 0; VBNMF_ERR_NO_DEVICE: no gfx950 device. */
+int vbnmf_matrix_vb_project(const vbnmf_matrix *X, int64_t col_begin, int64_t col_end, int32_t r,
+                            const double *lw, const double *ew, double ah, double bh, double fudge,
+                            double *lh, double *eh, double *dh,
+                            int32_t max_it, double tol, int32_t device,
+                            double *ev_cell, int32_t *it_cell, int32_t *reason_cell);
+/* Constants of that kernel at rank r (host only; any out pointer may be NULL): the stored entries of a cell that the
+ * workgroup's threads take in one pass (those of vbnmf_project_info), and the kernel time in ms of the calling thread's
+ * most recent vbnmf_matrix_vb_project. */
+int vbnmf_vb_project_info(int32_t r, int32_t *pass_entries, double *last_kernel_ms);
+
 /* Cluster of every cell from the coefficients the engine holds:
  * ids[j] = which.max(h[, j])[1], 1-based, first maximum on ties (R/factorize.R:55-56 inside
  * connectivity(), R/utils.R:906 cluster_id); h = the ML coefficient matrix, or E[H] of a VB
