@@ -155,6 +155,9 @@ SIGNATURES = {
     "vbnmf_project_info": (ctypes.c_int, [_I32, c_int32_p, c_double_p]),
     "vbnmf_matrix_vb_project": (ctypes.c_int, [_VP, _I64, _I64, _I32, c_double_p, c_double_p, _D, _D, _D, c_double_p, c_double_p,
                                                c_double_p, _I32, _D, _I32, c_double_p, c_int32_p, c_int32_p]),
+    "vbnmf_matrix_vb_project_coupled": (ctypes.c_int, [_VP, _I64, _I64, _I32, c_double_p, c_double_p, c_double_p, c_int32_p, _I32, _I32, _D,
+                                                       c_double_p, c_double_p, c_double_p, _I32, _D, _I32, c_double_p, c_int32_p,
+                                                       c_int32_p, c_int32_p, c_int32_p, c_double_p, c_double_p, _I64]),
     "vbnmf_vb_project_info": (ctypes.c_int, [_I32, c_int32_p, c_double_p]),
     "vbnmf_engine_cluster_ids": (ctypes.c_int, [_VP, c_int32_p]),
     "vbnmf_engine_spmm": (ctypes.c_int, [_VP, _I32, c_double_p, c_double_p]),

@@ -4170,6 +4170,8 @@ struct ProjectDevice {
     int32_t *row = nullptr, *it = nullptr, *reason = nullptr;
     double *val = nullptr, *W = nullptr, *cw = nullptr, *H = nullptr, *lk = nullptr;
     double *eh = nullptr, *dh = nullptr;  // (the VB projection's further results)
+    double *S = nullptr, *lgx = nullptr, *seh = nullptr, *sll = nullptr, *hist = nullptr;   // (the coupled VB projection's carried
+    VbpCtl *ctl = nullptr;                                                                  //  state, cell sums and control block)
     unsigned int *ticket = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool queued = false;
@@ -4179,6 +4181,7 @@ struct ProjectDevice {
         if (queued) (void)hipStreamSynchronize(nullptr);
         dev_free(colptr); dev_free(row); dev_free(it); dev_free(reason); dev_free(val); dev_free(W); dev_free(cw); dev_free(H);
         dev_free(lk); dev_free(eh); dev_free(dh); dev_free(ticket);
+        dev_free(S); dev_free(lgx); dev_free(seh); dev_free(sll); dev_free(hist); dev_free(ctl);
         if (ev0) (void)hipEventDestroy(ev0);
         if (ev1) (void)hipEventDestroy(ev1);
         if (caller_device >= 0) (void)hipSetDevice(caller_device);
@@ -4271,17 +4274,14 @@ int project_columns(const Matrix &M, int64_t cb, int64_t ce, int32_t r, const do
 // up once, one launch takes every cell to its own stop.
 thread_local double tl_vb_project_kernel_ms = 0.0;
 
-int vb_project_columns(const Matrix &M, int64_t cb, int64_t ce, int32_t r, const double *lw, const double *ew, double ah, double bh,
-                       double fudge, double *lh, double *eh, double *dh, int32_t max_it, double tol, int32_t device, double *ev_cell,
-                       int32_t *it_cell, int32_t *reason_cell)
+// What both VB projections put on the device (vbproject.h): per gene, 2 R wide, lw_i. | (lw log lw)_i. (R/bayesian.R:90; padding
+// columns 0), colSums(ew) (:80; every column added gene by gene, in order), the start cell by cell -- formed on the library's host
+// threads --, the cells' compressed columns, and room for eh, dh and the cell evidences.
+int vb_project_upload(const Matrix &M, int64_t cb, int64_t ce, int32_t r, const double *lw, const double *ew, const double *lh,
+                      ProjectDevice &D)
 {
     const int64_t n = M.n, nc = ce - cb;
     const int R = padded_rank(r);
-    ProjectDevice D;
-    (void)hipGetDevice(&D.caller_device);
-    HIPCHECK(hipSetDevice(device));
-    // what a cell gathers per gene, 2 R wide: lw_i. | (lw log lw)_i. (R/bayesian.R:90; padding columns 0), colSums(ew) (:80;
-    // every column added gene by gene, in order) and the start, cell by cell -- on the library's host threads
     std::vector<double> Tp((size_t)n * 2 * R, 0.0), cew((size_t)R, 0.0), Hp((size_t)nc * R, 0.0);
     parallel_for(n, [&](int64_t b, int64_t e, int) {
         for (int64_t i = b; i < e; i++)
@@ -4313,9 +4313,6 @@ int vb_project_columns(const Matrix &M, int64_t cb, int64_t ce, int32_t r, const
     if (int rc = dev_alloc(&D.eh, Hp.size())) return rc;
     if (int rc = dev_alloc(&D.dh, Hp.size())) return rc;
     if (int rc = dev_alloc(&D.lk, (size_t)nc)) return rc;
-    if (int rc = dev_alloc(&D.it, (size_t)nc)) return rc;
-    if (int rc = dev_alloc(&D.reason, (size_t)nc)) return rc;
-    if (int rc = dev_alloc(&D.ticket, 1)) return rc;
     HIPCHECK(hipMemcpy(D.colptr, M.colptr.data() + cb, ((size_t)nc + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
     if (ne > 0) {
         HIPCHECK(hipMemcpy(D.row, M.row.data() + e0, (size_t)ne * sizeof(int32_t), hipMemcpyHostToDevice));
@@ -4324,6 +4321,41 @@ int vb_project_columns(const Matrix &M, int64_t cb, int64_t ce, int32_t r, const
     HIPCHECK(hipMemcpy(D.W, Tp.data(), Tp.size() * sizeof(double), hipMemcpyHostToDevice));
     HIPCHECK(hipMemcpy(D.cw, cew.data(), cew.size() * sizeof(double), hipMemcpyHostToDevice));
     HIPCHECK(hipMemcpy(D.H, Hp.data(), Hp.size() * sizeof(double), hipMemcpyHostToDevice));
+    return VBNMF_OK;
+}
+
+// lh, eh, dh (each may be NULL) of the cells back into r x cells column-major arrays
+int vb_project_download(const ProjectDevice &D, int64_t nc, int32_t r, double *lh, double *eh, double *dh)
+{
+    const int R = padded_rank(r);
+    std::vector<double> back((size_t)nc * R);
+    double *const outs[3] = {lh, eh, dh};
+    const double *const srcs[3] = {D.H, D.eh, D.dh};
+    for (int q = 0; q < 3; q++) {
+        if (!outs[q]) continue;
+        HIPCHECK(hipMemcpy(back.data(), srcs[q], back.size() * sizeof(double), hipMemcpyDeviceToHost));
+        double *out = outs[q];
+        parallel_for(nc, [&](int64_t b, int64_t e, int) {
+            for (int64_t j = b; j < e; j++)
+                for (int k = 0; k < r; k++) out[(size_t)j * r + k] = back[(size_t)j * R + k];
+        });
+    }
+    return VBNMF_OK;
+}
+
+int vb_project_columns(const Matrix &M, int64_t cb, int64_t ce, int32_t r, const double *lw, const double *ew, double ah, double bh,
+                       double fudge, double *lh, double *eh, double *dh, int32_t max_it, double tol, int32_t device, double *ev_cell,
+                       int32_t *it_cell, int32_t *reason_cell)
+{
+    const int64_t nc = ce - cb, e0 = M.colptr[cb];
+    const int R = padded_rank(r);
+    ProjectDevice D;
+    (void)hipGetDevice(&D.caller_device);
+    HIPCHECK(hipSetDevice(device));
+    if (int rc = vb_project_upload(M, cb, ce, r, lw, ew, lh, D)) return rc;
+    if (int rc = dev_alloc(&D.it, (size_t)nc)) return rc;
+    if (int rc = dev_alloc(&D.reason, (size_t)nc)) return rc;
+    if (int rc = dev_alloc(&D.ticket, 1)) return rc;
     HIPCHECK(hipMemsetAsync(D.ticket, 0, sizeof(unsigned int), nullptr));
 
     VbProjectArgs a;
@@ -4346,18 +4378,7 @@ int vb_project_columns(const Matrix &M, int64_t cb, int64_t ce, int32_t r, const
     });
     if (rc) return rc;
     HIPCHECK(hipEventRecord(D.ev1, nullptr));
-    std::vector<double> back(Hp.size());
-    double *const outs[3] = {lh, eh, dh};
-    const double *const srcs[3] = {D.H, D.eh, D.dh};
-    for (int q = 0; q < 3; q++) {
-        if (!outs[q]) continue;
-        HIPCHECK(hipMemcpy(back.data(), srcs[q], back.size() * sizeof(double), hipMemcpyDeviceToHost));
-        double *out = outs[q];
-        parallel_for(nc, [&](int64_t b, int64_t e, int) {
-            for (int64_t j = b; j < e; j++)
-                for (int k = 0; k < r; k++) out[(size_t)j * r + k] = back[(size_t)j * R + k];
-        });
-    }
+    if (int rc = vb_project_download(D, nc, r, lh, eh, dh)) return rc;
     float ms = 0.0f;
     HIPCHECK(hipEventSynchronize(D.ev1));
     HIPCHECK(hipEventElapsedTime(&ms, D.ev0, D.ev1));
@@ -4365,6 +4386,82 @@ int vb_project_columns(const Matrix &M, int64_t cb, int64_t ce, int32_t r, const
     if (ev_cell) HIPCHECK(hipMemcpy(ev_cell, D.lk, (size_t)nc * sizeof(double), hipMemcpyDeviceToHost));
     if (it_cell) HIPCHECK(hipMemcpy(it_cell, D.it, (size_t)nc * sizeof(int32_t), hipMemcpyDeviceToHost));
     if (reason_cell) HIPCHECK(hipMemcpy(reason_cell, D.reason, (size_t)nc * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return VBNMF_OK;
+}
+
+// ---- the coupled form (vbproject.h, k_vbp_step / k_vbp_control): the same upload plus what a cell carries between launches;
+// (step, control) pairs are queued eight steps ahead, never past max_it, and the control block is read after each batch.
+constexpr int kVbpBatch = 8;
+
+int vb_project_coupled_columns(const Matrix &M, int64_t cb, int64_t ce, int32_t r, const double *lw, const double *ew, double *hyper,
+                               const int32_t *flags, int32_t n0, int32_t dn, double fudge, double *lh, double *eh, double *dh,
+                               int32_t max_it, double tol, int32_t device, double *ev_cell, int32_t *it_cell, int32_t *reason_cell,
+                               int32_t *it_out, int32_t *reason_out, double *evidence, double *history, int64_t history_rows)
+{
+    const int64_t nc = ce - cb, e0 = M.colptr[cb];
+    const int R = padded_rank(r);
+    ProjectDevice D;
+    (void)hipGetDevice(&D.caller_device);
+    HIPCHECK(hipSetDevice(device));
+    const int64_t hrows = history ? std::min<int64_t>(std::max<int64_t>(history_rows, 0), max_it) : 0;
+    if (int rc = vb_project_upload(M, cb, ce, r, lw, ew, lh, D)) return rc;
+    if (int rc = dev_alloc(&D.S, (size_t)nc * R)) return rc;
+    if (int rc = dev_alloc(&D.lgx, (size_t)nc)) return rc;
+    if (int rc = dev_alloc(&D.seh, (size_t)nc)) return rc;
+    if (int rc = dev_alloc(&D.sll, (size_t)nc)) return rc;
+    if (int rc = dev_alloc(&D.hist, (size_t)hrows * 5)) return rc;
+    if (int rc = dev_alloc(&D.ctl, 1)) return rc;
+    VbpCtl c;
+    std::memset(&c, 0, sizeof c);                            // it, stop, reason, lk0, the ticket: 0
+    c.hyper[0] = 1.0; c.hyper[1] = 1.0; c.hyper[2] = hyper[0]; c.hyper[3] = hyper[1];
+    c.tol = tol; c.max_it = max_it; c.n0 = n0; c.dn = dn;
+    c.flags[2] = flags[0] ? 1 : 0; c.flags[3] = flags[1] ? 1 : 0;
+    HIPCHECK(hipMemcpy(D.ctl, &c, sizeof c, hipMemcpyHostToDevice));
+
+    VbpStepArgs a;
+    a.colptr = D.colptr; a.base = e0; a.row = D.row; a.val = D.val; a.T = D.W; a.cew = D.cw; a.LH = D.H; a.EH = D.eh; a.DH = D.dh;
+    a.S = D.S; a.lgx = D.lgx; a.ev = D.lk; a.seh = D.seh; a.sll = D.sll; a.ctl = D.ctl; a.ncell = nc; a.r = r; a.fudge = fudge;
+    // a persistent grid, as project_columns'
+    int cus = 0;
+    HIPCHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
+    if (cus <= 0) cus = 256;
+    const unsigned grid = (unsigned)std::min<int64_t>(nc, (int64_t)cus * (2048 / kProjThreads));
+    HIPCHECK(hipEventCreate(&D.ev0));
+    HIPCHECK(hipEventCreate(&D.ev1));
+    HIPCHECK(hipEventRecord(D.ev0, nullptr));
+    D.queued = true;
+    int32_t queued = 0;
+    while (!c.stop && queued < max_it) {
+        const int32_t batch = std::min<int32_t>(kVbpBatch, max_it - queued);
+        int rc = with_rank(R, [&](auto rt) {
+            for (int32_t q = 0; q < batch; q++) {
+                hipLaunchKernelGGL((k_vbp_step<rt()>), dim3(grid), dim3(kProjThreads), 0, nullptr, a);
+                hipLaunchKernelGGL(k_vbp_control, dim3(1), dim3(1024), 0, nullptr, D.lk, D.seh, D.sll, nc, (int)r, D.ctl, hrows ? D.hist : nullptr,
+                                   hrows);
+            }
+            HIPCHECK(hipGetLastError());
+            return (int)VBNMF_OK;
+        });
+        if (rc) return rc;
+        queued += batch;
+        HIPCHECK(hipMemcpy(&c, D.ctl, sizeof c, hipMemcpyDeviceToHost));     // (waits for the batch)
+    }
+    if (!c.stop) return fail(VBNMF_ERR_HIP, "the coupled projection's device loop did not stop within max_it = %d steps", max_it);
+    HIPCHECK(hipEventRecord(D.ev1, nullptr));
+    if (int rc = vb_project_download(D, nc, r, lh, eh, dh)) return rc;
+    float ms = 0.0f;
+    HIPCHECK(hipEventSynchronize(D.ev1));
+    HIPCHECK(hipEventElapsedTime(&ms, D.ev0, D.ev1));
+    tl_vb_project_kernel_ms = ms;
+    if (ev_cell) HIPCHECK(hipMemcpy(ev_cell, D.lk, (size_t)nc * sizeof(double), hipMemcpyDeviceToHost));
+    if (it_cell) std::fill(it_cell, it_cell + nc, c.it);                     // one stop: every cell made the same steps
+    if (reason_cell) std::fill(reason_cell, reason_cell + nc, c.reason);
+    const int64_t rows = std::min<int64_t>(hrows, c.it);
+    if (rows > 0) HIPCHECK(hipMemcpy(history, D.hist, (size_t)rows * 5 * sizeof(double), hipMemcpyDeviceToHost));
+    hyper[0] = c.hyper[2]; hyper[1] = c.hyper[3];
+    if (it_out) *it_out = c.it;
+    if (reason_out) *reason_out = c.reason;
+    if (evidence) *evidence = c.E;
     return VBNMF_OK;
 }
 
@@ -4421,6 +4518,33 @@ int vbnmf_matrix_vb_project(const vbnmf_matrix *X, int64_t col_begin, int64_t co
         return fail(VBNMF_ERR_OOM, "out of host memory for the projection's staging arrays");
     } catch (const std::exception &ex) {
         return fail(VBNMF_ERR_HIP, "vbnmf_matrix_vb_project: %s", ex.what());
+    }
+}
+
+int vbnmf_matrix_vb_project_coupled(const vbnmf_matrix *X, int64_t col_begin, int64_t col_end, int32_t r, const double *lw,
+                                    const double *ew, double *hyper, const int32_t *flags, int32_t n0, int32_t dn, double fudge,
+                                    double *lh, double *eh, double *dh, int32_t max_it, double tol, int32_t device, double *ev_cell,
+                                    int32_t *it_cell, int32_t *reason_cell, int32_t *it, int32_t *reason, double *evidence,
+                                    double *history, int64_t history_rows)
+{
+    if (!X || !lw || !ew || !lh || !hyper || !flags) return fail(VBNMF_ERR_BAD_ARG, "NULL argument");
+    if (X->M.shell) return fail(VBNMF_ERR_BAD_ARG, "a shell matrix holds no entries: vb_project needs the compressed columns");
+    if (r < 1 || r > VBNMF_MAX_RANK) return fail(VBNMF_ERR_BAD_ARG, "rank %d is outside [1, %d]", r, VBNMF_MAX_RANK);
+    if (col_begin < 0 || col_end > X->M.m || col_begin >= col_end)
+        return fail(VBNMF_ERR_BAD_ARG, "column range [%lld, %lld) is empty or outside the matrix's %lld columns", (long long)col_begin,
+                    (long long)col_end, (long long)X->M.m);
+    if (max_it < 1) return fail(VBNMF_ERR_BAD_ARG, "max_it must be >= 1");
+    if (!(hyper[0] > 0.0) || !(hyper[1] > 0.0)) return fail(VBNMF_ERR_BAD_ARG, "ah and bh must be > 0 (got %g, %g)", hyper[0], hyper[1]);
+    if (dn < 1) return fail(VBNMF_ERR_BAD_ARG, "dn must be >= 1");
+    if (n0 < 0) return fail(VBNMF_ERR_BAD_ARG, "n0 must be >= 0");
+    if (int rc = check_device(device)) return rc;
+    try {
+        return vb_project_coupled_columns(X->M, col_begin, col_end, r, lw, ew, hyper, flags, n0, dn, fudge, lh, eh, dh, max_it, tol, device,
+                                          ev_cell, it_cell, reason_cell, it, reason, evidence, history, history_rows);
+    } catch (const std::bad_alloc &) {
+        return fail(VBNMF_ERR_OOM, "out of host memory for the projection's staging arrays");
+    } catch (const std::exception &ex) {
+        return fail(VBNMF_ERR_HIP, "vbnmf_matrix_vb_project_coupled: %s", ex.what());
     }
 }
 

@@ -7,7 +7,9 @@ are: no tiled layout is cut and no engine is created.  No CPU fallback: without 
 
 ``vb_project`` is the same for a variational-Bayes fit (``vbnmf_matrix_vb_project``, csrc/vbproject.h): the H half of
 ``vbnmf_updateR`` (reference R/bayesian.R:71-95) under the fitted posterior q(W) and the fitted hyper-parameters, giving E[H],
-sd[H] and an evidence term per cell.
+sd[H] and an evidence term per cell.  With ``hyper_update=`` or ``stop="global"`` it is the H half of ``vb_iterate`` instead
+(``vbnmf_matrix_vb_project_coupled``): the prior of H is re-estimated on the new cells as the loop goes (R/bayesian.R:342-344)
+and all cells stop together.
 """
 from __future__ import annotations
 
@@ -19,7 +21,7 @@ import numpy as np
 from . import _native as N
 from .engine import EPS, CountMatrix
 
-REASONS = {1: "converged", 3: "NaN likelihood", 4: "Itmax reached"}
+REASONS = {1: "converged", 3: "NaN likelihood", 4: "Itmax reached", 5: "hyper-parameter update failed to converge"}
 
 
 @dataclass
@@ -151,9 +153,12 @@ class VBProjection:
     lcoeff: list = field(default_factory=list)      # lh = exp(E[log H]): pass it as lh0= to resume
     cell_evidence: np.ndarray = None                # the cell's columns of U1 + U3 (R/bayesian.R:90-91, :94-95), not / (n m)
     nsteps: np.ndarray = None                       # iterations of every cell
-    reason: np.ndarray = None                       # why every cell stopped: 1 converged, 3 NaN evidence, 4 Itmax
-    hyper: dict = field(default_factory=dict)       # ah, bh the cells were placed under
+    reason: np.ndarray = None                       # why every cell stopped: 1 converged, 3 NaN evidence, 4 Itmax, 5 (REASONS)
+    hyper: dict = field(default_factory=dict)       # ah, bh the cells were placed under (the final pair of a coupled run)
     lml_cells: float = float("nan")                 # sum(cell_evidence) / (n m)
+    evidence: float = float("nan")                  # E = sum(cell_evidence); of a coupled run: as its control step summed it
+    hyper0: dict = field(default_factory=dict)      # ah, bh the projection started from
+    history: np.ndarray = None                      # coupled run with history=True: a row [E, mean(log lh), mean(eh), ah, bh] per step
 
 
 def vb_pass_entries(rank):
@@ -252,16 +257,79 @@ def vb_project_columns(M, lw, ew, lh, ah, bh, col_begin, col_end, fudge=EPS, Itm
     return lh, eh, dh, ev, it, why
 
 
-def vb_project(mat, result, rank=None, hyper=None, Itmax=10000, Tol=1e-5, fudge=EPS, lh0=None, device=0):
+def vb_project_coupled_columns(M, lw, ew, lh, ah, bh, col_begin, col_end, hyper_update=(False, False), n0=10, dn=1, fudge=EPS,
+                               Itmax=10000, Tol=1e-5, device=0, history_rows=0):
+    """``vbnmf_matrix_vb_project_coupled`` on cells ``[col_begin, col_end)`` of the ``CountMatrix`` ``M``: ``lh`` (r x cells,
+    the start) -> ``(lh, eh, dh, cell_evidence, nsteps, reason, (ah, bh), it, why, evidence, history)``; ``history`` holds the
+    rows of the steps made (at most ``history_rows``), or is None.  No argument is vetted here beyond what the library checks
+    itself."""
+    lw, ew = N.fcol(lw), N.fcol(ew)
+    r = lw.shape[1]
+    nc = int(col_end) - int(col_begin)
+    lh = np.array(lh, dtype=np.float64, order="F", copy=True)
+    eh, dh = np.zeros_like(lh, order="F"), np.zeros_like(lh, order="F")
+    ev = np.empty(max(nc, 0))
+    it = np.zeros(max(nc, 0), dtype=np.int32)
+    why = np.zeros(max(nc, 0), dtype=np.int32)
+    hy = np.array([ah, bh], dtype=np.float64)
+    flags = np.array([bool(hyper_update[0]), bool(hyper_update[1])], dtype=np.int32)
+    rows = max(int(history_rows), 0)
+    hist = np.full((rows, 5), np.nan) if rows else None
+    steps, stop, E = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_double(float("nan"))
+    N.check(N.load().vbnmf_matrix_vb_project_coupled(M._h, int(col_begin), int(col_end), int(r), N.dptr(lw), N.dptr(ew), N.dptr(hy),
+                                                     flags.ctypes.data_as(N.c_int32_p), int(n0), int(dn), float(fudge), N.dptr(lh),
+                                                     N.dptr(eh), N.dptr(dh), int(Itmax), float(Tol), int(device), N.dptr(ev),
+                                                     it.ctypes.data_as(N.c_int32_p), why.ctypes.data_as(N.c_int32_p),
+                                                     ctypes.byref(steps), ctypes.byref(stop), ctypes.byref(E), N.dptr(hist), rows))
+    if hist is not None:
+        hist = hist[:min(rows, steps.value)]
+    return lh, eh, dh, ev, it, why, (float(hy[0]), float(hy[1])), steps.value, stop.value, E.value, hist
+
+
+def _coupled_mode(hyper_update, stop, hyper_n0, hyper_dn):
+    """-> (coupled?, (fa, fb)) of ``vb_project``'s arguments, vetted; touches no device."""
+    if hyper_update is None:
+        flags = (False, False)
+    else:
+        try:
+            fa, fb = hyper_update
+        except (TypeError, ValueError):
+            raise ValueError("hyper_update must be a pair (update ah?, update bh?)") from None
+        flags = (bool(fa), bool(fb))
+    if stop is None:
+        stop = "global" if any(flags) else "cell"
+    if stop not in ("cell", "global"):
+        raise ValueError(f'stop must be "cell" or "global", not {stop!r}')
+    if stop == "cell" and any(flags):
+        raise ValueError('stop="cell" cannot go with hyper_update: an updated hyper-parameter couples the cells (stop="global")')
+    if int(hyper_dn) < 1:
+        raise ValueError("hyper_dn must be at least 1")
+    if int(hyper_n0) < 0:
+        raise ValueError("hyper_n0 must be at least 0")
+    return stop == "global", flags
+
+
+def vb_project(mat, result, rank=None, hyper=None, Itmax=10000, Tol=1e-5, fudge=EPS, lh0=None, device=0, hyper_update=None, stop=None,
+               hyper_n0=10, hyper_dn=1, history=False):
     """Posterior of the coefficients of the cells of ``mat`` under a fitted q(W), every cell iterated to its own stop on
-    the device.
+    the device -- or, with ``hyper_update`` / ``stop="global"``, all cells together with the prior of H re-estimated on them.
 
     ``mat``: genes x new cells (dense array, scipy sparse, or ``CountMatrix``), the genes of the fit in the fit's order.
     ``result``: a ``VBResult`` (its ``basis``, ``dbasis`` and hyper-parameters of ``rank``) or an ``(ew, sd)`` pair with
     ``hyper={"ah": .., "bh": ..}`` (``posterior_basis``).  ``Itmax``, ``Tol``: the bounds of R/bayesian.R:345-347, per cell
     (without the ``lkh >= lk0`` clause).  ``lh0``: the start, r x m, clipped at ``fudge``; None:
     ``lh_kj = sum_i x_ij / sum_k colSums(ew)_k`` for every k.  Returns ``VBProjection``.
+
+    ``hyper_update=(ah?, bh?)``: re-estimate the marked hyper-parameters of H on the cells of ``mat`` from step
+    ``hyper_n0 + 1`` on, every ``hyper_dn`` steps, as ``vb_iterate`` does (R/bayesian.R:342-344, ``hyper_update`` :2-53; the
+    reference sets ``bh`` to mean(E[H]) when either is marked).  The fit's own ``ah``, ``bh`` are the start (``hyper0`` of the
+    result; ``hyper`` is the final pair).  The cells are then coupled and stop together: ``stop="global"`` applies :345-347 to
+    the cells' total evidence (``evidence``), gate ``it > hyper_n0`` included, and is the default with a marked
+    hyper-parameter; ``stop="cell"`` (the default without) is each cell's own stop.  ``stop="global"`` without
+    ``hyper_update`` takes the per-cell steps under the global rule.  ``history=True`` keeps a row
+    ``[E, mean(log lh), mean(E[H]), ah, bh]`` per step.  ``reason`` 5: the hyper-parameter update failed to converge.
     """
+    coupled, flags = _coupled_mode(hyper_update, stop, hyper_n0, hyper_dn)
     lw, ew, sd, ah, bh = _posterior(result, rank, hyper, fudge)
     n, r = ew.shape
     own = not isinstance(mat, CountMatrix)
@@ -287,9 +355,16 @@ def vb_project(mat, result, rank=None, hyper=None, Itmax=10000, Tol=1e-5, fudge=
             if lh.shape != (r, m):
                 raise ValueError(f"lh0 must be {r} x {m}")
         lh[lh < fudge] = fudge                                                     # (NaN stays NaN)
-        lh, eh, dh, ev, it, why = vb_project_columns(M, lw, ew, lh, ah, bh, 0, m, fudge, Itmax, Tol, device)
+        if coupled:
+            lh, eh, dh, ev, it, why, (ah1, bh1), _steps, _why, E, hist = vb_project_coupled_columns(
+                M, lw, ew, lh, ah, bh, 0, m, flags, hyper_n0, hyper_dn, fudge, Itmax, Tol, device,
+                history_rows=min(int(Itmax), 1 << 20) if history else 0)
+        else:
+            lh, eh, dh, ev, it, why = vb_project_columns(M, lw, ew, lh, ah, bh, 0, m, fudge, Itmax, Tol, device)
+            ah1, bh1, E, hist = ah, bh, float(ev.sum()), None
     finally:
         if own:
             M.close()
     return VBProjection(ranks=[r], basis=[ew], dbasis=[sd], coeff=[eh], dcoeff=[np.sqrt(dh)], lcoeff=[lh], cell_evidence=ev,
-                        nsteps=it, reason=why, hyper={"ah": ah, "bh": bh}, lml_cells=float(ev.sum() / n / m))
+                        nsteps=it, reason=why, hyper={"ah": ah1, "bh": bh1}, lml_cells=float(ev.sum() / n / m), evidence=E,
+                        hyper0={"ah": ah, "bh": bh}, history=hist)

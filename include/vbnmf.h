@@ -557,9 +557,35 @@ int vbnmf_matrix_vb_project(const vbnmf_matrix *X, int64_t col_begin, int64_t co
                             double *lh, double *eh, double *dh,
                             int32_t max_it, double tol, int32_t device,
                             double *ev_cell, int32_t *it_cell, int32_t *reason_cell);
+/* The same projection with the prior of H re-estimated on the cells of the call and ONE stop for all of them: the H half of
+ * vb_iterate (R/bayesian.R:336-352) with q(W) held.  Step it = 1, 2, .. is the step above for every cell under the current
+ * (ah, bh); then, over the cells of the call,
+ *   E = sum_j ev_j ;  ehm = mean(eh) ;  lhm = mean(log lh)                        (means over the r * cells components)
+ *   if it > n0 and it % dn == 0: hyper_update (:2-53) with hyper.update = (F, F, flags[0], flags[1]): Newton on ah if
+ *     flags[0] (Niter 100, Tol 1e-3, :343-344), and bh <- ehm if either flag is set (:50-51 assign ehm in both branches)
+ *   stop, in this order (:342-348): the hyper-parameter update did not converge or took a non-finite step (reason 5; ah, bh
+ *     keep their values); E NaN (reason 3); it > 1, it > n0 and abs(1 - E / lk0) < tol (reason 1; lk0 = the previous E);
+ *     otherwise lk0 <- E, and max_it reached is reason 4.  `lkh >= lk0` is NOT applied, as above.
+ * The evidence of a step is taken under the (ah, bh) the step was made with; the returned pair includes the update of the
+ * last step.  With both flags 0 the cells take exactly the steps of vbnmf_matrix_vb_project, bit for bit, and only the stop
+ * differs.  The means run over the cells of THIS call: a caller who splits the columns estimates one prior per part.
+ * One launch per step plus one for the totals and the control step (csrc/vbproject.h); the host looks at the control block
+ * every eight steps.  hyper: in ah, bh to start from, out the final pair.  All cells make the same number of steps:
+ * it_cell and reason_cell (each may be NULL) are filled with that one value, also returned in it and reason (each may be
+ * NULL); evidence (may be NULL): the E of the last step.  history (may be NULL): history_rows x 5 row-major, row it - 1 =
+ * [E, lhm, ehm, ah, bh after the update]; rows past history_rows are not written.  Everything else as above.
+ * VBNMF_ERR_BAD_ARG: as above, NULL hyper or flags, dn < 1, n0 < 0. */
+int vbnmf_matrix_vb_project_coupled(const vbnmf_matrix *X, int64_t col_begin, int64_t col_end, int32_t r,
+                                    const double *lw, const double *ew, double *hyper, const int32_t *flags,
+                                    int32_t n0, int32_t dn, double fudge,
+                                    double *lh, double *eh, double *dh,
+                                    int32_t max_it, double tol, int32_t device,
+                                    double *ev_cell, int32_t *it_cell, int32_t *reason_cell,
+                                    int32_t *it, int32_t *reason, double *evidence,
+                                    double *history, int64_t history_rows);
 /* Constants of that kernel at rank r (host only; any out pointer may be NULL): the stored entries of a cell that the
  * workgroup's threads take in one pass (those of vbnmf_project_info), and the kernel time in ms of the calling thread's
- * most recent vbnmf_matrix_vb_project. */
+ * most recent vbnmf_matrix_vb_project or vbnmf_matrix_vb_project_coupled. */
 int vbnmf_vb_project_info(int32_t r, int32_t *pass_entries, double *last_kernel_ms);
 
 /* Cluster of every cell from the coefficients the engine holds:

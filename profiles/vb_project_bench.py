@@ -4,6 +4,7 @@ ranks 10 and 20: wall and kernel time to Tol = 1e-5 and the per-cell iteration c
 (csrc/project.h) on the same matrix with the posterior's E[W] as its basis, in the same process.
 
     python profiles/vb_project_bench.py [small]
+    python profiles/vb_project_bench.py coupled [small]      # the coupled form: profiles/vb_project_coupled_times.txt
 
 Prints the text of profiles/vb_project_times.txt.  One MI355X.  The posterior is what 30 VB steps (hyper-parameters 1, 1, 1, 1)
 from a random state leave on the same matrix: ew and sd = sqrt(dw) as a fit stores them; the cells placed are the matrix's own
@@ -72,9 +73,62 @@ def sweep(ranks):
     M.close()
 
 
+def fitted_pair(M, n, m, r, hyper):
+    """ew and sd = sqrt(dw) of what 30 VB steps from a random state leave on the matrix."""
+    eng = C.VBEngine(M, r)
+    wh = synth.random_state(n, m, r, hyper, seed=100 + r)
+    eng.set_state(wh["lw"], wh["lh"], wh["eh"])
+    for _ in range(30):
+        eng.step(hyper)
+    st = eng.get_state(("ew", "dw"))
+    eng.close()
+    return st["ew"], np.sqrt(st["dw"])
+
+
+def coupled(small):
+    """`python profiles/vb_project_bench.py coupled [small]`: time per iteration of the coupled form (k_vbp_step + k_vbp_control
+    per step, the host reading the control block every eight) next to the per-cell kernel's (kernel time over mean nsteps) on
+    the same posterior, in one process, interleaved, five repeats after a warm-up of each."""
+    t, (name, X, _) = timed(lambda: make_workload(small))
+    X = X.tocsc()
+    n, m = X.shape
+    say(f"{name}: n={n} m={m} stored entries={X.nnz} ({100.0 * X.nnz / n / m:.2f} %), generated in {t:.1f} s")
+    M = C.CountMatrix(X)
+    hyper = {"aw": 1.0, "bw": 1.0, "ah": 1.0, "bh": 1.0}
+    modes = (("cell", "per-cell kernel, stop=\"cell\"          ", {}),
+             ("off", "coupled, stop=\"global\", flags off    ", {"stop": "global"}),
+             ("on", "coupled, hyper_update=(True, True)     ", {"hyper_update": (True, True)}))
+    for r in (10, 20):
+        say(f"\n== rank {r} ==")
+        pair = fitted_pair(M, n, m, r, hyper)
+        per_it = {k: [] for k, _, _ in modes}
+        kern = {k: [] for k, _, _ in modes}
+        last = {}
+        for rep in range(REPS + 1):
+            for key, _, kw in modes:
+                p = C.vb_project(M, pair, hyper=hyper, Tol=1e-5, **kw)
+                last[key] = p
+                if rep:
+                    ms = P.vb_last_kernel_ms()
+                    kern[key].append(ms)
+                    per_it[key].append(ms / p.nsteps.mean())
+        for key, label, _ in modes:
+            p = last[key]
+            say(f"{label}: kernel ms {med(kern[key])} | mean iterations {p.nsteps.mean():.1f} (max {p.nsteps.max()}) | "
+                f"ms per iteration {med(per_it[key])}")
+            say(f"    reasons {dict(zip(*[a.tolist() for a in np.unique(p.reason, return_counts=True)]))}; evidence {p.evidence:.12g}; "
+                f"(ah, bh) {p.hyper0['ah']:.6g}, {p.hyper0['bh']:.6g} -> {p.hyper['ah']:.6g}, {p.hyper['bh']:.6g}")
+        base = sorted(per_it["cell"])[REPS // 2]
+        for key in ("off", "on"):
+            say(f"ms per iteration, {key} / per-cell: {sorted(per_it[key])[REPS // 2] / base:.3f}")
+    M.close()
+
+
 def main():
     if len(sys.argv) > 2 and sys.argv[1] == "sweep":
         return sweep([int(a) for a in sys.argv[2:]])
+    if len(sys.argv) > 1 and sys.argv[1] == "coupled":
+        return coupled(len(sys.argv) > 2 and sys.argv[2] == "small")
     small = len(sys.argv) > 1 and sys.argv[1] == "small"
     t, (name, X, _) = timed(lambda: make_workload(small))
     X = X.tocsc()
@@ -84,14 +138,7 @@ def main():
     hyper = {"aw": 1.0, "bw": 1.0, "ah": 1.0, "bh": 1.0}
     for r in (10, 20):
         say(f"\n== rank {r} ==")
-        eng = C.VBEngine(M, r)
-        wh = synth.random_state(n, m, r, hyper, seed=100 + r)
-        eng.set_state(wh["lw"], wh["lh"], wh["eh"])
-        for _ in range(30):
-            eng.step(hyper)
-        st = eng.get_state(("ew", "dw"))
-        eng.close()
-        pair = (st["ew"], np.sqrt(st["dw"]))
+        pair = fitted_pair(M, n, m, r, hyper)
         t_pb, _ = timed(lambda: C.posterior_basis(pair, hyper=hyper))
         say(f"posterior_basis (n r digammas on the host): {t_pb:.4f} s")
         walls, kerns = {"vb": [], "ml": []}, {"vb": [], "ml": []}
