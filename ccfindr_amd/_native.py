@@ -182,6 +182,8 @@ SIGNATURES = {
     "vbnmf_layout_destroy": (None, [_VP]),
     "vbnmf_test_special_host": (ctypes.c_int, [_I32, _I64, c_double_p, c_double_p]),
     "vbnmf_test_special_device": (ctypes.c_int, [_I32, _I64, c_double_p, c_double_p]),
+    "vbnmf_test_hyper_update_host": (ctypes.c_int, [_I64, c_int32_p, c_double_p, c_double_p, c_double_p, c_int32_p, c_int32_p, c_double_p]),
+    "vbnmf_test_hyper_update_device": (ctypes.c_int, [_I64, c_int32_p, c_double_p, c_double_p, c_double_p, c_int32_p, c_int32_p, c_double_p]),
     "vbnmf_test_svd_gram": (ctypes.c_int, [_I32, _I64, c_double_p, c_double_p]),
     "vbnmf_test_svd_small": (ctypes.c_int, [_I32, _I32, _I32, _I32, c_double_p, _D, c_double_p, c_double_p, c_double_p, c_double_p, c_int32_p]),
     "vbnmf_test_svd_apply": (ctypes.c_int, [_I32, _I64, c_double_p, c_double_p, _I32, c_double_p]),

@@ -2199,11 +2199,22 @@ void conn_finish(vbnmf_engine *const *engs, int count, int64_t *changes, int64_t
     }
 }
 
+// The four hyper-parameters a device-driven loop starts from: finite and > 0, or the Newton iteration of hyper_update
+// (dev_hyper_update_pair) would be handed a shape its special functions are not written for.  Checked before any launch.
+int check_hyper(const double *hyper)
+{
+    for (int q = 0; q < 4; q++)
+        if (!(hyper[q] > 0.0) || !std::isfinite(hyper[q]))
+            return fail(VBNMF_ERR_BAD_ARG, "aw, bw, ah and bh must be finite and > 0 (got %g, %g, %g, %g)", hyper[0], hyper[1], hyper[2], hyper[3]);
+    return VBNMF_OK;
+}
+
 int run_group(const LoopGroup &G, double *hyper, double fudge, int32_t max_it, double tol, int32_t n0, int32_t dn,
               const int32_t *flags, int32_t *it_out, double *lk0_out, double *lkh_out, int32_t *reason_out,
               double *history, int64_t history_rows)
 {
     if (!hyper || !flags) return fail(VBNMF_ERR_BAD_ARG, "NULL argument");
+    if (int rc = check_hyper(hyper)) return rc;
     if (max_it < 1 || dn < 1) return fail(VBNMF_ERR_BAD_ARG, "max_it and dn must be >= 1");
     if (history && history_rows < max_it) return fail(VBNMF_ERR_BAD_ARG, "history needs max_it rows of 9 doubles");
     for (int p = 0; p < G.count; p++) {
@@ -2356,6 +2367,7 @@ int vbnmf_batch_run(vbnmf_engine **engs, int32_t count, double *hyper, double fu
     if (max_it < 1 || dn < 1) return fail(VBNMF_ERR_BAD_ARG, "max_it and dn must be >= 1");
     if (history && history_rows < max_it) return fail(VBNMF_ERR_BAD_ARG, "history needs max_it rows of 9 doubles per engine");
     const int B = count;
+    for (int b = 0; b < B; b++) { if (int rc = check_hyper(hyper + (size_t)b * 4)) return rc; }
     if (int rc = batch_admit(engs, B, true, history ? (size_t)max_it * 9 : 0)) return rc;
     vbnmf_engine *e0 = engs[0];
 
@@ -3696,6 +3708,7 @@ int vbnmf_test_special_host(int32_t kind, int64_t n, const double *x, double *y)
             case 1: dev_psi_lgamma(x[i], &psi, &lg); y[i] = psi; break;
             case 2: dev_psi_lgamma(x[i], &psi, &lg); y[i] = lg; break;
             case 6: { static LogTabEntry tab[kLogTabSize]; static bool init = false; if (!init) { fill_log_table(tab); init = true; } y[i] = dev_log_tab(x[i], tab); break; }
+            case 7: y[i] = dev_trigamma(x[i]); break;
             default: y[i] = dev_div(1.0, x[i]); break;
         }
     }
@@ -3778,6 +3791,83 @@ constexpr int64_t kHookMaxRows = (int64_t)1 << 24;           // 8 GB of doubles 
 }  // namespace
 
 extern "C" {
+
+// ---- test hooks into hyper_update (reference R/bayesian.R:2-53) as the device-driven loops run it: `count` independent
+// cases, each with its flags[4], stats[4] = (mean log lw, mean log lh, mean ew, mean eh) and hyper_in[4] = (aw, bw, ah, bh).
+// Out per case: hyper_out[4], failed, iters (Newton iterations run) and trace[2][100]: side s's a1 of iteration k at
+// [100 s + k] (s = 0: aw, 1: ah), NaN where nothing was stored.
+// The host form runs the two sides one after the other through hyper_newton_side (special.h), the arithmetic the device's
+// lanes run; it takes any double (a shape that is not a positive number comes back failed).
+int vbnmf_test_hyper_update_host(int64_t count, const int32_t *flags, const double *stats, const double *hyper_in, double *hyper_out,
+                                 int32_t *failed, int32_t *iters, double *trace)
+{
+    if (!flags || !stats || !hyper_in || !hyper_out || !failed || !iters || !trace || count < 0) return fail(VBNMF_ERR_BAD_ARG, "NULL argument");
+    for (int64_t c = 0; c < count; c++) {
+        const int32_t *fl = flags + 4 * c;
+        const double *st = stats + 4 * c, *hi = hyper_in + 4 * c;
+        double *ho = hyper_out + 4 * c, *tr = trace + 200 * c;
+        for (int q = 0; q < 4; q++) ho[q] = hi[q];
+        for (int q = 0; q < 200; q++) tr[q] = __builtin_nan("");
+        failed[c] = 0; iters[c] = 0;
+        if (fl[0] + fl[1] + fl[2] + fl[3] == 0) continue;                                  // :4
+        double a0[2] = {hi[0], hi[2]}, a1[2] = {hi[0], hi[2]};
+        int f = 0, done = 0;
+        if (fl[0] + fl[2] > 0) {                                                           // :15
+            int i = 1;
+            while (i < 100) {
+                double u[2];
+                int bad = 0;
+                for (int s = 0; s < 2; s++) {
+                    int hv, b;
+                    a1[s] = hyper_newton_side(a0[s], hi[2 * s + 1], st[s], st[2 + s], fl[2 * s], &hv, &b);
+                    tr[100 * s + done] = a1[s];
+                    u[s] = b ? 0.0 : 1.0 - a1[s] / a0[s];
+                    bad |= b;
+                }
+                done++;
+                if (bad) { f = 1; break; }
+                if (u[0] * u[0] + u[1] * u[1] < 1e-3) break;                               // :37-38
+                a0[0] = a1[0]; a0[1] = a1[1]; i++;
+            }
+            if (i == 100) f = 1;                                                           // :43
+        }
+        iters[c] = done; failed[c] = f;
+        if (!f) { ho[0] = a1[0]; ho[1] = fl[1] ? st[2] : hi[1]; ho[2] = a1[1]; ho[3] = st[3]; }   // :48-51
+    }
+    return VBNMF_OK;
+}
+
+// The device form: one launch of k_test_hyper_update on device 0, one wave per case, lanes 0 and 1 in dev_hyper_update_pair.
+// A shape or scale that is not a positive finite number is VBNMF_ERR_BAD_ARG before any launch.
+int vbnmf_test_hyper_update_device(int64_t count, const int32_t *flags, const double *stats, const double *hyper_in, double *hyper_out,
+                                   int32_t *failed, int32_t *iters, double *trace)
+{
+    if (!flags || !stats || !hyper_in || !hyper_out || !failed || !iters || !trace) return fail(VBNMF_ERR_BAD_ARG, "NULL argument");
+    if (count < 1 || count > (1 << 20)) return fail(VBNMF_ERR_BAD_ARG, "count must be in [1, 2^20]");
+    for (int64_t q = 0; q < 4 * count; q++)
+        if (!(hyper_in[q] > 0.0) || !std::isfinite(hyper_in[q])) return fail(VBNMF_ERR_BAD_ARG, "hyper-parameters must be finite and > 0");
+    if (int rc = hook_device()) return rc;
+    HookBuffers hb;
+    const size_t n = (size_t)count;
+    double *dfl = nullptr, *dst = nullptr, *dhy = nullptr, *dfa = nullptr, *dit = nullptr, *dtr = nullptr;   // (the int32 arrays in double-sized buffers)
+    if (int rc = hb.alloc(&dfl, 2 * n)) return rc;
+    HIPCHECK(hipMemcpy(dfl, flags, 4 * n * sizeof(int32_t), hipMemcpyHostToDevice));
+    if (int rc = hb.upload(&dst, stats, 4 * n)) return rc;
+    if (int rc = hb.upload(&dhy, hyper_in, 4 * n)) return rc;
+    if (int rc = hb.alloc(&dfa, (n + 1) / 2)) return rc;
+    if (int rc = hb.alloc(&dit, (n + 1) / 2)) return rc;
+    if (int rc = hb.alloc(&dtr, 200 * n)) return rc;
+    HIPCHECK(hipMemset(dfa, 0, (n + 1) / 2 * sizeof(double)));
+    HIPCHECK(hipMemset(dit, 0, (n + 1) / 2 * sizeof(double)));
+    HIPCHECK(hipMemset(dtr, 0xFF, 200 * n * sizeof(double)));                              // NaN
+    hipLaunchKernelGGL(k_test_hyper_update, dim3((unsigned)n), dim3(64), 0, nullptr, (int)count, (const int32_t *)dfl, (const double *)dst,
+                       dhy, (int32_t *)dfa, (int32_t *)dit, dtr);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipMemcpy(failed, dfa, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIPCHECK(hipMemcpy(iters, dit, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (int rc = download(hyper_out, dhy, 4 * n)) return rc;
+    return download(trace, dtr, 200 * n);
+}
 
 // ---- test hooks into the dense kernels of the truncated SVD (init.h), each with the launch geometry of
 // vbnmf_engine_svd: upload, one launch of the product's kernel on the null stream, download
@@ -4534,7 +4624,8 @@ int vbnmf_matrix_vb_project_coupled(const vbnmf_matrix *X, int64_t col_begin, in
         return fail(VBNMF_ERR_BAD_ARG, "column range [%lld, %lld) is empty or outside the matrix's %lld columns", (long long)col_begin,
                     (long long)col_end, (long long)X->M.m);
     if (max_it < 1) return fail(VBNMF_ERR_BAD_ARG, "max_it must be >= 1");
-    if (!(hyper[0] > 0.0) || !(hyper[1] > 0.0)) return fail(VBNMF_ERR_BAD_ARG, "ah and bh must be > 0 (got %g, %g)", hyper[0], hyper[1]);
+    if (!(hyper[0] > 0.0) || !(hyper[1] > 0.0) || !std::isfinite(hyper[0]) || !std::isfinite(hyper[1]))
+        return fail(VBNMF_ERR_BAD_ARG, "ah and bh must be > 0 and finite (got %g, %g)", hyper[0], hyper[1]);
     if (dn < 1) return fail(VBNMF_ERR_BAD_ARG, "dn must be >= 1");
     if (n0 < 0) return fail(VBNMF_ERR_BAD_ARG, "n0 must be >= 0");
     if (int rc = check_device(device)) return rc;

@@ -909,7 +909,9 @@ struct LoopCtl {
     int32_t zstep, ncnn_step;      // steps in a row without a changed pair / how many of them end the run
 };
 
-__device__ inline int dev_hyper_update_pair(const int32_t *flags, const double *stats, double *hyper, int lane);
+template <bool TRACE = false>
+__device__ inline int dev_hyper_update_pair(const int32_t *flags, const double *stats, double *hyper, int lane,
+                                            double *trace = nullptr, int32_t *iters = nullptr);
 __device__ __forceinline__ double block_sum(double s, double *sm);
 
 // Device-driven loop of an unpartitioned engine: the control step (k_control below: the evidence of the step just swept,
@@ -1625,23 +1627,18 @@ __global__ __launch_bounds__(1024) void k_final(const double *__restrict__ bpW, 
 // Device-resident driver loop: hyper_update (reference R/bayesian.R:2-53) and the loop control of
 // vb_iterate (R/bayesian.R:342-348) after each step, by one thread.
 // ------------------------------------------------------------------------------------
-__device__ inline double dev_trigamma(double x)
-{
-    double s = 0.0;
-    while (x < 10.0) { s += 1.0 / (x * x); x += 1.0; }
-    const double xi = 1.0 / x, y = xi * xi;
-    const double ser = xi * y * (1.0 / 6 - y * (1.0 / 30 - y * (1.0 / 42 - y * (1.0 / 30 - y * (5.0 / 66 - y * (691.0 / 2730 - y * (7.0 / 6)))))));
-    return s + xi + 0.5 * y + ser;
-}
-__device__ inline double dev_digamma1(double x) { double p, g; dev_psi_lgamma(x, &p, &g); return (x > 0.0) ? p : __builtin_nan(""); }
-
+// (digamma, trigamma and one side's share of a Newton iteration: special.h, dev_digamma1 / dev_trigamma / hyper_newton_side.)
 // hyper_update (R/bayesian.R:2-53) by lanes 0 and 1 of a wave side by side: lane 0 iterates aw, lane 1 ah -- the two
 // Newton recurrences (:19-27) only meet in the convergence test (:37), which the lanes form by exchanging their
 // terms, so both run the same number of iterations as the sequential form and reach the same values.  A dependent fp64
 // chain (log, digamma, trigamma) costs microseconds on one lane; this halves it.
 // Returns 0, or 1 when the Newton iteration does not converge ("Hyper-parameter update failed to converge", :43);
 // lane 0 stores the four new hyper-parameters.
-__device__ inline int dev_hyper_update_pair(const int32_t *flags, const double *stats, double *hyper, int lane)
+// TRACE (the test hook k_test_hyper_update only; the loops instantiate TRACE = false, which compiles the stores away):
+// each lane stores its a1 of iteration k (0-based) to trace[100 * lane + k], lane 0 the number of iterations to *iters.
+template <bool TRACE>
+__device__ inline int dev_hyper_update_pair(const int32_t *flags, const double *stats, double *hyper, int lane, double *trace,
+                                            int32_t *iters)
 {
     if (flags[0] + flags[1] + flags[2] + flags[3] == 0) return 0;                          // :4
     double a0 = hyper[2 * lane];                           // aw (lane 0) or ah (lane 1)
@@ -1650,20 +1647,14 @@ __device__ inline int dev_hyper_update_pair(const int32_t *flags, const double *
     const int fa = flags[2 * lane];
     double a1 = a0;
     int failed = 0;
+    [[maybe_unused]] int done = 0;                         // iterations run (TRACE)
     if (flags[0] + flags[2] > 0) {                                                         // :15
         int i = 1;
         while (i < 100) {                                                                  // Niter = 100 (:343)
-            double d = fa ? (log(a0) - dev_digamma1(a0) - em / b0 + 1.0 + lm - log(b0)) / (1.0 / a0 - dev_trigamma(a0)) : 0.0;
-            // A non-finite step (a statistic of -inf: fudge = 0 with a shape so small that exp(psi) underflows to 0)
-            // would make the reference's halving loop below spin for ever -- on the host there, on the GPU here.
-            // It is reported as a failed hyper-parameter update (reason 3) instead; the halvings are bounded too
-            // (a finite d reaches a1 > 0 in < 1100 of them).
-            int bad = !(fabs(d) <= 1.79769313486231570815e308);
-            a1 = a0 - d;
-            for (int hv = 0; !bad && a1 <= 0.0; hv++) {                                    // :28-35
-                d *= 0.5; a1 = a0 - d;
-                if (hv >= 1100) bad = 1;
-            }
+            // A non-finite step is reported as a failed hyper-parameter update (reason 3): see hyper_newton_side.
+            int hv, bad;
+            a1 = hyper_newton_side(a0, b0, lm, em, fa, &hv, &bad);                         // :18-35
+            if constexpr (TRACE) trace[100 * lane + done++] = a1;
             const double u = bad ? 0.0 : 1.0 - a1 / a0;
             const double uw = __shfl(u, 0, 64), uh = __shfl(u, 1, 64);
             bad = __shfl(bad, 0, 64) | __shfl(bad, 1, 64);
@@ -1673,6 +1664,7 @@ __device__ inline int dev_hyper_update_pair(const int32_t *flags, const double *
         }
         if (i == 100) failed = 1;
     }
+    if constexpr (TRACE) { if (lane == 0) *iters = done; }
     const double aw1 = __shfl(a1, 0, 64), ah1 = __shfl(a1, 1, 64);
     if (lane == 0 && !failed) {
         hyper[0] = aw1; hyper[1] = flags[1] ? stats[2] : hyper[1];                         // :48-49
@@ -1764,8 +1756,22 @@ __global__ void k_test_special(int kind, int64_t n, const double *__restrict__ x
         case 3: y[i] = dev_div(1.0, x[i]); break;
         case 4: y[i] = sp_rcp_seed(x[i]); break;             // raw v_rcp_f64
         case 5: y[i] = (double)__builtin_amdgcn_rcpf((float)x[i]); break;   // raw v_rcp_f32
+        case 7: y[i] = dev_trigamma(x[i]); break;
         default: y[i] = dev_log_tab(x[i], tab); break;
     }
+}
+
+// Device-side evaluation of hyper_update, for tests (tests/test_gpu_hyper_update.py): one wave per case, lanes 0 and 1 in
+// the loops' own dev_hyper_update_pair, traced.  hyper: [count][4] in / out; trace: [count][2][100]; iters, failed: [count].
+__global__ __launch_bounds__(64) void k_test_hyper_update(int count, const int32_t *__restrict__ flags, const double *__restrict__ stats,
+                                                          double *hyper, int32_t *__restrict__ failed, int32_t *__restrict__ iters,
+                                                          double *trace)
+{
+    const int c = blockIdx.x, lane = threadIdx.x;
+    if (c >= count || lane > 1) return;
+    const int f = dev_hyper_update_pair<true>(flags + 4 * (size_t)c, stats + 4 * (size_t)c, hyper + 4 * (size_t)c, lane,
+                                              trace + 200 * (size_t)c, iters + c);
+    if (lane == 0) failed[c] = f;
 }
 
 }  // namespace vbnmf

@@ -1,4 +1,5 @@
-// special.h -- fp64 special functions for gfx950 device code: ln, digamma, log-gamma.
+// special.h -- fp64 special functions for gfx950 device code: ln, digamma, log-gamma; trigamma and the Newton step of
+// the hyper-parameter update at the end.
 //
 // The reference evaluates psi and ln Gamma through GSL (gsl_sf_psi, gsl_sf_lngamma; reference
 // src/vbnmf_update.cpp:59,63,82,85,87,89).  HIP has no digamma, ocml's log costs ~95
@@ -168,6 +169,42 @@ __host__ __device__ __forceinline__ void dev_psi_lgamma(double x, double *psi, d
     sg = fma(-y2, sg, 1.0 / 12);
     const double half_log_2pi = 0.91893853320467274178;
     *lgam = (((y - 0.5) * ly - y) + half_log_2pi + yi * sg) - (big ? 0.0 : dev_log(D));
+}
+
+// ---- the hyper-parameter Newton update (reference R/bayesian.R:2-53): R's digamma() and psigamma(x, 1) at :19-24, and
+// one lane's share of one iteration.  __host__ __device__, so the host build can be held to mpmath as well
+// (tests/test_hyper_update_cpu.py through vbnmf_test_special_host / vbnmf_test_hyper_update_host).
+__host__ __device__ inline double dev_digamma1(double x) { double p, g; dev_psi_lgamma(x, &p, &g); return (x > 0.0) ? p : __builtin_nan(""); }
+
+// psi'(x), x > 0: the recurrence psi'(x) = psi'(x+1) + 1/x^2 up to x >= 10, then the asymptotic series.  Anything else
+// (x <= 0, NaN, +-inf) is NaN BEFORE the shift loop: from |x| >= 2^53 on x + 1 == x and the loop would never end.
+__host__ __device__ inline double dev_trigamma(double x)
+{
+    if (!(x > 0.0) || !(x <= 1.79769313486231570815e308)) return __builtin_nan("");
+    double s = 0.0;
+    while (x < 10.0) { s += 1.0 / (x * x); x += 1.0; }
+    const double xi = 1.0 / x, y = xi * xi;
+    const double ser = xi * y * (1.0 / 6 - y * (1.0 / 30 - y * (1.0 / 42 - y * (1.0 / 30 - y * (5.0 / 66 - y * (691.0 / 2730 - y * (7.0 / 6)))))));
+    return s + xi + 0.5 * y + ser;
+}
+
+// One side (aw or ah) of one Newton iteration of hyper_update: the step d (:19-25; 0 with the side's flag off), a1 = a0 - d
+// (:26-27) and the halvings of d while a1 <= 0 (:28-35).  A non-finite step (a statistic of -inf: fudge = 0 with a shape
+// so small that exp(psi) underflows to 0; a shape that is not a positive number) would make the reference's halving
+// loop spin for ever -- on the host there, on the GPU here.  It comes back as *bad = 1 instead, which the caller reports
+// as a failed hyper-parameter update; the halvings are bounded too (a finite d reaches a1 > 0 in < 1100 of them).
+__host__ __device__ inline double hyper_newton_side(double a0, double b0, double lm, double em, int fa, int *halvings, int *bad_out)
+{
+    double d = fa ? (log(a0) - dev_digamma1(a0) - em / b0 + 1.0 + lm - log(b0)) / (1.0 / a0 - dev_trigamma(a0)) : 0.0;
+    int bad = !(fabs(d) <= 1.79769313486231570815e308);
+    double a1 = a0 - d;
+    int hv = 0;
+    for (; !bad && a1 <= 0.0; hv++) {                                                      // :28-35
+        d *= 0.5; a1 = a0 - d;
+        if (hv >= 1100) bad = 1;
+    }
+    *halvings = hv; *bad_out = bad;
+    return a1;
 }
 
 }  // namespace vbnmf

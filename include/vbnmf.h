@@ -766,10 +766,22 @@ void vbnmf_layout_destroy(vbnmf_layout *L);
  * and GSL's gsl_sf_psi / gsl_sf_lngamma, reference src/vbnmf_update.cpp:59,63,73,81-89),
  * evaluated on the host build and on the device, so tests can check them against mpmath.
  * kind: 0 = ln(x), 1 = psi(x), 2 = lnGamma(x), 3 = 1/x, 4/5 = raw hardware reciprocal seeds
- * (device only), 6 = the sweep's table-driven ln(x).
+ * (device only), 6 = the sweep's table-driven ln(x), 7 = psi'(x) of the hyper-parameter Newton update (NaN unless x is
+ * a positive finite number).
  * --------------------------------------------------------------------------------- */
 int vbnmf_test_special_host(int32_t kind, int64_t n, const double *x, double *y);
 int vbnmf_test_special_device(int32_t kind, int64_t n, const double *x, double *y);
+/* Test hooks into hyper_update (reference R/bayesian.R:2-53) as the device-driven loops end each step with it: `count`
+ * independent cases, case c with flags[4c..] (hyper.update), stats[4c..] = (mean log lw, mean log lh, mean ew, mean eh) and
+ * hyper_in[4c..] = (aw, bw, ah, bh).  Out: hyper_out[4c..] (the input, bit for bit, when the update failed or no flag is
+ * set), failed[c], iters[c] = Newton iterations run, and trace[200c + 100s + k] = side s's shape (0: aw, 1: ah) after
+ * iteration k, NaN where nothing was stored.  _device: one launch on device 0, one wave per case, lanes 0 and 1 in the
+ * loops' own two-lane routine; a hyper-parameter that is not finite and > 0 is VBNMF_ERR_BAD_ARG before the launch.
+ * _host: the same per-side arithmetic, the two sides in sequence, on the CPU; takes any double. */
+int vbnmf_test_hyper_update_host(int64_t count, const int32_t *flags, const double *stats, const double *hyper_in,
+                                 double *hyper_out, int32_t *failed, int32_t *iters, double *trace);
+int vbnmf_test_hyper_update_device(int64_t count, const int32_t *flags, const double *stats, const double *hyper_in,
+                                   double *hyper_out, int32_t *failed, int32_t *iters, double *trace);
 /* Test hooks into the dense kernels of the device-resident truncated SVD (csrc/init.h: k_gram, k_small, k_apply,
  * k_normal_init), one launch each with the geometry vbnmf_engine_svd uses, on device 0: host arrays are uploaded, the
  * product's own kernel runs, the results are downloaded (tests/test_gpu_svd_dense.py).  R is the padded width of the
