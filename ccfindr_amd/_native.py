@@ -159,6 +159,10 @@ SIGNATURES = {
                                                        c_double_p, c_double_p, c_double_p, _I32, _D, _I32, c_double_p, c_int32_p,
                                                        c_int32_p, c_int32_p, c_int32_p, c_double_p, c_double_p, _I64]),
     "vbnmf_vb_project_info": (ctypes.c_int, [_I32, c_int32_p, c_double_p]),
+    "vbnmf_matrix_gene_stats": (ctypes.c_int, [_VP, _I32, _I32, c_int64_p, c_double_p, c_double_p, c_int32_p, c_int64_p]),
+    "vbnmf_matrix_col_sums": (ctypes.c_int, [_VP, _I64, _I64, c_double_p]),
+    "vbnmf_qc_info": (ctypes.c_int, [c_int32_p, c_int32_p, c_int32_p, c_int32_p, c_double_p]),
+    "vbnmf_test_gene_mode_host": (ctypes.c_int, [_I64, _I64, c_double_p, c_int32_p]),
     "vbnmf_engine_cluster_ids": (ctypes.c_int, [_VP, c_int32_p]),
     "vbnmf_engine_spmm": (ctypes.c_int, [_VP, _I32, c_double_p, c_double_p]),
     "vbnmf_engine_cluster_changes": (ctypes.c_int, [_VP, c_int64_p, c_int32_p]),

@@ -98,6 +98,11 @@ double sum_lgamma_x1(const Matrix &X, int64_t cb, int64_t ce);
 // sum over stored entries of -x log x + x (the constant of the ML-NMF likelihood, reference R/factorize.R:46-47).
 double sum_xlogx(const Matrix &X, int64_t cb, int64_t ce);
 
+// has_mode (reference R/utils.R:329-339) of one row with `len` stored (non-zero) values among m cells, by an exact sort-and-count:
+// the levels are the distinct values present, zeros included (m - len of them, when that is positive), in ascending order; 1 iff
+// some level has fewer occurrences than the next one.  Distinct doubles are distinct levels.  host.cpp
+int gene_mode_host(int64_t m, int64_t len, const double *values);
+
 // ---- tiled device layout of one side (DESIGN.md "Data layout in HBM") ----
 //
 // A *task* is a run of at most `max_len` stored entries of one major (gene on side 0, cell

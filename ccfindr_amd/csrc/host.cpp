@@ -399,6 +399,29 @@ double sum_xlogx(const Matrix &X, int64_t cb, int64_t ce)
     return sum_over_entries(X, cb, ce, [](double v) { return v > 0.0 ? -v * std::log(v) + v : 0.0; });
 }
 
+int gene_mode_host(int64_t m, int64_t len, const double *values)
+{
+    std::vector<double> v(values, values + len);
+    std::sort(v.begin(), v.end());
+    const int64_t zeros = m - len;
+    int64_t prev = 0;                                    // occurrences of the level before (0: there is none yet)
+    bool zero_done = zeros <= 0;
+    for (int64_t q = 0; q < len;) {
+        if (!zero_done && v[q] > 0.0) {                  // the zeros' level sits between the negative and the positive values
+            if (prev && prev < zeros) return 1;
+            prev = zeros;
+            zero_done = true;
+        }
+        int64_t e = q + 1;
+        while (e < len && v[e] == v[q]) e++;
+        if (prev && prev < e - q) return 1;
+        prev = e - q;
+        q = e;
+    }
+    if (!zero_done && prev && prev < zeros) return 1;    // (every stored value negative)
+    return 0;
+}
+
 int check_dims(int64_t n, int64_t m)
 {
     if (n <= 0 || m <= 0) return fail(VBNMF_ERR_BAD_ARG, "matrix dimensions must be positive (got %lld x %lld)", (long long)n, (long long)m);
@@ -510,6 +533,37 @@ int vbnmf_matrix_empty_counts(const vbnmf_matrix *X, int64_t *empty_rows, int64_
     }
     if (empty_rows) *empty_rows = er;
     if (empty_cols) *empty_cols = ec;
+    return VBNMF_OK;
+}
+
+int vbnmf_matrix_col_sums(const vbnmf_matrix *X, int64_t col_begin, int64_t col_end, double *sums)
+{
+    if (!X || !sums) return fail(VBNMF_ERR_BAD_ARG, "NULL argument");
+    if (X->M.shell) return fail(VBNMF_ERR_STATE, "this matrix handle is a shell (vbnmf_matrix_shell): it holds no entries");
+    const Matrix &M = X->M;
+    if (col_begin < 0 || col_end > M.m || col_begin > col_end)
+        return fail(VBNMF_ERR_BAD_ARG, "column range [%lld, %lld) is outside the matrix's %lld columns", (long long)col_begin,
+                    (long long)col_end, (long long)M.m);
+    // Matrix::colSums (R/utils.R:81, :321): a sequential sum down each stored column, rows ascending
+    parallel_for(col_end - col_begin, [&](int64_t b, int64_t e, int) {
+        for (int64_t j = col_begin + b; j < col_begin + e; j++) {
+            double s = 0.0;
+            for (int64_t q = M.colptr[j]; q < M.colptr[j + 1]; q++) s += M.val[q];
+            sums[j - col_begin] = s;
+        }
+    });
+    return VBNMF_OK;
+}
+
+int vbnmf_test_gene_mode_host(int64_t m, int64_t len, const double *values, int32_t *out)
+{
+    if (!out || (!values && len > 0)) return fail(VBNMF_ERR_BAD_ARG, "NULL argument");
+    if (len < 0 || len > m) return fail(VBNMF_ERR_BAD_ARG, "a row of %lld cells cannot hold %lld stored values", (long long)m, (long long)len);
+    try {
+        *out = gene_mode_host(m, len, values);
+    } catch (const std::bad_alloc &) {
+        return fail(VBNMF_ERR_OOM, "out of host memory sorting a row of %lld values", (long long)len);
+    }
     return VBNMF_OK;
 }
 

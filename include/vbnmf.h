@@ -588,6 +588,43 @@ int vbnmf_matrix_vb_project_coupled(const vbnmf_matrix *X, int64_t col_begin, in
  * most recent vbnmf_matrix_vb_project or vbnmf_matrix_vb_project_coupled. */
 int vbnmf_vb_project_info(int32_t r, int32_t *pass_entries, double *last_kernel_ms);
 
+/* ---------------------------------------------------------------------------------
+ * Quality control between the file and the fit: what filter_cells / filter_genes (R/utils.R:78-95, :134-194) compute
+ * from the counts.  The gene side -- the reference's slow part: calc_vmr densifies (x - means)^2 or loops over the genes
+ * (:208-214, :341-344), the gene rescue calls has_mode row by row (:166-171) -- is one launch over the genes' rows on HIP
+ * device `device` (csrc/qc.h); the cell totals are a host pass.
+ * --------------------------------------------------------------------------------- */
+/* Per gene i of the whole matrix, from the stored values of its row (grouped by gene on the library's host threads, then
+ * uploaded: as 2- or 4-byte integers where every stored value is an integer that fits, else as doubles):
+ *   nnz[i]  = stored entries: ncexpr of R/utils.R:139
+ *   sum[i]  = sum_j x_ij; the mean of :199 is sum / m
+ *   ss[i]   = sum_j (x_ij - mu_i)^2 over all m cells, mu_i = sum[i] / m formed on the device, in the centred form of
+ *             :211-212 and :343: the stored entries' (x - mu)^2 plus (m - nnz) mu^2.  The caller divides by m (:212) or m - 1 (:343).
+ *   mode[i] = has_mode(row i) of :329-339 as its code runs: 1 iff, among the distinct values PRESENT in the row (zeros included,
+ *             m - nnz of them; ascending), some value has fewer occurrences than the next present one.  Distinct doubles are
+ *             distinct values (R's table() merges doubles that agree to 15 significant digits).
+ * The kernel decides rows whose values are all integers in [1, hist_bins) with an occurrence table in LDS; the other rows are
+ * finished on the host by an exact sort-and-count, host_finished (may be NULL) = their number.  mode holds 0 or 1 on return.
+ * hist_bins = 0: the default (vbnmf_qc_info); outside [2, 15360] (the table and the kernel's other 2176 bytes fit the 64 KB of
+ * LDS a launch may take): VBNMF_ERR_BAD_ARG.  A shell matrix: VBNMF_ERR_STATE.  No usable device: VBNMF_ERR_NO_DEVICE (checked
+ * after the arguments).  Sums are formed in a fixed order (csrc/qc.h) without floating-point atomics: the same matrix gives the
+ * same bits on every call. */
+int vbnmf_matrix_gene_stats(const vbnmf_matrix *X, int32_t device, int32_t hist_bins, int64_t *nnz, double *sum, double *ss,
+                            int32_t *mode, int64_t *host_finished);
+/* Matrix::colSums of columns [col_begin, col_end) (R/utils.R:81 filter_cells, :321 normalize_count): each stored column added
+ * sequentially, rows ascending -- bit-equal to that sum, on the library's host threads.  Host only: a column's total is one
+ * pass over entries the host already holds, cheaper than any upload.  A shell matrix: VBNMF_ERR_STATE. */
+int vbnmf_matrix_col_sums(const vbnmf_matrix *X, int64_t col_begin, int64_t col_end, double *sums);
+/* Constants of k_gene_stats and the calling thread's last vbnmf_matrix_gene_stats (any out pointer may be NULL):
+ * short_row_max = the longest row one wave takes alone (R/utils.R:139's ncexpr decides the class); pass_entries = entries of a
+ * longer row the workgroup takes per pass -- a ticket of the persistent grid is pass_entries / 64 consecutive rows, one per
+ * wave; default_hist_bins; grid_workgroups = the persistent grid's size on device 0 (0 without a device); times_ms[4] = grouping
+ * by gene, upload, kernel (device events), host finish (:166-171's rows the kernel left), in ms. */
+int vbnmf_qc_info(int32_t *short_row_max, int32_t *pass_entries, int32_t *default_hist_bins, int32_t *grid_workgroups, double *times_ms);
+/* Test hook (host only): the host finisher on one row -- has_mode (R/utils.R:329-339) of `len` stored non-zero values among m
+ * cells, by sort-and-count.  len outside [0, m]: VBNMF_ERR_BAD_ARG. */
+int vbnmf_test_gene_mode_host(int64_t m, int64_t len, const double *values, int32_t *out);
+
 /* Cluster of every cell from the coefficients the engine holds:
  * ids[j] = which.max(h[, j])[1], 1-based, first maximum on ties (R/factorize.R:55-56 inside
  * connectivity(), R/utils.R:906 cluster_id); h = the ML coefficient matrix, or E[H] of a VB
