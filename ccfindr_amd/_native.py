@@ -163,6 +163,9 @@ SIGNATURES = {
     "vbnmf_matrix_col_sums": (ctypes.c_int, [_VP, _I64, _I64, c_double_p]),
     "vbnmf_qc_info": (ctypes.c_int, [c_int32_p, c_int32_p, c_int32_p, c_int32_p, c_double_p]),
     "vbnmf_test_gene_mode_host": (ctypes.c_int, [_I64, _I64, c_double_p, c_int32_p]),
+    "vbnmf_gsea_perm": (ctypes.c_int, [_I32, _I64, _I32, _I32, c_uint8_p, c_double_p, c_int64_p, c_int32_p, c_uint8_p, _I64, c_int32_p,
+                                       c_double_p, c_int64_p, c_double_p]),
+    "vbnmf_gsea_info": (ctypes.c_int, [_I64, c_int32_p, c_int32_p, c_int32_p, c_int64_p, c_double_p]),
     "vbnmf_engine_cluster_ids": (ctypes.c_int, [_VP, c_int32_p]),
     "vbnmf_engine_spmm": (ctypes.c_int, [_VP, _I32, c_double_p, c_double_p]),
     "vbnmf_engine_cluster_changes": (ctypes.c_int, [_VP, c_int64_p, c_int32_p]),

@@ -38,6 +38,7 @@
 #include "project.h"
 #include "vbproject.h"
 #include "qc.h"
+#include "gsea.h"
 #include "init.h"
 #include "consensus.h"
 #include "cophenet.h"
@@ -4783,6 +4784,267 @@ int vbnmf_qc_info(int32_t *short_row_max, int32_t *pass_entries, int32_t *defaul
     }
     if (times_ms)
         for (int k = 0; k < 4; k++) times_ms[k] = tl_qc_times_ms[k];
+    return VBNMF_OK;
+}
+
+}  // extern "C"
+
+// ---- enrichment scores of assign_celltype's permutation loop (gsea.h): every argument is checked and the permutations are
+// inverted on the host, the tables go up once, then one launch of k_gsea_perm per chunk of permutations (the identity first:
+// the observed scores come from the same code) and one of k_gsea_count.
+namespace {
+
+thread_local double tl_gsea_times_ms[4] = {0.0, 0.0, 0.0, 0.0};   // upload, kernels (device events), read-back, host checks + inversion
+
+constexpr int64_t kGseaChunkBytes = 64ll << 20;                   // permutations of one upload: inverse + permutation rows within this
+
+// permutations of one chunk for a table of N rows; VBNMF_GSEA_CHUNK_PERMS (>= 1) makes it smaller
+int64_t gsea_chunk_perms(int64_t N)
+{
+    int64_t c = kGseaChunkBytes / (8 * std::max<int64_t>(N, 1));
+    c = std::max<int64_t>(1, std::min<int64_t>(c, 1 << 20));
+    if (const char *s = getenv("VBNMF_GSEA_CHUNK_PERMS")) {
+        const long v = atol(s);
+        if (v >= 1 && v < c) c = v;
+    }
+    return c;
+}
+
+struct GseaDevice {
+    int32_t *inv = nullptr, *perms = nullptr, *hit_row = nullptr, *M = nullptr, *prefix = nullptr;
+    uint8_t *valid = nullptr, *has_na = nullptr, *hit_is_miss = nullptr;
+    double *wp = nullptr, *es = nullptr, *null_es = nullptr;
+    int64_t *hit_ptr = nullptr;
+    long long *exceed = nullptr;
+    unsigned long long *words = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    bool queued = false;
+    int caller_device = -1;
+    ~GseaDevice()
+    {
+        if (queued) (void)hipStreamSynchronize(nullptr);
+        dev_free(inv); dev_free(perms); dev_free(hit_row); dev_free(M); dev_free(prefix); dev_free(valid); dev_free(has_na);
+        dev_free(hit_is_miss); dev_free(wp); dev_free(es); dev_free(null_es); dev_free(hit_ptr); dev_free(exceed); dev_free(words);
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+        if (caller_device >= 0) (void)hipSetDevice(caller_device);
+    }
+};
+
+// what the host derives from the checked arguments
+struct GseaHost {
+    std::vector<int32_t> M;            // [r x nS]
+    std::vector<uint8_t> has_na;       // [r]
+    std::unique_ptr<int32_t[]> inv;    // [nperm x N], every entry written by gsea_check
+    bool any_na = false;
+    int pad = 1;
+};
+
+int gsea_check(int64_t N, int32_t r, int32_t nS, const uint8_t *valid, const double *wp, const int64_t *hit_ptr, const int32_t *hit_row,
+               const uint8_t *hit_is_miss, int64_t nperm, const int32_t *perms, GseaHost &H)
+{
+    const int64_t nks = (int64_t)r * nS;
+    if (hit_ptr[0] != 0) return fail(VBNMF_ERR_BAD_ARG, "hit_ptr must start at 0");
+    for (int64_t q = 0; q < nks; q++)
+        if (hit_ptr[q + 1] < hit_ptr[q] || hit_ptr[q + 1] - hit_ptr[q] > N)
+            return fail(VBNMF_ERR_BAD_ARG, "hit_ptr is not ascending, or a set has more hits than the table has rows (cluster %lld, set %lld)",
+                        (long long)(q / nS), (long long)(q % nS));
+    if (hit_ptr[nks] > 0 && (!hit_row || !hit_is_miss)) return fail(VBNMF_ERR_BAD_ARG, "NULL argument");
+    H.M.assign((size_t)nks, 0);
+    H.has_na.assign((size_t)r, 0);
+    int64_t maxT = 0;
+    for (int32_t k = 0; k < r; k++) {
+        const uint8_t *v = valid + (int64_t)k * N;
+        int64_t nvalid = 0;
+        for (int64_t i = 0; i < N; i++) nvalid += v[i] != 0;
+        // x * gw^p of R/gsea.R:101 is NaN on a row that is no hit when its weight is not finite; the hits' walk would not see it
+        for (int64_t i = 0; i < N; i++)
+            if (v[i] && !std::isfinite(wp[(int64_t)k * N + i]))
+                return fail(VBNMF_ERR_BAD_ARG, "cluster %d, row %lld: the weight gw^p is not finite", k, (long long)i);
+        H.has_na[(size_t)k] = nvalid < N ? 1 : 0;
+        H.any_na = H.any_na || nvalid < N;
+        for (int32_t s = 0; s < nS; s++) {
+            const int64_t q = (int64_t)k * nS + s;
+            int64_t notmiss = 0, prev = -1;
+            for (int64_t h = hit_ptr[q]; h < hit_ptr[q + 1]; h++) {
+                const int64_t row = hit_row[h];
+                if (row <= prev || row >= N)
+                    return fail(VBNMF_ERR_BAD_ARG, "the hit rows of cluster %d, set %d are not ascending within [0, %lld)", k, s, (long long)N);
+                if (!v[row]) return fail(VBNMF_ERR_BAD_ARG, "cluster %d, set %d: hit row %lld is an NA row (R/gsea.R:93 drops it before the overlap)", k, s, (long long)row);
+                prev = row;
+                notmiss += hit_is_miss[h] == 0;
+            }
+            const int64_t T = hit_ptr[q + 1] - hit_ptr[q], M = nvalid - notmiss;
+            H.M[(size_t)q] = (int32_t)M;
+            if (T > 0 && M > 0) {
+                if (T > kGseaMaxSetHits)
+                    return fail(VBNMF_ERR_BAD_ARG, "cluster %d, set %d has %lld hits; at most %d are sorted in LDS (vbnmf_gsea_info)", k, s, (long long)T, kGseaMaxSetHits);
+                maxT = std::max(maxT, T);
+            }
+        }
+    }
+    while (H.pad < maxT) H.pad <<= 1;
+    // the inverse of every permutation; a row that is none is found here
+    H.inv.reset(new int32_t[std::max<size_t>((size_t)nperm * (size_t)N, 1)]);       // (not initialised: the workers' pages, below)
+    std::atomic<int64_t> bad{-1};
+    parallel_for(nperm, [&](int64_t b0, int64_t b1, int) {
+        for (int64_t b = b0; b < b1; b++) {
+            const int32_t *p = perms + b * N;
+            int32_t *iv = H.inv.get() + b * N;
+            // N entries inside [0, N) are a permutation iff none repeats; of a repeated row the last position stays in iv, so
+            // an earlier one does not read itself back.  Then every entry of iv has been written.
+            bool ok = true;
+            for (int64_t i = 0; i < N && ok; i++) ok = p[i] >= 0 && p[i] < N;
+            if (ok) {
+                for (int64_t i = 0; i < N; i++) iv[p[i]] = (int32_t)i;
+                for (int64_t i = 0; i < N && ok; i++) ok = iv[p[i]] == (int32_t)i;
+            }
+            if (!ok) { int64_t none = -1; bad.compare_exchange_strong(none, b); }
+        }
+    });
+    if (bad.load() >= 0) return fail(VBNMF_ERR_BAD_ARG, "row %lld of perms is no permutation of 0 .. %lld", (long long)bad.load(), (long long)N - 1);
+    return VBNMF_OK;
+}
+
+int gsea_grid(int cus) { return (cus > 0 ? cus : 256) * (2048 / kGseaThreads); }
+
+int gsea_run(int32_t device, int64_t N, int32_t r, int32_t nS, const uint8_t *valid, const double *wp, const int64_t *hit_ptr,
+             const int32_t *hit_row, const uint8_t *hit_is_miss, int64_t nperm, const int32_t *perms, const GseaHost &H,
+             double *es, int64_t *exceed, double *null_es)
+{
+    using clock = std::chrono::steady_clock;
+    auto ms_since = [](clock::time_point t0) { return std::chrono::duration<double, std::milli>(clock::now() - t0).count(); };
+    const int64_t nks = (int64_t)r * nS, nq = nks, nW = (N + 63) / 64;
+    const int64_t chunk = std::min<int64_t>(gsea_chunk_perms(N), std::max<int64_t>(nperm, 1));
+    GseaDevice D;
+    (void)hipGetDevice(&D.caller_device);
+    HIPCHECK(hipSetDevice(device));
+    int cus = 0;
+    HIPCHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
+    const int64_t max_items = std::max<int64_t>(chunk, 1) * r;
+    const unsigned grid_max = (unsigned)std::min<int64_t>(max_items, (int64_t)gsea_grid(cus));
+
+    auto t0 = clock::now();
+    const size_t nhits = (size_t)hit_ptr[nks];
+    if (int rc = dev_alloc(&D.valid, (size_t)r * N)) return rc;
+    if (int rc = dev_alloc(&D.wp, (size_t)r * N)) return rc;
+    if (int rc = dev_alloc(&D.has_na, (size_t)r)) return rc;
+    if (int rc = dev_alloc(&D.hit_ptr, (size_t)nks + 1)) return rc;
+    if (int rc = dev_alloc(&D.hit_row, nhits)) return rc;
+    if (int rc = dev_alloc(&D.hit_is_miss, nhits)) return rc;
+    if (int rc = dev_alloc(&D.M, (size_t)nks)) return rc;
+    if (int rc = dev_alloc(&D.es, (size_t)nq)) return rc;
+    if (int rc = dev_alloc(&D.exceed, (size_t)nq)) return rc;
+    if (nperm > 0) {
+        if (int rc = dev_alloc(&D.null_es, (size_t)chunk * nq)) return rc;
+        if (int rc = dev_alloc(&D.inv, (size_t)chunk * N)) return rc;
+        if (H.any_na) { if (int rc = dev_alloc(&D.perms, (size_t)chunk * N)) return rc; }
+    }
+    if (H.any_na) {
+        if (int rc = dev_alloc(&D.words, (size_t)grid_max * nW)) return rc;
+        if (int rc = dev_alloc(&D.prefix, (size_t)grid_max * nW)) return rc;
+    }
+    HIPCHECK(hipMemcpy(D.valid, valid, (size_t)r * N, hipMemcpyHostToDevice));
+    HIPCHECK(hipMemcpy(D.wp, wp, (size_t)r * N * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHECK(hipMemcpy(D.has_na, H.has_na.data(), (size_t)r, hipMemcpyHostToDevice));
+    HIPCHECK(hipMemcpy(D.hit_ptr, hit_ptr, ((size_t)nks + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
+    if (nhits) {
+        HIPCHECK(hipMemcpy(D.hit_row, hit_row, nhits * sizeof(int32_t), hipMemcpyHostToDevice));
+        HIPCHECK(hipMemcpy(D.hit_is_miss, hit_is_miss, nhits, hipMemcpyHostToDevice));
+    }
+    HIPCHECK(hipMemcpy(D.M, H.M.data(), (size_t)nks * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIPCHECK(hipMemset(D.exceed, 0, (size_t)nq * sizeof(long long)));
+    HIPCHECK(hipEventCreate(&D.ev0));
+    HIPCHECK(hipEventCreate(&D.ev1));
+    tl_gsea_times_ms[0] += ms_since(t0);
+
+    GseaArgs a;
+    a.N = N; a.r = r; a.nS = nS; a.pad = H.pad; a.valid = D.valid; a.has_na = D.has_na; a.wp = D.wp; a.hit_ptr = D.hit_ptr;
+    a.hit_row = D.hit_row; a.hit_is_miss = D.hit_is_miss; a.M = D.M; a.words = D.words; a.prefix = D.prefix;
+    const size_t lds = (size_t)kGseaLdsFixed + (size_t)kGseaLdsPerHit * (size_t)H.pad;
+    float kms = 0.0f;
+
+    // the observed scores: the identity permutation (R/gsea.R:57)
+    a.nb = 1; a.inv = nullptr; a.perms = nullptr; a.out = D.es;
+    HIPCHECK(hipEventRecord(D.ev0, nullptr));
+    D.queued = true;
+    hipLaunchKernelGGL(k_gsea_perm, dim3((unsigned)std::min<int64_t>(r, grid_max)), dim3(kGseaThreads), lds, nullptr, a);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipEventRecord(D.ev1, nullptr));
+    HIPCHECK(hipEventSynchronize(D.ev1));
+    HIPCHECK(hipEventElapsedTime(&kms, D.ev0, D.ev1));
+    tl_gsea_times_ms[1] += kms;
+
+    for (int64_t b0 = 0; b0 < nperm; b0 += chunk) {                                 // R/gsea.R:65-72
+        const int64_t nb = std::min(chunk, nperm - b0);
+        t0 = clock::now();
+        HIPCHECK(hipMemcpy(D.inv, H.inv.get() + b0 * N, (size_t)nb * N * sizeof(int32_t), hipMemcpyHostToDevice));
+        if (H.any_na) HIPCHECK(hipMemcpy(D.perms, perms + b0 * N, (size_t)nb * N * sizeof(int32_t), hipMemcpyHostToDevice));
+        tl_gsea_times_ms[0] += ms_since(t0);
+        a.nb = (int32_t)nb; a.inv = D.inv; a.perms = H.any_na ? D.perms : nullptr; a.out = D.null_es;
+        HIPCHECK(hipEventRecord(D.ev0, nullptr));
+        hipLaunchKernelGGL(k_gsea_perm, dim3((unsigned)std::min<int64_t>(nb * r, grid_max)), dim3(kGseaThreads), lds, nullptr, a);
+        HIPCHECK(hipGetLastError());
+        hipLaunchKernelGGL(k_gsea_count, dim3((unsigned)((nq + kGseaThreads - 1) / kGseaThreads)), dim3(kGseaThreads), 0, nullptr,
+                           D.es, D.null_es, (int32_t)nb, nq, D.exceed);
+        HIPCHECK(hipGetLastError());
+        HIPCHECK(hipEventRecord(D.ev1, nullptr));
+        HIPCHECK(hipEventSynchronize(D.ev1));
+        HIPCHECK(hipEventElapsedTime(&kms, D.ev0, D.ev1));
+        tl_gsea_times_ms[1] += kms;
+        if (null_es) {
+            t0 = clock::now();
+            HIPCHECK(hipMemcpy(null_es + b0 * nq, D.null_es, (size_t)nb * nq * sizeof(double), hipMemcpyDeviceToHost));
+            tl_gsea_times_ms[2] += ms_since(t0);
+        }
+    }
+    t0 = clock::now();
+    HIPCHECK(hipMemcpy(es, D.es, (size_t)nq * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHECK(hipMemcpy(exceed, D.exceed, (size_t)nq * sizeof(int64_t), hipMemcpyDeviceToHost));
+    D.queued = false;
+    for (int64_t q = 0; q < nq; q++)
+        if (es[q] != es[q]) exceed[q] = -1;
+    tl_gsea_times_ms[2] += ms_since(t0);
+    return VBNMF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vbnmf_gsea_perm(int32_t device, int64_t N, int32_t r, int32_t nS, const uint8_t *valid, const double *wp, const int64_t *hit_ptr,
+                    const int32_t *hit_row, const uint8_t *hit_is_miss, int64_t nperm, const int32_t *perms, double *es,
+                    int64_t *exceed, double *null_es)
+{
+    using clock = std::chrono::steady_clock;
+    for (double &v : tl_gsea_times_ms) v = 0.0;
+    if (N < 1 || N > 2147483584ll) return fail(VBNMF_ERR_BAD_ARG, "N = %lld rows is outside [1, 2^31 - 64]", (long long)N);
+    if (r < 1 || r > VBNMF_MAX_RANK) return fail(VBNMF_ERR_BAD_ARG, "rank %d is outside [1, %d]", r, VBNMF_MAX_RANK);
+    if (nS < 0 || nperm < 0) return fail(VBNMF_ERR_BAD_ARG, "negative number of sets or permutations");
+    if (!valid || !wp || !hit_ptr || (nS > 0 && (!es || !exceed)) || (nperm > 0 && !perms)) return fail(VBNMF_ERR_BAD_ARG, "NULL argument");
+    try {
+        const auto t0 = clock::now();
+        GseaHost H;
+        if (int rc = gsea_check(N, r, nS, valid, wp, hit_ptr, hit_row, hit_is_miss, nperm, perms, H)) return rc;
+        tl_gsea_times_ms[3] = std::chrono::duration<double, std::milli>(clock::now() - t0).count();
+        if (int rc = check_device(device)) return rc;
+        if (nS == 0) return VBNMF_OK;
+        return gsea_run(device, N, r, nS, valid, wp, hit_ptr, hit_row, hit_is_miss, nperm, perms, H, es, exceed, null_es);
+    } catch (const std::bad_alloc &) {
+        return fail(VBNMF_ERR_OOM, "out of host memory inverting %lld permutations of %lld rows", (long long)nperm, (long long)N);
+    } catch (const std::exception &ex) {
+        return fail(VBNMF_ERR_HIP, "vbnmf_gsea_perm: %s", ex.what());
+    }
+}
+
+int vbnmf_gsea_info(int64_t N, int32_t *wave_width, int32_t *workgroup_size, int32_t *max_set_hits, int64_t *chunk_perms, double *times_ms)
+{
+    if (wave_width) *wave_width = kGseaWave;
+    if (workgroup_size) *workgroup_size = kGseaThreads;
+    if (max_set_hits) *max_set_hits = kGseaMaxSetHits;
+    if (chunk_perms) *chunk_perms = gsea_chunk_perms(N);
+    if (times_ms)
+        for (int k = 0; k < 4; k++) times_ms[k] = tl_gsea_times_ms[k];
     return VBNMF_OK;
 }
 

@@ -625,6 +625,47 @@ int vbnmf_qc_info(int32_t *short_row_max, int32_t *pass_entries, int32_t *defaul
  * cells, by sort-and-count.  len outside [0, m]: VBNMF_ERR_BAD_ARG. */
 int vbnmf_test_gene_mode_host(int64_t m, int64_t len, const double *values, int32_t *out);
 
+/* ---------------------------------------------------------------------------------
+ * Cluster annotation: the enrichment scores of assignCelltype() (R/gsea.R:41-77) -- gsea() (:79-115) once on the meta
+ * table as it stands (:57) and once per permutation of its rows (:65-72) -- on HIP device `device` (csrc/gsea.h).
+ * The reference walks every cluster x every set x all N rows nperm + 1 times in R; here a (permutation, cluster) is one
+ * work item of one launch per chunk of permutations, and a set costs a sort and a walk of its hits alone.
+ * --------------------------------------------------------------------------------- */
+/* The meta table has N rows and r clusters (columns of glist / gwgt, :54-55).  Per cluster k (arrays [r x N], k major):
+ *   valid[k*N + i] = !is.na(gwgt[i, k]) (:92), 0 or 1;   wp[k*N + i] = gwgt[i, k]^p (:100), formed by the caller (any value
+ *   on NA rows: it is not read).
+ * Per (k, s), s one of nS gene sets: the rows i with overlap() TRUE (:95, :117-128), ascending, in CSR form --
+ *   hit_row[hit_ptr[k*nS + s] .. hit_ptr[k*nS + s + 1]), and hit_is_miss = 1 where the row is also a miss of :104 (matched
+ *   only through a group prefix, not literally in the set).  Hits stand on valid rows only (:93 drops NA rows first).
+ * The library derives M[k, s] = valid rows - hits that are no misses (pm[length(pm)] of :106).
+ * perms: nperm x N, row b = sample(N) - 1 of :66: the meta-table row that stands at each position; all clusters share it
+ *   (glist[perm,], gwgt[perm,], :67).  nperm = 0: the observed scores only (perms may be NULL).
+ * Results:
+ *   es[s*r + k]      = ES[s, k] of :108 on the table as it stands; NaN where (k, s) has no hit (NA of :96-99), where M = 0
+ *                      (:106 divides by it) or where the hits' weights sum to 0 (:102).
+ *   exceed[s*r + k]  = number of permutations b with es < ES_b, strict (:69), formed in integer arithmetic; -1 where es is NaN.
+ *                      pvalue of :74 = exceed / nperm.
+ *   null_es[(b*nS + s)*r + k] = ES_b[s, k]; may be NULL.
+ * The scores are those of the reference's dense cumsum BIT FOR BIT: the hits' weights are added in table order by one thread,
+ * the rows between them add exact zeros, and the maximum is attained at a hit or at the last row (csrc/gsea.h).  No
+ * floating-point atomics: the same inputs give the same bits on every call.
+ * Limits: any N < 2^31 - 64, 1 <= r <= VBNMF_MAX_RANK, any nS.  A set with more than max_set_hits (vbnmf_gsea_info: 4096) hits in
+ * a cluster is VBNMF_ERR_BAD_ARG -- the sort lives in LDS -- unless its M is 0 (a set holding every gene: NaN whatever its
+ * size).  The permutations are uploaded in chunks of chunk_perms (vbnmf_gsea_info).
+ * Everything is checked on the host before a device is looked for, and the device sees no unchecked index:
+ * VBNMF_ERR_BAD_ARG for a NULL argument, N, r, nS, nperm out of range, hit_ptr not ascending from 0, hit rows not strictly
+ * ascending in [0, N) or on an NA row, a weight wp of a valid row that is not finite (0 * Inf of :101 would be NaN on a row
+ * the hits' walk never sees), a row of perms that is no permutation of 0 .. N-1; then VBNMF_ERR_NO_DEVICE. */
+int vbnmf_gsea_perm(int32_t device, int64_t N, int32_t r, int32_t nS, const uint8_t *valid, const double *wp, const int64_t *hit_ptr,
+                    const int32_t *hit_row, const uint8_t *hit_is_miss, int64_t nperm, const int32_t *perms, double *es,
+                    int64_t *exceed, double *null_es);
+/* Constants of k_gsea_perm and the calling thread's last vbnmf_gsea_perm (any out pointer may be NULL): wave_width (64);
+ * workgroup_size (256: one workgroup per (permutation, cluster) of :65 x :88); max_set_hits = the hits of one (cluster, set)
+ * the workgroup sorts in LDS (a cap, not a pass size: vbnmf_gsea_perm refuses more); chunk_perms = permutations of one upload
+ * for a table of N rows (64 MB of inverse and permutation rows; the environment variable VBNMF_GSEA_CHUNK_PERMS >= 1 makes it
+ * smaller); times_ms[4] = upload, kernels (device events), read-back, host checks with the permutations' inversion, in ms. */
+int vbnmf_gsea_info(int64_t N, int32_t *wave_width, int32_t *workgroup_size, int32_t *max_set_hits, int64_t *chunk_perms, double *times_ms);
+
 /* Cluster of every cell from the coefficients the engine holds:
  * ids[j] = which.max(h[, j])[1], 1-based, first maximum on ties (R/factorize.R:55-56 inside
  * connectivity(), R/utils.R:906 cluster_id); h = the ML coefficient matrix, or E[H] of a VB

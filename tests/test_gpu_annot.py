@@ -1,0 +1,163 @@
+"""k_gsea_perm / k_gsea_count (csrc/gsea.h) behind assign_celltype (ccfindr_amd/annotate.py) on the device, against the DENSE
+restatement of R/gsea.R:41-128 in tests/util_annot.py, given the same permutations and the same gw^p array.  ES, the null scores
+and the exceed counts must be EXACTLY equal -- bits and NaN positions: the kernel adds the hits' weights in the reference's
+order, so there is no tolerance to set.  Table and set sizes are aimed at the kernel's boundaries (vbnmf_gsea_info): W = the
+wave width, G = the workgroup size, CAP = the hits of one set the workgroup sorts in LDS."""
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import util_annot as U  # noqa: E402
+
+import ccfindr_amd as C  # noqa: E402
+from ccfindr_amd import annotate as A  # noqa: E402
+from ccfindr_amd import synth  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+INFO = A.gsea_info()
+W, G, CAP = INFO["wave_width"], INFO["workgroup_size"], INFO["max_set_hits"]
+
+
+def make_table(n, r, seed, na_clusters=(), all_prefixed=False):
+    """A meta table of n rows: every cluster lists the same n genes in its own order, weights decreasing with ties.  The clusters
+    in ``na_clusters`` end in NA rows (gene '', weight NaN), as a column shorter than the table does.  A tenth of the genes are
+    named IG* (all of them with ``all_prefixed``)."""
+    rng = np.random.default_rng(seed)
+    names = np.array([("IG%d" % i) if (all_prefixed or i % 10 == 3) else ("g%d" % i) for i in range(n)])
+    gene = np.empty((n, r), dtype=names.dtype)
+    w = np.empty((n, r))
+    for k in range(r):
+        gene[:, k] = names[rng.permutation(n)]
+        w[:, k] = np.sort(np.round(rng.gamma(0.8, 1.0, size=n), 1) + 0.1)[::-1]        # ties, and no zero
+        if k in na_clusters and n > 1:
+            cut = n - int(rng.integers(1, max(2, n // 3 + 1)))
+            gene[cut:, k] = ""
+            w[cut:, k] = np.nan
+    return C.MetaTable(gene=gene.astype(str), w=w, cv=np.full((n, r), 0.1)), names
+
+
+def make_sets(names, seed, sizes):
+    rng = np.random.default_rng(seed)
+    gset = {"none": ["absent1", "absent2"], "every": list(names)}
+    for t in sizes:
+        if 0 < t <= len(names):
+            gset["size%d" % t] = list(rng.choice(names, size=t, replace=False))
+    if len(names) >= 4:
+        gset["prefix"] = ["IG", str(names[0]), str(names[1])]                            # IG* rows by prefix: hits AND misses
+    return gset
+
+
+def make_perms(n, nperm, seed):
+    rng = np.random.default_rng(seed)
+    perms = np.array([rng.permutation(n) for _ in range(nperm)], dtype=np.int32).reshape(nperm, n)
+    perms[0] = np.arange(n)                                                              # the identity: exact ties meet the strict <
+    if nperm > 2:
+        perms[2] = perms[1]                                                              # and one permutation twice
+    return perms
+
+
+def compare(meta, gset, p, perms, label):
+    out = C.assign_celltype(meta, meta.rank, gset, p=p, p_value=True, perms=perms, grp_prefix=("IG",), return_null=True)
+    tb = A.gsea_tables(meta, gset, p=p, grp_prefix=("IG",))
+    es, exceed, null = U.assign_dense(meta.gene, meta.w, tb["wp"].T, gset, perms, ("IG",))
+    nan = int(np.isnan(es).sum())
+    print(f"{label}: N={meta.gene.shape[0]} r={meta.rank} sets={len(gset)} p={p} nperm={len(perms)}: {nan} of {es.size} scores NaN, "
+          f"largest set {int(np.diff(tb['hit_ptr']).max())} hits, exceed in [{exceed.min()}, {exceed.max()}]")
+    assert U.bits_equal(out["ES"], es), (label, out["ES"], es)
+    assert U.bits_equal(out["null_es"], null), label
+    assert out["exceed"].dtype == np.int64 and np.array_equal(out["exceed"], exceed), (label, out["exceed"], exceed)
+    with np.errstate(invalid="ignore"):
+        want_p = np.where(np.isnan(es), np.nan, exceed / float(len(perms)))
+    assert U.bits_equal(out["pvalue"], want_p)
+    assert np.array_equal(null[0], es, equal_nan=True) and np.all(exceed[~np.isnan(es)] <= len(perms) - 1)
+    # the observed scores alone: the same bits
+    assert U.bits_equal(C.assign_celltype(meta, meta.rank, gset, p=p, grp_prefix=("IG",)), es)
+    return out, es
+
+
+SMALL = [1, 2, W - 1, W, W + 1, G - 1, G + 1]
+
+
+@pytest.mark.parametrize("n", SMALL)
+def test_small_tables(n):
+    i = SMALL.index(n)
+    r = (1, 2, 5)[i % 3]
+    for j, p in enumerate((0, 0.5, 1)):
+        na = () if (n == 1 or (i + j) % 3 == 0) else tuple(range(1, r, 2)) if r > 1 else (0,)
+        meta, names = make_table(n, r, 100 * n + j, na_clusters=na)
+        gset = make_sets(names, n + j, (1, 2, W, W + 1, n // 2, n - 1))
+        compare(meta, gset, p, make_perms(n, 24, 7 * n + j), f"N={n} p={p} NA clusters {na}")
+
+
+def test_large_table_cap_set_and_every_gene():
+    """N = 4096 = CAP: with every gene named IG*, the set ['IG'] hits every row through the prefix and every row is a miss
+    (T = CAP, M = N) in the cluster without NA rows; the set holding every gene has M = 0 (NaN); sets of 0, 1, W, W + 1 hits."""
+    n = 4096
+    assert CAP >= n
+    meta, names = make_table(n, 2, 41, na_clusters=(1,), all_prefixed=True)
+    gset = make_sets(names, 43, (1, W, W + 1, 300))
+    gset["prefix"] = ["IG"]
+    tb = A.gsea_tables(meta, gset, p=0.5)
+    assert int(np.diff(tb["hit_ptr"]).max()) == n and tb["hit_is_miss"].sum() >= n
+    out, es = compare(meta, gset, 0.5, make_perms(n, 6, 47), "N=4096")
+    k = list(gset).index("every")
+    assert np.isnan(es[k]).all() and np.isnan(es[list(gset).index("none")]).all()
+    assert not np.isnan(es[list(gset).index("prefix")]).any()
+
+
+def test_permutations_cross_a_chunk(monkeypatch):
+    """nperm = 200 at N = 4096 with the chunk shrunk to 64 permutations through the environment variable
+    VBNMF_GSEA_CHUNK_PERMS: four uploads, the last one short; the counts add up across them."""
+    n = 4096
+    monkeypatch.setenv("VBNMF_GSEA_CHUNK_PERMS", "64")
+    assert A.gsea_info(n)["chunk_perms"] == 64
+    meta, names = make_table(n, 2, 51, na_clusters=(0,))
+    gset = {"a": list(names[5:25]), "b": ["IG", "g0"], "none": ["absent"]}
+    compare(meta, gset, 1, make_perms(n, 200, 53), "chunks")
+
+
+def test_same_bits_on_every_call():
+    meta, names = make_table(777, 5, 61, na_clusters=(0, 3))
+    gset = make_sets(names, 63, (1, W, W + 1, 500))
+    perms = make_perms(777, 40, 67)
+    a = C.assign_celltype(meta, 5, gset, p=0.5, p_value=True, perms=perms, return_null=True)
+    b = C.assign_celltype(meta, 5, gset, p=0.5, p_value=True, perms=perms, return_null=True)
+    assert U.bits_equal(a["null_es"], b["null_es"]) and U.bits_equal(a["ES"], b["ES"]) and np.array_equal(a["exceed"], b["exceed"])
+    # remove_na drops the sets whose first column is NaN, from every result
+    c = C.assign_celltype(meta, 5, gset, p=0.5, p_value=True, perms=perms, return_null=True, remove_na=True)
+    keep = ~np.isnan(a["ES"][:, 0])
+    assert 0 < keep.sum() < len(keep)
+    assert U.bits_equal(c["ES"], a["ES"][keep]) and U.bits_equal(c["null_es"], a["null_es"][:, keep])
+    # seeded permutations: the same seed gives the same p-values
+    d = C.assign_celltype(meta, 5, gset, p_value=True, nperm=30, seed=5)
+    e = C.assign_celltype(meta, 5, gset, p_value=True, nperm=30, seed=5)
+    assert U.bits_equal(d["pvalue"], e["pvalue"]) and np.nanmax(d["pvalue"]) <= 1.0
+
+
+def test_planted_markers_end_to_end():
+    """vb_factorize at rank 3 on simulate_data counts with ten marker genes planted per cluster (extra counts in that cluster's
+    cells alone), then assign_celltype on the fit: every planted set has its largest ES in its own cluster -- the fitted
+    cluster that holds most of the planted cluster's cells."""
+    sizes, n = (100, 100, 100), 200
+    X = synth.simulate_data(n, sizes, seed=9, sparse=False, shuffle=False)
+    rng = np.random.default_rng(19)
+    planted = np.repeat(np.arange(3), sizes)
+    gene_names = ["gene%d" % i for i in range(n)]
+    gset = {}
+    for c in range(3):
+        rows = np.arange(10 * c, 10 * c + 10)
+        X[np.ix_(rows, np.flatnonzero(planted == c))] += rng.poisson(8.0, size=(10, sizes[c]))
+        gset["type%d" % c] = [gene_names[i] for i in rows]
+    X = np.asfortranarray(X)
+    res = C.vb_factorize(X, ranks=3, nrun=2, verbose=0, progress_bar=False, seed=3)
+    ids = C.cluster_id(res, rank=3)
+    own = [int(np.bincount(ids[planted == c], minlength=4).argmax()) - 1 for c in range(3)]
+    assert sorted(own) == [0, 1, 2], own
+    out = C.assign_celltype(res, 3, gset, gene_names=gene_names, p=1, p_value=True, nperm=50, seed=1)
+    print("ES\n", out["ES"], "\npvalue\n", out["pvalue"], "\nown clusters", own)
+    assert out["ES"].shape == (3, 3) and not np.isnan(out["ES"]).any()
+    assert [int(np.argmax(out["ES"][c])) for c in range(3)] == own
