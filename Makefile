@@ -9,7 +9,7 @@ OBJ := build/obj
 CXXFLAGS ?= -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-function -pthread
 HIPFLAGS ?= $(CXXFLAGS) --offload-arch=$(ARCH)
 HOST_HDRS := $(CSRC)/common.h include/vbnmf.h
-DEV_HDRS := $(HOST_HDRS) $(CSRC)/kernels.h $(CSRC)/mlnmf.h $(CSRC)/project.h $(CSRC)/vbproject.h $(CSRC)/qc.h $(CSRC)/gsea.h $(CSRC)/special.h $(CSRC)/init.h $(CSRC)/consensus.h $(CSRC)/cophenet.h $(CSRC)/comm.h
+DEV_HDRS := $(HOST_HDRS) $(CSRC)/kernels.h $(CSRC)/mlnmf.h $(CSRC)/project.h $(CSRC)/vbproject.h $(CSRC)/qc.h $(CSRC)/gsea.h $(CSRC)/tsne.h $(CSRC)/special.h $(CSRC)/init.h $(CSRC)/consensus.h $(CSRC)/cophenet.h $(CSRC)/comm.h
 
 all: $(LIB) oracle testlibs
 

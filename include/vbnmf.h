@@ -666,6 +666,60 @@ int vbnmf_gsea_perm(int32_t device, int64_t N, int32_t r, int32_t nS, const uint
  * smaller); times_ms[4] = upload, kernels (device events), read-back, host checks with the permutations' inversion, in ms. */
 int vbnmf_gsea_info(int64_t N, int32_t *wave_width, int32_t *workgroup_size, int32_t *max_set_hits, int64_t *chunk_perms, double *times_ms);
 
+/* ---------------------------------------------------------------------------------
+ * The map of the cells: visualize_clusters() (R/utils.R:692-712) runs Rtsne on t(h) (:700).  Here: the t-SNE authors'
+ * exact algorithm (no Barnes-Hut tree, Rtsne's theta = 0) on HIP device `device`, in fp64 with fixed summation trees
+ * (csrc/tsne.h, DESIGN.md 5k states every formula).  Rtsne is a CPU package this project cannot run: the algorithm below
+ * is pinned by the project's own tests, not by Rtsne's output.  No n x n array exists: the force kernel recomputes
+ * P_ij = (exp(-beta_i D_ij) / S_i + exp(-beta_j D_ij) / S_j) / (2n) for every pair of every iteration.
+ * --------------------------------------------------------------------------------- */
+typedef struct vbnmf_tsne vbnmf_tsne;
+
+/* x: n points x d doubles, row-major (t(h) of :700: a cell's coefficients are contiguous); 1 <= d <= VBNMF_MAX_RANK, n <= 2^31 - 2048.
+ * normalize != 0: the column means are subtracted and everything is divided by the largest absolute value (not when that is 0),
+ * on the host, sequentially.  No PCA.  Then, on the device, per point i the bisection on beta_i (start 1, at most 200 trips,
+ * |H_i - ln perplexity| < 1e-5; S_i = sum_{j != i} exp(-beta_i D_ij) + DBL_MIN, D_ij = sum_k (x_ik - x_jk)^2).
+ * A row that uses up its 200 trips keeps the beta of its last update, and S_i is evaluated once more at that beta.
+ * The handle keeps x, beta and 1/S on the device; the state (Y, uY, gains) starts unset.
+ * All arguments are checked before a device is looked for -- VBNMF_ERR_BAD_ARG for a NULL x or handle, n or d out of range,
+ * perplexity not finite, < 1 or not 3 perplexity < n - 1 (Rtsne's rule), a non-finite x -- then VBNMF_ERR_NO_DEVICE.  No CPU
+ * fallback. */
+int vbnmf_tsne_create(int32_t device, int64_t n, int32_t d, const double *x, double perplexity, int32_t normalize, vbnmf_tsne **handle);
+void vbnmf_tsne_destroy(vbnmf_tsne *t);
+/* beta[n], sum_p[n] = S_i, trips[n] = evaluations of H_i the bisection made (1 .. 200); any may be NULL. */
+int vbnmf_tsne_affinity(vbnmf_tsne *t, double *beta, double *sum_p, int32_t *trips);
+/* Y, uY, gains: n x 2 row-major each.  set: Y is required (finite); uY NULL = 0, gains NULL = 1 (the start state of the
+ * descent).  get: any may be NULL; VBNMF_ERR_STATE before the first set. */
+int vbnmf_tsne_set_state(vbnmf_tsne *t, const double *Y, const double *uY, const double *gains);
+int vbnmf_tsne_get_state(vbnmf_tsne *t, double *Y, double *uY, double *gains);
+/* One evaluation on the current Y; changes nothing.  A[n x 2] = exaggeration * sum_j P_ij w_ij (y_i - y_j) (the product is
+ * the one the update forms first), R[n x 2] = sum_j w_ij^2 (y_i - y_j), z[n] = sum_j w_ij, w_ij = 1 / (1 + |y_i - y_j|^2),
+ * cost_i[n] = sum_j P_ij ln(P_ij Z / w_ij) with Z = sum_i z_i (terms with P_ij = 0 count 0; always at exaggeration 1).
+ * Any out pointer may be NULL.  exaggeration must be finite.  VBNMF_ERR_STATE before the first set_state. */
+int vbnmf_tsne_forces(vbnmf_tsne *t, double exaggeration, double *A, double *R, double *z, double *cost_i);
+/* Iterations first_iter .. first_iter + n_iter - 1 (numbered from 1) of the descent, queued on one stream with no
+ * synchronisation or read-back between them.  Iteration it: e = exaggeration while it <= stop_lying_iter, else 1;
+ * m = momentum while it <= mom_switch_iter, else final_momentum;
+ *   dY = e A - R / Z (no factor 4: eta = 200 is tuned to that);  gains = sign(dY) != sign(uY) ? gains + 0.2 : 0.8 gains,
+ *   floored at min_gain (sign is -1, 0, +1);  uY = m uY - eta gains dY;  Y += uY;  the column means of Y are subtracted.
+ * The cost C = sum_{i != j} P_ij ln(P_ij Z / w_ij) of the Y an iteration leaves is recorded after every iteration `it` with
+ * it % cost_every == 0 (cost_every <= 0: never) and after the call's last one: itercosts[k], cost_iters[k] = it, *n_costs
+ * their number; the caller provides n_iter / cost_every + 1 entries (n_iter entries at the most).  The device array of the
+ * costs is read once, after the last iteration.  n_iter = 0: nothing runs, *n_costs = 0.
+ * VBNMF_ERR_BAD_ARG: first_iter < 1, n_iter < 0, a schedule value that is not finite, NULL itercosts, cost_iters or n_costs;
+ * VBNMF_ERR_STATE before the first set_state. */
+int vbnmf_tsne_run(vbnmf_tsne *t, int32_t first_iter, int32_t n_iter, double exaggeration, int32_t stop_lying_iter,
+                   int32_t mom_switch_iter, double momentum, double final_momentum, double eta, double min_gain, int32_t cost_every,
+                   double *itercosts, int32_t *cost_iters, int32_t *n_costs);
+/* Constants of the kernels and the handle's launches (t may be NULL: the grids are then 0 and the times are those of the
+ * calling thread's last vbnmf_tsne_create).  ints[8]: wave width (64), workgroup size of the affinity and force kernels (256),
+ * the force kernel's i-block (64 points a workgroup) and j-tile (32 points a pass through LDS), the affinity kernel's LDS row
+ * capacity (2048 distances; a longer row lives in the workgroup's row of a global scratch buffer), the affinity grid, the
+ * force grid, the update kernel's workgroup size (1024, one workgroup).  times_ms[7]: normalise, upload, affinities (device
+ * events) of the create; of the handle's last run the loop (device events over its iterations, without the closing cost
+ * evaluation), the read-back, and the last iteration's force and update launch each by itself (device events). */
+int vbnmf_tsne_info(vbnmf_tsne *t, int32_t *ints, double *times_ms);
+
 /* Cluster of every cell from the coefficients the engine holds:
  * ids[j] = which.max(h[, j])[1], 1-based, first maximum on ties (R/factorize.R:55-56 inside
  * connectivity(), R/utils.R:906 cluster_id); h = the ML coefficient matrix, or E[H] of a VB
