@@ -1,6 +1,6 @@
 # Builds the MI355X (gfx950) library and the CPU oracle.  `python -c "import __graft_entry__ as g; g.build()"`
-# runs the same commands.  One object per source (build/, git-ignored): a change to the host side does not recompile
-# the kernels' 24 rank instantiations.
+# runs the same commands.  One object per source of ccfindr_amd/csrc (build/, git-ignored): every *.cpp as plain C++, every
+# *.hip for gfx950 -- one unit per feature, so a change to one feature recompiles that unit and not the engine's kernels.
 HIPCC ?= /opt/rocm/bin/hipcc
 ARCH ?= gfx950
 CSRC := ccfindr_amd/csrc
@@ -8,40 +8,26 @@ LIB := ccfindr_amd/lib/libvbnmf_hip.so
 OBJ := build/obj
 CXXFLAGS ?= -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-function -pthread
 HIPFLAGS ?= $(CXXFLAGS) --offload-arch=$(ARCH)
-HOST_HDRS := $(CSRC)/common.h include/vbnmf.h
-DEV_HDRS := $(HOST_HDRS) $(CSRC)/kernels.h $(CSRC)/mlnmf.h $(CSRC)/project.h $(CSRC)/vbproject.h $(CSRC)/qc.h $(CSRC)/gsea.h $(CSRC)/tsne.h $(CSRC)/special.h $(CSRC)/init.h $(CSRC)/consensus.h $(CSRC)/cophenet.h $(CSRC)/comm.h
+DEV_HDRS := $(wildcard $(CSRC)/*.h) include/vbnmf.h
+SOURCES := $(sort $(wildcard $(CSRC)/*.cpp) $(wildcard $(CSRC)/*.hip))
+OBJECTS := $(patsubst $(CSRC)/%,$(OBJ)/%.o,$(basename $(SOURCES)))
 
 all: $(LIB) oracle testlibs
 
-$(OBJ)/host.o: $(CSRC)/host.cpp $(HOST_HDRS)
+$(OBJ)/%.o: $(CSRC)/%.cpp
 	mkdir -p $(OBJ)
-	$(HIPCC) $(CXXFLAGS) -c -o $@ $<
+	$(HIPCC) $(CXXFLAGS) -MMD -c -o $@ $<
 
-$(OBJ)/layout.o: $(CSRC)/layout.cpp $(HOST_HDRS)
+$(OBJ)/%.o: $(CSRC)/%.hip
 	mkdir -p $(OBJ)
-	$(HIPCC) $(CXXFLAGS) -c -o $@ $<
+	$(HIPCC) $(HIPFLAGS) -MMD -c -o $@ -x hip $<
 
-$(OBJ)/blob.o: $(CSRC)/blob.cpp $(HOST_HDRS)
-	mkdir -p $(OBJ)
-	$(HIPCC) $(CXXFLAGS) -c -o $@ $<
+# An object's headers: the compiler's own list from its last compile (-MMD), so a header rebuilds the units that include it
+# and no other; an object that has no such list yet depends on every header.
+$(foreach o,$(OBJECTS),$(if $(wildcard $(o:.o=.d)),,$(eval $(o): $(DEV_HDRS))))
+-include $(OBJECTS:.o=.d)
 
-$(OBJ)/mtx.o: $(CSRC)/mtx.cpp $(HOST_HDRS)
-	mkdir -p $(OBJ)
-	$(HIPCC) $(CXXFLAGS) -c -o $@ $<
-
-$(OBJ)/order.o: $(CSRC)/order.cpp $(HOST_HDRS)
-	mkdir -p $(OBJ)
-	$(HIPCC) $(CXXFLAGS) -c -o $@ $<
-
-$(OBJ)/consensus.o: $(CSRC)/consensus.cpp $(HOST_HDRS)
-	mkdir -p $(OBJ)
-	$(HIPCC) $(CXXFLAGS) -c -o $@ $<
-
-$(OBJ)/engine.o: $(CSRC)/engine.hip $(DEV_HDRS)
-	mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -c -o $@ -x hip $<
-
-$(LIB): $(OBJ)/host.o $(OBJ)/layout.o $(OBJ)/blob.o $(OBJ)/mtx.o $(OBJ)/order.o $(OBJ)/consensus.o $(OBJ)/engine.o
+$(LIB): $(OBJECTS)
 	mkdir -p $(dir $(LIB))
 	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) -o $@ $^ -pthread
 

@@ -29,7 +29,7 @@ from .engine import EPS, CountMatrix, VBEngine, geometry_rank_for, rank_classes
 
 import ctypes
 
-BATCH_MAX_RANK = 16          # ranks the batch kernels are built for (csrc/engine.hip: kBatchMaxPaddedRank)
+BATCH_MAX_RANK = 16          # ranks the batch kernels are built for (csrc/rank.h: kBatchMaxPaddedRank)
 
 
 # ---------------------------------------------------------------------------------------
@@ -135,7 +135,7 @@ def hyper_update(hyper_update, wh, hyper, Niter=100, Tol=1e-4):
                   / (1 / ah0 - _trigamma(ah0))) if flags[2] else 0.0
             # A non-finite Newton step (a -inf mean log: fudge = 0 and a shape small enough for exp(psi) to underflow)
             # makes the reference's halving loops below spin for ever; it is reported as the failure of :43 instead,
-            # as the device loop does (kernels.h dev_hyper_update_pair).
+            # as the device loop does (hyper.h dev_hyper_update_pair).
             if not (math.isfinite(dw) and math.isfinite(dh)):
                 raise RuntimeError("Hyper-parameter update failed to converge")
             aw1, ah1 = aw0 - dw, ah0 - dh

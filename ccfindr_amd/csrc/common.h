@@ -24,7 +24,7 @@ int env_int(const char *name, int dflt);    // an integer environment switch (un
 // device (when not null): the HIP device the accumulator lives on.
 int consensus_download(vbnmf_consensus *c, std::vector<uint8_t> &labels, int64_t &m, int32_t &runs, int32_t &unlabelled, int32_t *device = nullptr);
 
-// The grouped cophenetic on the device (cophenet.h, compiled into engine.hip), as consensus.cpp's host glue sees it:
+// The grouped cophenetic on the device (cophenet.h, compiled into cophenet.hip), as consensus.cpp's host glue sees it:
 // plain device buffers and three launches.  Every function returns a status and leaves the message set.
 constexpr int64_t kCophMaxGroups = 32768;   // the chain kernel's activity flags fill 32 KB of LDS; W and S take 16 G^2 bytes
 constexpr int kCophOut = 10;                // doubles in the chain kernel's result block (cophenet.h: k_coph_chain)

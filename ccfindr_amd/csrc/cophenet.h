@@ -1,5 +1,5 @@
 // cophenet.h -- the grouped cophenetic correlation (reference R/factorize.R:69-78; host form: consensus.cpp) on the
-// device, for more groups than the host form serves (included once, by engine.hip).  Two steps:
+// device, for more groups than the host form serves (included once, by cophenet.hip).  Two steps:
 //   k_coph_setup_*  W[i][j] = distance of groups i, j (the host's expression, so the host's bits) and the weighted
 //                   sums S[i][j] = size_i size_j dist(i, j); per row i, the sums over j > i the correlation needs.
 //   k_coph_chain    the whole nearest-neighbour chain in ONE workgroup: ~3G dependent row arg-mins and G row / column
@@ -243,63 +243,5 @@ __global__ __launch_bounds__(kCophChainThreads) void k_coph_chain(double *W, dou
         out[6] = cmin; out[7] = cmax; out[8] = (double)status; out[9] = (double)done;
     }
 }
-
-// ---- the host's handle on the above (declared in common.h; consensus.cpp holds the glue) ----
-#define COPH_HIP(expr)                                                                                                      \
-    do {                                                                                                                    \
-        hipError_t _e = (expr);                                                                                             \
-        if (_e != hipSuccess) return fail(VBNMF_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-    } while (0)
-
-int coph_dev_alloc(void **p, size_t bytes, const char *what)
-{
-    *p = nullptr;
-    const hipError_t e = hipMalloc(p, bytes ? bytes : 1);
-    if (e == hipSuccess) return VBNMF_OK;
-    (void)hipGetLastError();
-    *p = nullptr;
-    if (e == hipErrorOutOfMemory) return fail(VBNMF_ERR_OOM, "out of device memory: %zu bytes for %s", bytes, what);
-    return fail(VBNMF_ERR_HIP, "hipMalloc of %zu bytes for %s failed: %s", bytes, what, hipGetErrorString(e));
-}
-
-void coph_dev_free(void *p)
-{
-    if (p) (void)hipFree(p);
-}
-
-int coph_dev_upload(void *dst, const void *src, size_t bytes)
-{
-    if (bytes) COPH_HIP(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
-    return VBNMF_OK;
-}
-
-int coph_dev_download(void *dst, const void *src, size_t bytes)
-{
-    if (bytes) COPH_HIP(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
-    return VBNMF_OK;
-}
-
-int coph_dev_setup_tuples(const uint8_t *tuples, const int64_t *sizes, int G, int R, double *W, double *S, double *weight, unsigned long long *isum, double *mm)
-{
-    hipLaunchKernelGGL(k_coph_setup_tuples, dim3((unsigned)G), dim3(kCophSetupThreads), 0, 0, tuples, sizes, G, R, W, S, weight, isum, mm);
-    COPH_HIP(hipGetLastError());
-    return VBNMF_OK;
-}
-
-int coph_dev_setup_dist(const double *dist, const int64_t *sizes, int G, double *W, double *S, double *weight, double *fsum, double *mm)
-{
-    hipLaunchKernelGGL(k_coph_setup_dist, dim3((unsigned)G), dim3(kCophSetupThreads), 0, 0, dist, sizes, G, W, S, weight, fsum, mm);
-    COPH_HIP(hipGetLastError());
-    return VBNMF_OK;
-}
-
-int coph_dev_chain(double *W, double *S, double *weight, int *chain, int G, int link, long long *merges, double *heights, double *out)
-{
-    hipLaunchKernelGGL(k_coph_chain, dim3(1), dim3(kCophChainThreads), 0, 0, W, S, weight, chain, G, link, merges, heights, out);
-    COPH_HIP(hipGetLastError());
-    COPH_HIP(hipDeviceSynchronize());
-    return VBNMF_OK;
-}
-#undef COPH_HIP
 
 }  // namespace vbnmf

@@ -28,35 +28,22 @@
 #include <string>
 #include <system_error>
 #include <thread>
-#include <type_traits>
 #include <utility>
 
 #include "common.h"
 #include "comm.h"
+#include "device.h"
 #include "kernels.h"
 #include "mlnmf.h"
-#include "project.h"
-#include "vbproject.h"
-#include "qc.h"
-#include "gsea.h"
-#include "tsne.h"
+#include "rank.h"
 #include "init.h"
 #include "consensus.h"
-#include "cophenet.h"
 
 using namespace vbnmf;
 
-#define HIPCHECK(expr)                                                                                   \
-    do {                                                                                                 \
-        hipError_t _e = (expr);                                                                          \
-        if (_e != hipSuccess)                                                                            \
-            return fail(VBNMF_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-    } while (0)
-
 namespace {
 
-constexpr int kHostOut = 16;
-void dev_free(void *p);             // returns a device buffer to the pool (below)          // doubles in the pinned result block of an engine
+constexpr int kHostOut = 16;        // doubles in the pinned result block of an engine
 
 // The layout's arrays on the device.  Engines made from a cached layout (same matrix, same geometry, same device)
 // share one of these; the per-engine part is DeviceSide::part.
@@ -92,109 +79,6 @@ struct DeviceSide {
     bool wide = false;
     bool merge = false;                        // the sweep adds the runs of a slice in the wave: one partial row per run (Layout::merge)
 };
-
-// ---- device buffer pool.  An engine owns ~25 device buffers (state, partial rows up to 100 MB a side, reduce buffers);
-// a rank sweep creates and destroys an engine per (run, rank) unit, and every hipFree synchronises the whole device --
-// including the streams of other engines of the process (vb_factorize(concurrent = K)).  Freed buffers therefore go to a
-// per-process free list and the next engine takes the smallest one that fits (within 1.5 x of the request); the list holds
-// at most VBNMF_POOL_MB (default 4096) and gives the oldest buffers back to the driver beyond that.  Measured on the C4
-// sweep (19 engines in a row): engine creation + destruction 0.5 s -> 0.1 s (profiles/r04_c4_sweep.json).
-struct PoolBuf { void *p; size_t bytes; int device; };
-struct DevicePool {
-    std::mutex mu;
-    std::vector<PoolBuf> free_list;                  // oldest first
-    std::vector<PoolBuf> live;                       // buffers handed out (size and device of every pointer)
-    size_t held = 0;
-    size_t cap = [] { const char *s = getenv("VBNMF_POOL_MB"); long v = s ? atol(s) : 4096; return (size_t)(v < 0 ? 0 : v) << 20; }();
-};
-DevicePool &device_pool() { static DevicePool *P = new DevicePool(); return *P; }      // (never destroyed: no HIP calls at exit)
-
-int pool_alloc(void **p, size_t bytes)
-{
-    *p = nullptr;
-    if (bytes == 0) bytes = 8;
-    int device = 0;
-    (void)hipGetDevice(&device);
-    DevicePool &P = device_pool();
-    {
-        std::lock_guard<std::mutex> g(P.mu);
-        int best = -1;
-        for (int q = 0; q < (int)P.free_list.size(); q++) {
-            const PoolBuf &b = P.free_list[q];
-            if (b.device == device && b.bytes >= bytes && b.bytes <= bytes + bytes / 2 + 4096 && (best < 0 || b.bytes < P.free_list[best].bytes)) best = q;
-        }
-        if (best >= 0) {
-            PoolBuf b = P.free_list[best];
-            P.free_list.erase(P.free_list.begin() + best);
-            P.held -= b.bytes;
-            P.live.push_back(b);
-            *p = b.p;
-            return VBNMF_OK;
-        }
-    }
-    hipError_t e = hipMalloc(p, bytes);
-    if (e == hipErrorOutOfMemory) {                  // give the pooled buffers back and try once more
-        (void)hipGetLastError();
-        std::vector<PoolBuf> drop;
-        { std::lock_guard<std::mutex> g(P.mu); drop.swap(P.free_list); P.held = 0; }
-        for (const PoolBuf &b : drop) (void)hipFree(b.p);
-        e = hipMalloc(p, bytes);
-    }
-    if (e == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(VBNMF_ERR_OOM, "out of device memory (%zu bytes)", bytes); }
-    if (e != hipSuccess) return fail(VBNMF_ERR_HIP, "hipMalloc failed: %s", hipGetErrorString(e));
-    std::lock_guard<std::mutex> g(P.mu);
-    P.live.push_back({*p, bytes, device});
-    return VBNMF_OK;
-}
-
-// The caller guarantees that no queued work still uses the buffer (engines synchronise their streams before they free).
-void dev_free(void *p)
-{
-    if (!p) return;
-    DevicePool &P = device_pool();
-    std::vector<PoolBuf> drop;
-    {
-        std::lock_guard<std::mutex> g(P.mu);
-        PoolBuf b{p, 0, 0};
-        bool known = false;
-        for (size_t q = 0; q < P.live.size(); q++)
-            if (P.live[q].p == p) { b = P.live[q]; P.live.erase(P.live.begin() + q); known = true; break; }
-        if (!known || P.cap == 0 || b.bytes > P.cap) { drop.push_back(b); }
-        else {
-            P.free_list.push_back(b);
-            P.held += b.bytes;
-            while (P.held > P.cap && !P.free_list.empty()) {
-                drop.push_back(P.free_list.front());
-                P.held -= P.free_list.front().bytes;
-                P.free_list.erase(P.free_list.begin());
-            }
-        }
-    }
-    for (const PoolBuf &b : drop) (void)hipFree(b.p);
-}
-
-template <typename T>
-int dev_alloc(T **p, size_t count)
-{
-    if (count == 0) count = 1;
-    return pool_alloc((void **)p, count * sizeof(T));
-}
-
-template <typename T>
-int dev_upload(T **p, const ExtVec<T> &v)
-{
-    if (int rc = dev_alloc(p, v.size())) return rc;
-    if (!v.empty()) HIPCHECK(hipMemcpy(*p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    return VBNMF_OK;
-}
-
-template <typename T, typename A>
-int dev_upload(T **p, const std::vector<T, A> &v)
-{
-    if (int rc = dev_alloc(p, v.size())) return rc;
-    if (!v.empty()) HIPCHECK(hipMemcpy(*p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    return VBNMF_OK;
-}
 
 }  // namespace
 
@@ -523,60 +407,6 @@ int launch_lds_kernel(vbnmf_engine *e, dim3 grid, int threads, const Args &...ar
         if (e->device < 16) attr_set[e->device].store(true, std::memory_order_release);
     }
     return launch_kernel<K>(e, grid, threads, e->lds_bytes, args...);
-}
-
-// ---- dispatch over the padded rank (compile-time so factor rows live in registers) ----
-#define VBNMF_FOR_EACH_R_UP_TO_64(X) \
-    X(2) X(4) X(6) X(8) X(10) X(12) X(14) X(16) X(18) X(20) X(22) X(24) X(26) X(28) X(30) X(32) \
-    X(40) X(48) X(56) X(64)
-// every padded rank: up to 32 by 2 (one lane per task), 40..64 by 8 (two lanes), 80..128 by 16 (four lanes)
-#ifdef VBNMF_DEV_FEW_RANKS              /* development builds only: a few ranks, for a compile check in a minute */
-#define VBNMF_FOR_EACH_R(X) X(4) X(6) X(8) X(10) X(20) X(48) X(80)
-#define VBNMF_FOR_EACH_R_BATCH(X) X(4) X(6) X(8) X(10)
-#else
-#define VBNMF_FOR_EACH_R(X) VBNMF_FOR_EACH_R_UP_TO_64(X) X(80) X(96) X(112) X(128)
-#define VBNMF_FOR_EACH_R_BATCH(X) X(2) X(4) X(6) X(8) X(10) X(12) X(14) X(16)
-#endif
-constexpr int kBatchMaxPaddedRank = 16;      // the small-matrix regime the batch is for (instantiations cost build time)
-static_assert(rank_shares(kBatchMaxPaddedRank) == 1, "the batch sweeps have no form that shares a rank among lanes");
-
-// f(std::integral_constant<int, R>{}) for the padded rank R of one of the lists above; returns f's status.  The lists are
-// expanded here and nowhere else: with_rank serves every rank, with_rank_up_to_64 the truncated SVD's dense kernels,
-// with_batch_rank the kernels that step a batch of engines.
-#define X(RR) case RR: return f(std::integral_constant<int, RR>{});
-template <class F>
-int with_rank(int R, F &&f)
-{
-    switch (R) {
-        VBNMF_FOR_EACH_R(X)
-        default: return fail(VBNMF_ERR_BAD_ARG, "unsupported padded rank %d", R);
-    }
-}
-
-template <class F>
-int with_rank_up_to_64(int R, F &&f)
-{
-    switch (R) {
-        VBNMF_FOR_EACH_R_UP_TO_64(X)
-        default: return fail(VBNMF_ERR_BAD_ARG, "unsupported padded rank %d", R);
-    }
-}
-
-template <class F>
-int with_batch_rank(int R, F &&f)
-{
-    switch (R) {
-        VBNMF_FOR_EACH_R_BATCH(X)
-        default: return fail(VBNMF_ERR_BAD_ARG, "a batch serves padded ranks up to %d (this engine: %d)", kBatchMaxPaddedRank, R);
-    }
-}
-#undef X
-
-// f(std::true_type{}) or f(std::false_type{}): a run-time switch as a template argument
-template <class F>
-int with_flag(bool on, F &&f)
-{
-    return on ? f(std::true_type{}) : f(std::false_type{});
 }
 
 // The template arguments the sweep family shares, for the padded rank RT and the engine's entry format: above 32 the
@@ -983,23 +813,6 @@ int use_device(const vbnmf_engine *e)
     if (e->poisoned)
         return fail(VBNMF_ERR_STATE, "the engine timed out earlier (VBNMF_WAIT_TIMEOUT_S) and may still have work queued; destroy it");
     HIPCHECK(hipSetDevice(e->device));
-    return VBNMF_OK;
-}
-
-int check_device(int device)
-{
-    int cnt = 0;
-    hipError_t err = hipGetDeviceCount(&cnt);
-    if (err != hipSuccess || cnt <= 0) {
-        (void)hipGetLastError();
-        return fail(VBNMF_ERR_NO_DEVICE, "no HIP device is available (%s); this library has no CPU fallback",
-                    err != hipSuccess ? hipGetErrorString(err) : "device count is 0");
-    }
-    if (device < 0 || device >= cnt) return fail(VBNMF_ERR_BAD_ARG, "device %d is outside [0, %d)", device, cnt);
-    hipDeviceProp_t prop;
-    HIPCHECK(hipGetDeviceProperties(&prop, device));
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return fail(VBNMF_ERR_NO_DEVICE, "device %d is %s; this library carries gfx950 (MI355X) code only", device, prop.gcnArchName);
     return VBNMF_OK;
 }
 
@@ -1428,8 +1241,7 @@ int vbnmf_matrix_preload_layout(const vbnmf_matrix *X, int32_t side, int32_t geo
     if (!X) return fail(VBNMF_ERR_BAD_ARG, "matrix handle is NULL");
     if (side != 0 && side != 1) return fail(VBNMF_ERR_BAD_ARG, "side must be 0 or 1");
     if (geometry_rank < 1 || geometry_rank > VBNMF_MAX_RANK || n_wg < 1) return fail(VBNMF_ERR_BAD_ARG, "bad geometry");
-    if (int rc = check_device(device)) return rc;
-    HIPCHECK(hipSetDevice(device));
+    if (int rc = use_device(device)) return rc;
     const int R = padded_rank(geometry_rank);
     const int64_t nmaj = side == 0 ? X->M.n : X->M.m, nmin = side == 0 ? X->M.m : X->M.n;
     int rc = VBNMF_OK;
@@ -1451,8 +1263,7 @@ int vbnmf_matrix_preload_layout(const vbnmf_matrix *X, int32_t side, int32_t geo
 // first (a sharded sweep's peers waiting for the layouts) spends that wait here.
 int vbnmf_device_warmup(int32_t device)
 {
-    if (int rc = check_device(device)) return rc;
-    HIPCHECK(hipSetDevice(device));
+    if (int rc = use_device(device)) return rc;
     double *p = nullptr;
     if (int rc = dev_alloc(&p, 1024)) return rc;
     double host[8] = {0};
@@ -3377,15 +3188,6 @@ int consensus_download(vbnmf_consensus *c, std::vector<uint8_t> &labels, int64_t
 }
 }  // namespace vbnmf
 
-namespace vbnmf {
-int coph_dev_use(int device)
-{
-    if (int rc = check_device(device)) return rc;
-    HIPCHECK(hipSetDevice(device));
-    return VBNMF_OK;
-}
-}  // namespace vbnmf
-
 extern "C" {
 
 void vbnmf_consensus_destroy(vbnmf_consensus *c)
@@ -3403,8 +3205,7 @@ int vbnmf_consensus_create(int64_t m, int32_t rank, int32_t max_runs, int32_t de
     *out = nullptr;
     if (m < 1 || rank < 1 || rank > VBNMF_MAX_RANK || max_runs < 1)
         return fail(VBNMF_ERR_BAD_ARG, "consensus accumulator needs m >= 1, 1 <= rank <= %d, max_runs >= 1", VBNMF_MAX_RANK);
-    if (int rc = check_device(device)) return rc;
-    HIPCHECK(hipSetDevice(device));
+    if (int rc = use_device(device)) return rc;
     std::unique_ptr<vbnmf_consensus, void (*)(vbnmf_consensus *)> c(new (std::nothrow) vbnmf_consensus(), vbnmf_consensus_destroy);
     if (!c) return fail(VBNMF_ERR_OOM, "out of host memory");
     c->device = device; c->m = m; c->r = rank; c->max_runs = max_runs;
@@ -3721,8 +3522,7 @@ int vbnmf_test_special_host(int32_t kind, int64_t n, const double *x, double *y)
 int vbnmf_test_special_device(int32_t kind, int64_t n, const double *x, double *y)
 {
     if (!x || !y || n < 0) return fail(VBNMF_ERR_BAD_ARG, "NULL argument");
-    if (int rc = check_device(0)) return rc;
-    HIPCHECK(hipSetDevice(0));
+    if (int rc = use_device(0)) return rc;
     double *dx = nullptr, *dy = nullptr;
     LogTabEntry *dt = nullptr;
     std::vector<LogTabEntry> tab(kLogTabSize);
@@ -3746,27 +3546,11 @@ int vbnmf_test_special_device(int32_t kind, int64_t n, const double *x, double *
 
 namespace {
 
-// What a dense-SVD test hook holds on the device (and pinned): released on every return path.
-struct HookBuffers {
-    std::vector<void *> dev;
+// What a dense-SVD test hook holds on the device (DeviceCall's alloc / upload; never entered: use_device(0) chose the device)
+// and pinned: released on every return path.
+struct HookBuffers : DeviceCall {
     void *pinned = nullptr;
-    ~HookBuffers()
-    {
-        for (void *p : dev) dev_free(p);
-        if (pinned) (void)hipHostFree(pinned);
-    }
-    int alloc(double **p, size_t count)
-    {
-        if (int rc = dev_alloc(p, count)) return rc;
-        dev.push_back(*p);
-        return VBNMF_OK;
-    }
-    int upload(double **p, const double *src, size_t count)
-    {
-        if (int rc = alloc(p, count)) return rc;
-        HIPCHECK(hipMemcpy(*p, src, count * sizeof(double), hipMemcpyHostToDevice));
-        return VBNMF_OK;
-    }
+    ~HookBuffers() { if (pinned) (void)hipHostFree(pinned); }
 };
 
 int download(double *dst, const double *src, size_t count)
@@ -3779,14 +3563,6 @@ int download(double *dst, const double *src, size_t count)
 int hook_width(int32_t R)
 {
     return with_rank_up_to_64(R, [](auto) { return (int)VBNMF_OK; });
-}
-
-// device 0 for a test hook, looked for after the arguments have passed
-int hook_device()
-{
-    if (int rc = check_device(0)) return rc;
-    HIPCHECK(hipSetDevice(0));
-    return VBNMF_OK;
 }
 
 constexpr int64_t kHookMaxRows = (int64_t)1 << 24;           // 8 GB of doubles at R = 64: a test has no use for more
@@ -3849,7 +3625,7 @@ int vbnmf_test_hyper_update_device(int64_t count, const int32_t *flags, const do
     if (count < 1 || count > (1 << 20)) return fail(VBNMF_ERR_BAD_ARG, "count must be in [1, 2^20]");
     for (int64_t q = 0; q < 4 * count; q++)
         if (!(hyper_in[q] > 0.0) || !std::isfinite(hyper_in[q])) return fail(VBNMF_ERR_BAD_ARG, "hyper-parameters must be finite and > 0");
-    if (int rc = hook_device()) return rc;
+    if (int rc = use_device(0)) return rc;
     HookBuffers hb;
     const size_t n = (size_t)count;
     double *dfl = nullptr, *dst = nullptr, *dhy = nullptr, *dfa = nullptr, *dit = nullptr, *dtr = nullptr;   // (the int32 arrays in double-sized buffers)
@@ -3878,7 +3654,7 @@ int vbnmf_test_svd_gram(int32_t R, int64_t N, const double *A, double *gp)
 {
     if (!A || !gp || N < 1 || N > kHookMaxRows) return fail(VBNMF_ERR_BAD_ARG, "NULL argument or N outside [1, 2^24]");
     if (int rc = hook_width(R)) return rc;
-    if (int rc = hook_device()) return rc;
+    if (int rc = use_device(0)) return rc;
     HookBuffers hb;
     double *dA = nullptr, *dgp = nullptr;
     const size_t RR = (size_t)R * R;
@@ -3901,7 +3677,7 @@ int vbnmf_test_svd_small(int32_t R, int32_t k, int32_t mode, int32_t nb, const d
     if (nb < 1 || nb > 65536) return fail(VBNMF_ERR_BAD_ARG, "nb must be in [1, 65536]");
     if (int rc = hook_width(R)) return rc;
     if (k < 1 || k > R) return fail(VBNMF_ERR_BAD_ARG, "k must be in [1, R]");
-    if (int rc = hook_device()) return rc;
+    if (int rc = use_device(0)) return rc;
     HookBuffers hb;
     const size_t RR = (size_t)R * R;
     double *dgp = nullptr, *dS = nullptr, *dS2 = nullptr, *dvals = nullptr, *dstat = nullptr, *hv = nullptr, *hv_dev = nullptr;
@@ -3940,7 +3716,7 @@ int vbnmf_test_svd_apply(int32_t R, int64_t N, const double *A, const double *S,
 {
     if (!A || !S || !B || N < 1 || N > kHookMaxRows) return fail(VBNMF_ERR_BAD_ARG, "NULL argument or N outside [1, 2^24]");
     if (int rc = hook_width(R)) return rc;
-    if (int rc = hook_device()) return rc;
+    if (int rc = use_device(0)) return rc;
     HookBuffers hb;
     double *dA = nullptr, *dS = nullptr, *dB = nullptr;
     if (int rc = hb.upload(&dA, A, (size_t)N * R)) return rc;
@@ -3963,7 +3739,7 @@ int vbnmf_test_svd_normal(int64_t nmaj, int32_t r, int32_t R, uint64_t seed, dou
     if (!g || nmaj < 1 || nmaj > kHookMaxRows) return fail(VBNMF_ERR_BAD_ARG, "NULL argument or nmaj outside [1, 2^24]");
     if (int rc = hook_width(R)) return rc;
     if (r < 1 || r > R) return fail(VBNMF_ERR_BAD_ARG, "r must be in [1, R]");
-    if (int rc = hook_device()) return rc;
+    if (int rc = use_device(0)) return rc;
     HookBuffers hb;
     double *dg = nullptr;
     const int64_t cnt = nmaj * R;
@@ -4200,15 +3976,6 @@ int with_csc(int64_t n, int64_t m, int32_t r, const int32_t *p, const int32_t *i
 
 extern "C" {
 
-// Gives every device buffer the pool holds back to the driver (buffers in use by live engines are not touched).
-void vbnmf_pool_trim(void)
-{
-    DevicePool &P = device_pool();
-    std::vector<PoolBuf> drop;
-    { std::lock_guard<std::mutex> g(P.mu); drop.swap(P.free_list); P.held = 0; }
-    for (const PoolBuf &b : drop) (void)hipFree(b.p);
-}
-
 void vbnmf_stateless_cache_clear(void)
 {
     StatelessCache &C = stateless_cache();
@@ -4248,1139 +4015,6 @@ int vbnmf_ml_update_csc(int64_t n, int64_t m, int32_t r, const int32_t *p, const
 {
     if (!w_in || !h_in) return fail(VBNMF_ERR_BAD_ARG, "w or h is NULL");
     return with_csc(n, m, r, p, i, x, [&](vbnmf_engine *e) { return ml_update_once(e, w_in, h_in, prior, gamma_a, gamma_b, w, h, lk); });
-}
-
-}  // extern "C"
-
-// ---- projection of new cells onto a fitted basis (project.h): no layout, no engine -- the column range's compressed columns,
-// the basis and the start go up once, one launch takes every cell to its own stop.
-namespace {
-
-thread_local double tl_project_kernel_ms = 0.0;
-
-struct ProjectDevice {
-    int64_t *colptr = nullptr;
-    int32_t *row = nullptr, *it = nullptr, *reason = nullptr;
-    double *val = nullptr, *W = nullptr, *cw = nullptr, *H = nullptr, *lk = nullptr;
-    double *eh = nullptr, *dh = nullptr;  // (the VB projection's further results)
-    double *S = nullptr, *lgx = nullptr, *seh = nullptr, *sll = nullptr, *hist = nullptr;   // (the coupled VB projection's carried
-    VbpCtl *ctl = nullptr;                                                                  //  state, cell sums and control block)
-    unsigned int *ticket = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    bool queued = false;
-    int caller_device = -1;               // the device that was current when the call came in: current again when it returns
-    ~ProjectDevice()
-    {
-        if (queued) (void)hipStreamSynchronize(nullptr);
-        dev_free(colptr); dev_free(row); dev_free(it); dev_free(reason); dev_free(val); dev_free(W); dev_free(cw); dev_free(H);
-        dev_free(lk); dev_free(eh); dev_free(dh); dev_free(ticket);
-        dev_free(S); dev_free(lgx); dev_free(seh); dev_free(sll); dev_free(hist); dev_free(ctl);
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-        if (caller_device >= 0) (void)hipSetDevice(caller_device);
-    }
-};
-
-int project_columns(const Matrix &M, int64_t cb, int64_t ce, int32_t r, const double *w, double *h, int32_t prior, double ga, double gb,
-                    int32_t max_it, double tol, int32_t device, double *lk_cell, int32_t *it_cell, int32_t *reason_cell)
-{
-    const int64_t n = M.n, nc = ce - cb;
-    const int R = padded_rank(r);
-    ProjectDevice D;
-    (void)hipGetDevice(&D.caller_device);
-    HIPCHECK(hipSetDevice(device));
-    // the basis by rows, R wide (what a cell gathers), colSums(w) (R/factorize.R:9; every column added gene by gene, in order)
-    // and the start, cell by cell -- on the library's host threads
-    std::vector<double> Wp((size_t)n * R, 0.0), cw((size_t)R, 0.0), Hp((size_t)nc * R, 0.0);
-    parallel_for(n, [&](int64_t b, int64_t e, int) {
-        for (int64_t i = b; i < e; i++)
-            for (int k = 0; k < r; k++) Wp[(size_t)i * R + k] = w[(size_t)k * n + i];
-    });
-    parallel_for(r, [&](int64_t b, int64_t e, int) {
-        for (int64_t k = b; k < e; k++) {
-            double s = 0.0;
-            for (int64_t i = 0; i < n; i++) s += w[(size_t)k * n + i];
-            cw[k] = s;
-        }
-    });
-    parallel_for(nc, [&](int64_t b, int64_t e, int) {
-        for (int64_t j = b; j < e; j++)
-            for (int k = 0; k < r; k++) Hp[(size_t)j * R + k] = h[(size_t)j * r + k];
-    });
-    const int64_t e0 = M.colptr[cb], ne = M.colptr[ce] - e0;
-
-    if (int rc = dev_alloc(&D.colptr, (size_t)nc + 1)) return rc;
-    if (int rc = dev_alloc(&D.row, (size_t)ne)) return rc;
-    if (int rc = dev_alloc(&D.val, (size_t)ne)) return rc;
-    if (int rc = dev_alloc(&D.W, Wp.size())) return rc;
-    if (int rc = dev_alloc(&D.cw, cw.size())) return rc;
-    if (int rc = dev_alloc(&D.H, Hp.size())) return rc;
-    if (int rc = dev_alloc(&D.lk, (size_t)nc)) return rc;
-    if (int rc = dev_alloc(&D.it, (size_t)nc)) return rc;
-    if (int rc = dev_alloc(&D.reason, (size_t)nc)) return rc;
-    if (int rc = dev_alloc(&D.ticket, 1)) return rc;
-    HIPCHECK(hipMemcpy(D.colptr, M.colptr.data() + cb, ((size_t)nc + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
-    if (ne > 0) {
-        HIPCHECK(hipMemcpy(D.row, M.row.data() + e0, (size_t)ne * sizeof(int32_t), hipMemcpyHostToDevice));
-        HIPCHECK(hipMemcpy(D.val, M.val.data() + e0, (size_t)ne * sizeof(double), hipMemcpyHostToDevice));
-    }
-    HIPCHECK(hipMemcpy(D.W, Wp.data(), Wp.size() * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHECK(hipMemcpy(D.cw, cw.data(), cw.size() * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHECK(hipMemcpy(D.H, Hp.data(), Hp.size() * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHECK(hipMemsetAsync(D.ticket, 0, sizeof(unsigned int), nullptr));
-
-    ProjectArgs a;
-    a.colptr = D.colptr; a.base = e0; a.row = D.row; a.val = D.val; a.W = D.W; a.cw = D.cw; a.H = D.H; a.lk = D.lk; a.it = D.it;
-    a.reason = D.reason; a.ticket = D.ticket; a.ncell = nc; a.r = r; a.prior = prior ? 1 : 0; a.max_it = max_it;
-    a.ga = ga; a.gb = gb; a.tol = tol; a.eps = 2.220446049250313e-16;
-    // a persistent grid: as many workgroups as a CU holds threads for (the kernel's few KB of LDS do not bound it)
-    int cus = 0;
-    HIPCHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
-    if (cus <= 0) cus = 256;
-    const unsigned grid = (unsigned)std::min<int64_t>(nc, (int64_t)cus * (2048 / kProjThreads));
-    HIPCHECK(hipEventCreate(&D.ev0));
-    HIPCHECK(hipEventCreate(&D.ev1));
-    HIPCHECK(hipEventRecord(D.ev0, nullptr));
-    D.queued = true;
-    int rc = with_rank(R, [&](auto rt) {
-        hipLaunchKernelGGL((k_project<rt()>), dim3(grid), dim3(kProjThreads), 0, nullptr, a);
-        HIPCHECK(hipGetLastError());
-        return (int)VBNMF_OK;
-    });
-    if (rc) return rc;
-    HIPCHECK(hipEventRecord(D.ev1, nullptr));
-    HIPCHECK(hipMemcpy(Hp.data(), D.H, Hp.size() * sizeof(double), hipMemcpyDeviceToHost));
-    float ms = 0.0f;
-    HIPCHECK(hipEventElapsedTime(&ms, D.ev0, D.ev1));
-    tl_project_kernel_ms = ms;
-    parallel_for(nc, [&](int64_t b, int64_t e, int) {
-        for (int64_t j = b; j < e; j++)
-            for (int k = 0; k < r; k++) h[(size_t)j * r + k] = Hp[(size_t)j * R + k];
-    });
-    if (lk_cell) HIPCHECK(hipMemcpy(lk_cell, D.lk, (size_t)nc * sizeof(double), hipMemcpyDeviceToHost));
-    if (it_cell) HIPCHECK(hipMemcpy(it_cell, D.it, (size_t)nc * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (reason_cell) HIPCHECK(hipMemcpy(reason_cell, D.reason, (size_t)nc * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return VBNMF_OK;
-}
-
-// ---- the same for a VB fit's posterior basis (vbproject.h): the table lw | lw log lw by rows, colSums(ew) and the start go
-// up once, one launch takes every cell to its own stop.
-thread_local double tl_vb_project_kernel_ms = 0.0;
-
-// What both VB projections put on the device (vbproject.h): per gene, 2 R wide, lw_i. | (lw log lw)_i. (R/bayesian.R:90; padding
-// columns 0), colSums(ew) (:80; every column added gene by gene, in order), the start cell by cell -- formed on the library's host
-// threads --, the cells' compressed columns, and room for eh, dh and the cell evidences.
-int vb_project_upload(const Matrix &M, int64_t cb, int64_t ce, int32_t r, const double *lw, const double *ew, const double *lh,
-                      ProjectDevice &D)
-{
-    const int64_t n = M.n, nc = ce - cb;
-    const int R = padded_rank(r);
-    std::vector<double> Tp((size_t)n * 2 * R, 0.0), cew((size_t)R, 0.0), Hp((size_t)nc * R, 0.0);
-    parallel_for(n, [&](int64_t b, int64_t e, int) {
-        for (int64_t i = b; i < e; i++)
-            for (int k = 0; k < r; k++) {
-                const double v = lw[(size_t)k * n + i];
-                Tp[(size_t)i * 2 * R + k] = v;
-                Tp[(size_t)i * 2 * R + R + k] = v * std::log(v);
-            }
-    });
-    parallel_for(r, [&](int64_t b, int64_t e, int) {
-        for (int64_t k = b; k < e; k++) {
-            double s = 0.0;
-            for (int64_t i = 0; i < n; i++) s += ew[(size_t)k * n + i];
-            cew[k] = s;
-        }
-    });
-    parallel_for(nc, [&](int64_t b, int64_t e, int) {
-        for (int64_t j = b; j < e; j++)
-            for (int k = 0; k < r; k++) Hp[(size_t)j * R + k] = lh[(size_t)j * r + k];
-    });
-    const int64_t e0 = M.colptr[cb], ne = M.colptr[ce] - e0;
-
-    if (int rc = dev_alloc(&D.colptr, (size_t)nc + 1)) return rc;
-    if (int rc = dev_alloc(&D.row, (size_t)ne)) return rc;
-    if (int rc = dev_alloc(&D.val, (size_t)ne)) return rc;
-    if (int rc = dev_alloc(&D.W, Tp.size())) return rc;
-    if (int rc = dev_alloc(&D.cw, cew.size())) return rc;
-    if (int rc = dev_alloc(&D.H, Hp.size())) return rc;
-    if (int rc = dev_alloc(&D.eh, Hp.size())) return rc;
-    if (int rc = dev_alloc(&D.dh, Hp.size())) return rc;
-    if (int rc = dev_alloc(&D.lk, (size_t)nc)) return rc;
-    HIPCHECK(hipMemcpy(D.colptr, M.colptr.data() + cb, ((size_t)nc + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
-    if (ne > 0) {
-        HIPCHECK(hipMemcpy(D.row, M.row.data() + e0, (size_t)ne * sizeof(int32_t), hipMemcpyHostToDevice));
-        HIPCHECK(hipMemcpy(D.val, M.val.data() + e0, (size_t)ne * sizeof(double), hipMemcpyHostToDevice));
-    }
-    HIPCHECK(hipMemcpy(D.W, Tp.data(), Tp.size() * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHECK(hipMemcpy(D.cw, cew.data(), cew.size() * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHECK(hipMemcpy(D.H, Hp.data(), Hp.size() * sizeof(double), hipMemcpyHostToDevice));
-    return VBNMF_OK;
-}
-
-// lh, eh, dh (each may be NULL) of the cells back into r x cells column-major arrays
-int vb_project_download(const ProjectDevice &D, int64_t nc, int32_t r, double *lh, double *eh, double *dh)
-{
-    const int R = padded_rank(r);
-    std::vector<double> back((size_t)nc * R);
-    double *const outs[3] = {lh, eh, dh};
-    const double *const srcs[3] = {D.H, D.eh, D.dh};
-    for (int q = 0; q < 3; q++) {
-        if (!outs[q]) continue;
-        HIPCHECK(hipMemcpy(back.data(), srcs[q], back.size() * sizeof(double), hipMemcpyDeviceToHost));
-        double *out = outs[q];
-        parallel_for(nc, [&](int64_t b, int64_t e, int) {
-            for (int64_t j = b; j < e; j++)
-                for (int k = 0; k < r; k++) out[(size_t)j * r + k] = back[(size_t)j * R + k];
-        });
-    }
-    return VBNMF_OK;
-}
-
-int vb_project_columns(const Matrix &M, int64_t cb, int64_t ce, int32_t r, const double *lw, const double *ew, double ah, double bh,
-                       double fudge, double *lh, double *eh, double *dh, int32_t max_it, double tol, int32_t device, double *ev_cell,
-                       int32_t *it_cell, int32_t *reason_cell)
-{
-    const int64_t nc = ce - cb, e0 = M.colptr[cb];
-    const int R = padded_rank(r);
-    ProjectDevice D;
-    (void)hipGetDevice(&D.caller_device);
-    HIPCHECK(hipSetDevice(device));
-    if (int rc = vb_project_upload(M, cb, ce, r, lw, ew, lh, D)) return rc;
-    if (int rc = dev_alloc(&D.it, (size_t)nc)) return rc;
-    if (int rc = dev_alloc(&D.reason, (size_t)nc)) return rc;
-    if (int rc = dev_alloc(&D.ticket, 1)) return rc;
-    HIPCHECK(hipMemsetAsync(D.ticket, 0, sizeof(unsigned int), nullptr));
-
-    VbProjectArgs a;
-    a.colptr = D.colptr; a.base = e0; a.row = D.row; a.val = D.val; a.T = D.W; a.cew = D.cw; a.LH = D.H; a.EH = D.eh; a.DH = D.dh;
-    a.ev = D.lk; a.it = D.it; a.reason = D.reason; a.ticket = D.ticket; a.ncell = nc; a.r = r; a.max_it = max_it;
-    a.ah = ah; a.bh = bh; a.tol = tol; a.fudge = fudge;
-    // a persistent grid, as project_columns'
-    int cus = 0;
-    HIPCHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
-    if (cus <= 0) cus = 256;
-    const unsigned grid = (unsigned)std::min<int64_t>(nc, (int64_t)cus * (2048 / kProjThreads));
-    HIPCHECK(hipEventCreate(&D.ev0));
-    HIPCHECK(hipEventCreate(&D.ev1));
-    HIPCHECK(hipEventRecord(D.ev0, nullptr));
-    D.queued = true;
-    int rc = with_rank(R, [&](auto rt) {
-        hipLaunchKernelGGL((k_vb_project<rt()>), dim3(grid), dim3(kProjThreads), 0, nullptr, a);
-        HIPCHECK(hipGetLastError());
-        return (int)VBNMF_OK;
-    });
-    if (rc) return rc;
-    HIPCHECK(hipEventRecord(D.ev1, nullptr));
-    if (int rc = vb_project_download(D, nc, r, lh, eh, dh)) return rc;
-    float ms = 0.0f;
-    HIPCHECK(hipEventSynchronize(D.ev1));
-    HIPCHECK(hipEventElapsedTime(&ms, D.ev0, D.ev1));
-    tl_vb_project_kernel_ms = ms;
-    if (ev_cell) HIPCHECK(hipMemcpy(ev_cell, D.lk, (size_t)nc * sizeof(double), hipMemcpyDeviceToHost));
-    if (it_cell) HIPCHECK(hipMemcpy(it_cell, D.it, (size_t)nc * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (reason_cell) HIPCHECK(hipMemcpy(reason_cell, D.reason, (size_t)nc * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return VBNMF_OK;
-}
-
-// ---- the coupled form (vbproject.h, k_vbp_step / k_vbp_control): the same upload plus what a cell carries between launches;
-// (step, control) pairs are queued eight steps ahead, never past max_it, and the control block is read after each batch.
-constexpr int kVbpBatch = 8;
-
-int vb_project_coupled_columns(const Matrix &M, int64_t cb, int64_t ce, int32_t r, const double *lw, const double *ew, double *hyper,
-                               const int32_t *flags, int32_t n0, int32_t dn, double fudge, double *lh, double *eh, double *dh,
-                               int32_t max_it, double tol, int32_t device, double *ev_cell, int32_t *it_cell, int32_t *reason_cell,
-                               int32_t *it_out, int32_t *reason_out, double *evidence, double *history, int64_t history_rows)
-{
-    const int64_t nc = ce - cb, e0 = M.colptr[cb];
-    const int R = padded_rank(r);
-    ProjectDevice D;
-    (void)hipGetDevice(&D.caller_device);
-    HIPCHECK(hipSetDevice(device));
-    const int64_t hrows = history ? std::min<int64_t>(std::max<int64_t>(history_rows, 0), max_it) : 0;
-    if (int rc = vb_project_upload(M, cb, ce, r, lw, ew, lh, D)) return rc;
-    if (int rc = dev_alloc(&D.S, (size_t)nc * R)) return rc;
-    if (int rc = dev_alloc(&D.lgx, (size_t)nc)) return rc;
-    if (int rc = dev_alloc(&D.seh, (size_t)nc)) return rc;
-    if (int rc = dev_alloc(&D.sll, (size_t)nc)) return rc;
-    if (int rc = dev_alloc(&D.hist, (size_t)hrows * 5)) return rc;
-    if (int rc = dev_alloc(&D.ctl, 1)) return rc;
-    VbpCtl c;
-    std::memset(&c, 0, sizeof c);                            // it, stop, reason, lk0, the ticket: 0
-    c.hyper[0] = 1.0; c.hyper[1] = 1.0; c.hyper[2] = hyper[0]; c.hyper[3] = hyper[1];
-    c.tol = tol; c.max_it = max_it; c.n0 = n0; c.dn = dn;
-    c.flags[2] = flags[0] ? 1 : 0; c.flags[3] = flags[1] ? 1 : 0;
-    HIPCHECK(hipMemcpy(D.ctl, &c, sizeof c, hipMemcpyHostToDevice));
-
-    VbpStepArgs a;
-    a.colptr = D.colptr; a.base = e0; a.row = D.row; a.val = D.val; a.T = D.W; a.cew = D.cw; a.LH = D.H; a.EH = D.eh; a.DH = D.dh;
-    a.S = D.S; a.lgx = D.lgx; a.ev = D.lk; a.seh = D.seh; a.sll = D.sll; a.ctl = D.ctl; a.ncell = nc; a.r = r; a.fudge = fudge;
-    // a persistent grid, as project_columns'
-    int cus = 0;
-    HIPCHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
-    if (cus <= 0) cus = 256;
-    const unsigned grid = (unsigned)std::min<int64_t>(nc, (int64_t)cus * (2048 / kProjThreads));
-    HIPCHECK(hipEventCreate(&D.ev0));
-    HIPCHECK(hipEventCreate(&D.ev1));
-    HIPCHECK(hipEventRecord(D.ev0, nullptr));
-    D.queued = true;
-    int32_t queued = 0;
-    while (!c.stop && queued < max_it) {
-        const int32_t batch = std::min<int32_t>(kVbpBatch, max_it - queued);
-        int rc = with_rank(R, [&](auto rt) {
-            for (int32_t q = 0; q < batch; q++) {
-                hipLaunchKernelGGL((k_vbp_step<rt()>), dim3(grid), dim3(kProjThreads), 0, nullptr, a);
-                hipLaunchKernelGGL(k_vbp_control, dim3(1), dim3(1024), 0, nullptr, D.lk, D.seh, D.sll, nc, (int)r, D.ctl, hrows ? D.hist : nullptr,
-                                   hrows);
-            }
-            HIPCHECK(hipGetLastError());
-            return (int)VBNMF_OK;
-        });
-        if (rc) return rc;
-        queued += batch;
-        HIPCHECK(hipMemcpy(&c, D.ctl, sizeof c, hipMemcpyDeviceToHost));     // (waits for the batch)
-    }
-    if (!c.stop) return fail(VBNMF_ERR_HIP, "the coupled projection's device loop did not stop within max_it = %d steps", max_it);
-    HIPCHECK(hipEventRecord(D.ev1, nullptr));
-    if (int rc = vb_project_download(D, nc, r, lh, eh, dh)) return rc;
-    float ms = 0.0f;
-    HIPCHECK(hipEventSynchronize(D.ev1));
-    HIPCHECK(hipEventElapsedTime(&ms, D.ev0, D.ev1));
-    tl_vb_project_kernel_ms = ms;
-    if (ev_cell) HIPCHECK(hipMemcpy(ev_cell, D.lk, (size_t)nc * sizeof(double), hipMemcpyDeviceToHost));
-    if (it_cell) std::fill(it_cell, it_cell + nc, c.it);                     // one stop: every cell made the same steps
-    if (reason_cell) std::fill(reason_cell, reason_cell + nc, c.reason);
-    const int64_t rows = std::min<int64_t>(hrows, c.it);
-    if (rows > 0) HIPCHECK(hipMemcpy(history, D.hist, (size_t)rows * 5 * sizeof(double), hipMemcpyDeviceToHost));
-    hyper[0] = c.hyper[2]; hyper[1] = c.hyper[3];
-    if (it_out) *it_out = c.it;
-    if (reason_out) *reason_out = c.reason;
-    if (evidence) *evidence = c.E;
-    return VBNMF_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int vbnmf_matrix_project(const vbnmf_matrix *X, int64_t col_begin, int64_t col_end, int32_t r, const double *w, double *h,
-                         int32_t prior, double gamma_a, double gamma_b, int32_t max_it, double tol, int32_t device,
-                         double *lk_cell, int32_t *it_cell, int32_t *reason_cell)
-{
-    if (!X || !w || !h) return fail(VBNMF_ERR_BAD_ARG, "NULL argument");
-    if (X->M.shell) return fail(VBNMF_ERR_BAD_ARG, "a shell matrix holds no entries: project needs the compressed columns");
-    if (r < 1 || r > VBNMF_MAX_RANK) return fail(VBNMF_ERR_BAD_ARG, "rank %d is outside [1, %d]", r, VBNMF_MAX_RANK);
-    if (col_begin < 0 || col_end > X->M.m || col_begin >= col_end)
-        return fail(VBNMF_ERR_BAD_ARG, "column range [%lld, %lld) is empty or outside the matrix's %lld columns", (long long)col_begin,
-                    (long long)col_end, (long long)X->M.m);
-    if (max_it < 1) return fail(VBNMF_ERR_BAD_ARG, "max_it must be >= 1");
-    if (int rc = check_device(device)) return rc;
-    try {
-        return project_columns(X->M, col_begin, col_end, r, w, h, prior, gamma_a, gamma_b, max_it, tol, device, lk_cell, it_cell, reason_cell);
-    } catch (const std::bad_alloc &) {
-        return fail(VBNMF_ERR_OOM, "out of host memory for the projection's staging arrays");
-    } catch (const std::exception &ex) {
-        return fail(VBNMF_ERR_HIP, "vbnmf_matrix_project: %s", ex.what());
-    }
-}
-
-int vbnmf_project_info(int32_t r, int32_t *pass_entries, double *last_kernel_ms)
-{
-    if (r < 1 || r > VBNMF_MAX_RANK) return fail(VBNMF_ERR_BAD_ARG, "rank %d is outside [1, %d]", r, VBNMF_MAX_RANK);
-    if (pass_entries) *pass_entries = proj_pass_entries(padded_rank(r));
-    if (last_kernel_ms) *last_kernel_ms = tl_project_kernel_ms;
-    return VBNMF_OK;
-}
-
-int vbnmf_matrix_vb_project(const vbnmf_matrix *X, int64_t col_begin, int64_t col_end, int32_t r, const double *lw, const double *ew,
-                            double ah, double bh, double fudge, double *lh, double *eh, double *dh, int32_t max_it, double tol,
-                            int32_t device, double *ev_cell, int32_t *it_cell, int32_t *reason_cell)
-{
-    if (!X || !lw || !ew || !lh) return fail(VBNMF_ERR_BAD_ARG, "NULL argument");
-    if (X->M.shell) return fail(VBNMF_ERR_BAD_ARG, "a shell matrix holds no entries: vb_project needs the compressed columns");
-    if (r < 1 || r > VBNMF_MAX_RANK) return fail(VBNMF_ERR_BAD_ARG, "rank %d is outside [1, %d]", r, VBNMF_MAX_RANK);
-    if (col_begin < 0 || col_end > X->M.m || col_begin >= col_end)
-        return fail(VBNMF_ERR_BAD_ARG, "column range [%lld, %lld) is empty or outside the matrix's %lld columns", (long long)col_begin,
-                    (long long)col_end, (long long)X->M.m);
-    if (max_it < 1) return fail(VBNMF_ERR_BAD_ARG, "max_it must be >= 1");
-    if (!(ah > 0.0) || !(bh > 0.0)) return fail(VBNMF_ERR_BAD_ARG, "ah and bh must be > 0 (got %g, %g)", ah, bh);
-    if (int rc = check_device(device)) return rc;
-    try {
-        return vb_project_columns(X->M, col_begin, col_end, r, lw, ew, ah, bh, fudge, lh, eh, dh, max_it, tol, device, ev_cell, it_cell,
-                                  reason_cell);
-    } catch (const std::bad_alloc &) {
-        return fail(VBNMF_ERR_OOM, "out of host memory for the projection's staging arrays");
-    } catch (const std::exception &ex) {
-        return fail(VBNMF_ERR_HIP, "vbnmf_matrix_vb_project: %s", ex.what());
-    }
-}
-
-int vbnmf_matrix_vb_project_coupled(const vbnmf_matrix *X, int64_t col_begin, int64_t col_end, int32_t r, const double *lw,
-                                    const double *ew, double *hyper, const int32_t *flags, int32_t n0, int32_t dn, double fudge,
-                                    double *lh, double *eh, double *dh, int32_t max_it, double tol, int32_t device, double *ev_cell,
-                                    int32_t *it_cell, int32_t *reason_cell, int32_t *it, int32_t *reason, double *evidence,
-                                    double *history, int64_t history_rows)
-{
-    if (!X || !lw || !ew || !lh || !hyper || !flags) return fail(VBNMF_ERR_BAD_ARG, "NULL argument");
-    if (X->M.shell) return fail(VBNMF_ERR_BAD_ARG, "a shell matrix holds no entries: vb_project needs the compressed columns");
-    if (r < 1 || r > VBNMF_MAX_RANK) return fail(VBNMF_ERR_BAD_ARG, "rank %d is outside [1, %d]", r, VBNMF_MAX_RANK);
-    if (col_begin < 0 || col_end > X->M.m || col_begin >= col_end)
-        return fail(VBNMF_ERR_BAD_ARG, "column range [%lld, %lld) is empty or outside the matrix's %lld columns", (long long)col_begin,
-                    (long long)col_end, (long long)X->M.m);
-    if (max_it < 1) return fail(VBNMF_ERR_BAD_ARG, "max_it must be >= 1");
-    if (!(hyper[0] > 0.0) || !(hyper[1] > 0.0) || !std::isfinite(hyper[0]) || !std::isfinite(hyper[1]))
-        return fail(VBNMF_ERR_BAD_ARG, "ah and bh must be > 0 and finite (got %g, %g)", hyper[0], hyper[1]);
-    if (dn < 1) return fail(VBNMF_ERR_BAD_ARG, "dn must be >= 1");
-    if (n0 < 0) return fail(VBNMF_ERR_BAD_ARG, "n0 must be >= 0");
-    if (int rc = check_device(device)) return rc;
-    try {
-        return vb_project_coupled_columns(X->M, col_begin, col_end, r, lw, ew, hyper, flags, n0, dn, fudge, lh, eh, dh, max_it, tol, device,
-                                          ev_cell, it_cell, reason_cell, it, reason, evidence, history, history_rows);
-    } catch (const std::bad_alloc &) {
-        return fail(VBNMF_ERR_OOM, "out of host memory for the projection's staging arrays");
-    } catch (const std::exception &ex) {
-        return fail(VBNMF_ERR_HIP, "vbnmf_matrix_vb_project_coupled: %s", ex.what());
-    }
-}
-
-int vbnmf_vb_project_info(int32_t r, int32_t *pass_entries, double *last_kernel_ms)
-{
-    if (r < 1 || r > VBNMF_MAX_RANK) return fail(VBNMF_ERR_BAD_ARG, "rank %d is outside [1, %d]", r, VBNMF_MAX_RANK);
-    if (pass_entries) *pass_entries = proj_pass_entries(padded_rank(r));
-    if (last_kernel_ms) *last_kernel_ms = tl_vb_project_kernel_ms;
-    return VBNMF_OK;
-}
-
-}  // extern "C"
-
-// ---- per-gene statistics for filter_genes (qc.h): the values grouped by gene and their row pointers go up once, one launch
-// takes every row, the rows the kernel left undecided are finished on the host.
-namespace {
-
-thread_local double tl_qc_times_ms[4] = {0.0, 0.0, 0.0, 0.0};     // grouping by gene, upload, kernel (device events), host finish
-
-struct QcDevice {
-    int64_t *rowptr = nullptr, *nnz = nullptr;
-    double *val = nullptr, *sum = nullptr, *ss = nullptr;
-    int32_t *mode = nullptr;
-    unsigned int *ticket = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    bool queued = false;
-    int caller_device = -1;
-    ~QcDevice()
-    {
-        if (queued) (void)hipStreamSynchronize(nullptr);
-        dev_free(rowptr); dev_free(nnz); dev_free(val); dev_free(sum); dev_free(ss); dev_free(mode); dev_free(ticket);
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-        if (caller_device >= 0) (void)hipSetDevice(caller_device);
-    }
-};
-
-// persistent workgroups of k_gene_stats on a device with `cus` compute units: as many as a CU holds threads for
-int qc_grid(int cus) { return (cus > 0 ? cus : 256) * (2048 / kQcThreads); }
-
-int gene_stats_rows(const Matrix &M, int32_t device, int32_t bins, int64_t *nnz, double *sum, double *ss, int32_t *mode,
-                    int64_t *host_finished)
-{
-    using clock = std::chrono::steady_clock;
-    auto ms_since = [](clock::time_point t0) { return std::chrono::duration<double, std::milli>(clock::now() - t0).count(); };
-    const int64_t n = M.n, m = M.m;
-    for (double &v : tl_qc_times_ms) v = 0.0;
-    QcDevice D;
-    (void)hipGetDevice(&D.caller_device);
-    HIPCHECK(hipSetDevice(device));
-    // the values by gene, on the library's host threads (the cell numbers come with them and are dropped: no cell order, no cache)
-    auto t0 = clock::now();
-    std::vector<int64_t> rptr;
-    BigVec<int32_t> ridx;
-    BigVec<double> rval;
-    transpose_compressed(m, n, M.colptr.data(), M.row.data(), M.val.data(), 0, rptr, ridx, rval, nullptr);
-    BigVec<int32_t>().swap(ridx);
-    tl_qc_times_ms[0] = ms_since(t0);
-
-    t0 = clock::now();
-    if (int rc = dev_alloc(&D.rowptr, (size_t)n + 1)) return rc;
-    if (int rc = dev_alloc(&D.nnz, (size_t)n)) return rc;
-    if (int rc = dev_alloc(&D.sum, (size_t)n)) return rc;
-    if (int rc = dev_alloc(&D.ss, (size_t)n)) return rc;
-    if (int rc = dev_alloc(&D.mode, (size_t)n)) return rc;
-    if (int rc = dev_alloc(&D.ticket, 1)) return rc;
-    if (int rc = dev_alloc(&D.val, rval.size())) return rc;
-    HIPCHECK(hipMemcpy(D.rowptr, rptr.data(), ((size_t)n + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
-    // the values go up as the doubles they are: packing integer counts into 2-byte words first cost more on the host than the
-    // shorter copy saved, and the kernel's time did not change (profiles/qc_times.txt)
-    if (!rval.empty()) HIPCHECK(hipMemcpy(D.val, rval.data(), rval.size() * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHECK(hipMemsetAsync(D.ticket, 0, sizeof(unsigned int), nullptr));
-    HIPCHECK(hipEventCreate(&D.ev0));
-    HIPCHECK(hipEventCreate(&D.ev1));
-    int cus = 0;
-    HIPCHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
-    const int64_t tickets = (n + kQcTicketRows - 1) / kQcTicketRows;
-    const unsigned grid = (unsigned)std::min<int64_t>(tickets, (int64_t)qc_grid(cus));
-    tl_qc_times_ms[1] = ms_since(t0);
-    QcArgs a;
-    a.rowptr = D.rowptr; a.val = D.val; a.n = n; a.m = m; a.bins = bins; a.nnz = D.nnz; a.sum = D.sum; a.ss = D.ss; a.mode = D.mode;
-    a.ticket = D.ticket;
-    HIPCHECK(hipEventRecord(D.ev0, nullptr));
-    D.queued = true;
-    hipLaunchKernelGGL(k_gene_stats, dim3(grid), dim3(kQcThreads), (size_t)kQcLdsFixed + 4 * (size_t)bins, nullptr, a);
-    HIPCHECK(hipGetLastError());
-    HIPCHECK(hipEventRecord(D.ev1, nullptr));
-    HIPCHECK(hipMemcpy(nnz, D.nnz, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost));
-    HIPCHECK(hipMemcpy(sum, D.sum, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
-    HIPCHECK(hipMemcpy(ss, D.ss, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
-    HIPCHECK(hipMemcpy(mode, D.mode, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    float kms = 0.0f;
-    HIPCHECK(hipEventElapsedTime(&kms, D.ev0, D.ev1));
-    tl_qc_times_ms[2] = kms;
-
-    // the rows the kernel left (a value that is no integer in [1, bins)): an exact sort-and-count each
-    t0 = clock::now();
-    std::vector<int64_t> left;
-    for (int64_t i = 0; i < n; i++)
-        if (mode[i] == 2) left.push_back(i);
-    parallel_for((int64_t)left.size(), [&](int64_t b, int64_t e, int) {
-        for (int64_t k = b; k < e; k++) {
-            const int64_t i = left[(size_t)k];
-            mode[i] = gene_mode_host(m, rptr[i + 1] - rptr[i], rval.data() + rptr[i]);
-        }
-    });
-    if (host_finished) *host_finished = (int64_t)left.size();
-    tl_qc_times_ms[3] = ms_since(t0);
-    return VBNMF_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int vbnmf_matrix_gene_stats(const vbnmf_matrix *X, int32_t device, int32_t hist_bins, int64_t *nnz, double *sum, double *ss,
-                            int32_t *mode, int64_t *host_finished)
-{
-    if (!X || !nnz || !sum || !ss || !mode) return fail(VBNMF_ERR_BAD_ARG, "NULL argument");
-    if (X->M.shell) return fail(VBNMF_ERR_STATE, "this matrix handle is a shell (vbnmf_matrix_shell): it holds no entries");
-    if (hist_bins == 0) hist_bins = kQcDefaultBins;
-    if (hist_bins < 2 || hist_bins > kQcMaxBins)
-        return fail(VBNMF_ERR_BAD_ARG, "hist_bins %d is outside [2, %d] (the occurrence table lives in LDS)", hist_bins, kQcMaxBins);
-    if (int rc = check_device(device)) return rc;
-    try {
-        return gene_stats_rows(X->M, device, hist_bins, nnz, sum, ss, mode, host_finished);
-    } catch (const std::bad_alloc &) {
-        return fail(VBNMF_ERR_OOM, "out of host memory grouping the values by gene");
-    } catch (const std::exception &ex) {
-        return fail(VBNMF_ERR_HIP, "vbnmf_matrix_gene_stats: %s", ex.what());
-    }
-}
-
-int vbnmf_qc_info(int32_t *short_row_max, int32_t *pass_entries, int32_t *default_hist_bins, int32_t *grid_workgroups, double *times_ms)
-{
-    if (short_row_max) *short_row_max = kQcShortMax;
-    if (pass_entries) *pass_entries = kQcPassEntries;
-    if (default_hist_bins) *default_hist_bins = kQcDefaultBins;
-    if (grid_workgroups) {
-        int cnt = 0, cus = 0;
-        if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) { (void)hipGetLastError(); *grid_workgroups = 0; }
-        else if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, 0) != hipSuccess) { (void)hipGetLastError(); *grid_workgroups = 0; }
-        else *grid_workgroups = qc_grid(cus);
-    }
-    if (times_ms)
-        for (int k = 0; k < 4; k++) times_ms[k] = tl_qc_times_ms[k];
-    return VBNMF_OK;
-}
-
-}  // extern "C"
-
-// ---- enrichment scores of assign_celltype's permutation loop (gsea.h): every argument is checked and the permutations are
-// inverted on the host, the tables go up once, then one launch of k_gsea_perm per chunk of permutations (the identity first:
-// the observed scores come from the same code) and one of k_gsea_count.
-namespace {
-
-thread_local double tl_gsea_times_ms[4] = {0.0, 0.0, 0.0, 0.0};   // upload, kernels (device events), read-back, host checks + inversion
-
-constexpr int64_t kGseaChunkBytes = 64ll << 20;                   // permutations of one upload: inverse + permutation rows within this
-
-// permutations of one chunk for a table of N rows; VBNMF_GSEA_CHUNK_PERMS (>= 1) makes it smaller
-int64_t gsea_chunk_perms(int64_t N)
-{
-    int64_t c = kGseaChunkBytes / (8 * std::max<int64_t>(N, 1));
-    c = std::max<int64_t>(1, std::min<int64_t>(c, 1 << 20));
-    if (const char *s = getenv("VBNMF_GSEA_CHUNK_PERMS")) {
-        const long v = atol(s);
-        if (v >= 1 && v < c) c = v;
-    }
-    return c;
-}
-
-struct GseaDevice {
-    int32_t *inv = nullptr, *perms = nullptr, *hit_row = nullptr, *M = nullptr, *prefix = nullptr;
-    uint8_t *valid = nullptr, *has_na = nullptr, *hit_is_miss = nullptr;
-    double *wp = nullptr, *es = nullptr, *null_es = nullptr;
-    int64_t *hit_ptr = nullptr;
-    long long *exceed = nullptr;
-    unsigned long long *words = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    bool queued = false;
-    int caller_device = -1;
-    ~GseaDevice()
-    {
-        if (queued) (void)hipStreamSynchronize(nullptr);
-        dev_free(inv); dev_free(perms); dev_free(hit_row); dev_free(M); dev_free(prefix); dev_free(valid); dev_free(has_na);
-        dev_free(hit_is_miss); dev_free(wp); dev_free(es); dev_free(null_es); dev_free(hit_ptr); dev_free(exceed); dev_free(words);
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-        if (caller_device >= 0) (void)hipSetDevice(caller_device);
-    }
-};
-
-// what the host derives from the checked arguments
-struct GseaHost {
-    std::vector<int32_t> M;            // [r x nS]
-    std::vector<uint8_t> has_na;       // [r]
-    std::unique_ptr<int32_t[]> inv;    // [nperm x N], every entry written by gsea_check
-    bool any_na = false;
-    int pad = 1;
-};
-
-int gsea_check(int64_t N, int32_t r, int32_t nS, const uint8_t *valid, const double *wp, const int64_t *hit_ptr, const int32_t *hit_row,
-               const uint8_t *hit_is_miss, int64_t nperm, const int32_t *perms, GseaHost &H)
-{
-    const int64_t nks = (int64_t)r * nS;
-    if (hit_ptr[0] != 0) return fail(VBNMF_ERR_BAD_ARG, "hit_ptr must start at 0");
-    for (int64_t q = 0; q < nks; q++)
-        if (hit_ptr[q + 1] < hit_ptr[q] || hit_ptr[q + 1] - hit_ptr[q] > N)
-            return fail(VBNMF_ERR_BAD_ARG, "hit_ptr is not ascending, or a set has more hits than the table has rows (cluster %lld, set %lld)",
-                        (long long)(q / nS), (long long)(q % nS));
-    if (hit_ptr[nks] > 0 && (!hit_row || !hit_is_miss)) return fail(VBNMF_ERR_BAD_ARG, "NULL argument");
-    H.M.assign((size_t)nks, 0);
-    H.has_na.assign((size_t)r, 0);
-    int64_t maxT = 0;
-    for (int32_t k = 0; k < r; k++) {
-        const uint8_t *v = valid + (int64_t)k * N;
-        int64_t nvalid = 0;
-        for (int64_t i = 0; i < N; i++) nvalid += v[i] != 0;
-        // x * gw^p of R/gsea.R:101 is NaN on a row that is no hit when its weight is not finite; the hits' walk would not see it
-        for (int64_t i = 0; i < N; i++)
-            if (v[i] && !std::isfinite(wp[(int64_t)k * N + i]))
-                return fail(VBNMF_ERR_BAD_ARG, "cluster %d, row %lld: the weight gw^p is not finite", k, (long long)i);
-        H.has_na[(size_t)k] = nvalid < N ? 1 : 0;
-        H.any_na = H.any_na || nvalid < N;
-        for (int32_t s = 0; s < nS; s++) {
-            const int64_t q = (int64_t)k * nS + s;
-            int64_t notmiss = 0, prev = -1;
-            for (int64_t h = hit_ptr[q]; h < hit_ptr[q + 1]; h++) {
-                const int64_t row = hit_row[h];
-                if (row <= prev || row >= N)
-                    return fail(VBNMF_ERR_BAD_ARG, "the hit rows of cluster %d, set %d are not ascending within [0, %lld)", k, s, (long long)N);
-                if (!v[row]) return fail(VBNMF_ERR_BAD_ARG, "cluster %d, set %d: hit row %lld is an NA row (R/gsea.R:93 drops it before the overlap)", k, s, (long long)row);
-                prev = row;
-                notmiss += hit_is_miss[h] == 0;
-            }
-            const int64_t T = hit_ptr[q + 1] - hit_ptr[q], M = nvalid - notmiss;
-            H.M[(size_t)q] = (int32_t)M;
-            if (T > 0 && M > 0) {
-                if (T > kGseaMaxSetHits)
-                    return fail(VBNMF_ERR_BAD_ARG, "cluster %d, set %d has %lld hits; at most %d are sorted in LDS (vbnmf_gsea_info)", k, s, (long long)T, kGseaMaxSetHits);
-                maxT = std::max(maxT, T);
-            }
-        }
-    }
-    while (H.pad < maxT) H.pad <<= 1;
-    // the inverse of every permutation; a row that is none is found here
-    H.inv.reset(new int32_t[std::max<size_t>((size_t)nperm * (size_t)N, 1)]);       // (not initialised: the workers' pages, below)
-    std::atomic<int64_t> bad{-1};
-    parallel_for(nperm, [&](int64_t b0, int64_t b1, int) {
-        for (int64_t b = b0; b < b1; b++) {
-            const int32_t *p = perms + b * N;
-            int32_t *iv = H.inv.get() + b * N;
-            // N entries inside [0, N) are a permutation iff none repeats; of a repeated row the last position stays in iv, so
-            // an earlier one does not read itself back.  Then every entry of iv has been written.
-            bool ok = true;
-            for (int64_t i = 0; i < N && ok; i++) ok = p[i] >= 0 && p[i] < N;
-            if (ok) {
-                for (int64_t i = 0; i < N; i++) iv[p[i]] = (int32_t)i;
-                for (int64_t i = 0; i < N && ok; i++) ok = iv[p[i]] == (int32_t)i;
-            }
-            if (!ok) { int64_t none = -1; bad.compare_exchange_strong(none, b); }
-        }
-    });
-    if (bad.load() >= 0) return fail(VBNMF_ERR_BAD_ARG, "row %lld of perms is no permutation of 0 .. %lld", (long long)bad.load(), (long long)N - 1);
-    return VBNMF_OK;
-}
-
-int gsea_grid(int cus) { return (cus > 0 ? cus : 256) * (2048 / kGseaThreads); }
-
-int gsea_run(int32_t device, int64_t N, int32_t r, int32_t nS, const uint8_t *valid, const double *wp, const int64_t *hit_ptr,
-             const int32_t *hit_row, const uint8_t *hit_is_miss, int64_t nperm, const int32_t *perms, const GseaHost &H,
-             double *es, int64_t *exceed, double *null_es)
-{
-    using clock = std::chrono::steady_clock;
-    auto ms_since = [](clock::time_point t0) { return std::chrono::duration<double, std::milli>(clock::now() - t0).count(); };
-    const int64_t nks = (int64_t)r * nS, nq = nks, nW = (N + 63) / 64;
-    const int64_t chunk = std::min<int64_t>(gsea_chunk_perms(N), std::max<int64_t>(nperm, 1));
-    GseaDevice D;
-    (void)hipGetDevice(&D.caller_device);
-    HIPCHECK(hipSetDevice(device));
-    int cus = 0;
-    HIPCHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
-    const int64_t max_items = std::max<int64_t>(chunk, 1) * r;
-    const unsigned grid_max = (unsigned)std::min<int64_t>(max_items, (int64_t)gsea_grid(cus));
-
-    auto t0 = clock::now();
-    const size_t nhits = (size_t)hit_ptr[nks];
-    if (int rc = dev_alloc(&D.valid, (size_t)r * N)) return rc;
-    if (int rc = dev_alloc(&D.wp, (size_t)r * N)) return rc;
-    if (int rc = dev_alloc(&D.has_na, (size_t)r)) return rc;
-    if (int rc = dev_alloc(&D.hit_ptr, (size_t)nks + 1)) return rc;
-    if (int rc = dev_alloc(&D.hit_row, nhits)) return rc;
-    if (int rc = dev_alloc(&D.hit_is_miss, nhits)) return rc;
-    if (int rc = dev_alloc(&D.M, (size_t)nks)) return rc;
-    if (int rc = dev_alloc(&D.es, (size_t)nq)) return rc;
-    if (int rc = dev_alloc(&D.exceed, (size_t)nq)) return rc;
-    if (nperm > 0) {
-        if (int rc = dev_alloc(&D.null_es, (size_t)chunk * nq)) return rc;
-        if (int rc = dev_alloc(&D.inv, (size_t)chunk * N)) return rc;
-        if (H.any_na) { if (int rc = dev_alloc(&D.perms, (size_t)chunk * N)) return rc; }
-    }
-    if (H.any_na) {
-        if (int rc = dev_alloc(&D.words, (size_t)grid_max * nW)) return rc;
-        if (int rc = dev_alloc(&D.prefix, (size_t)grid_max * nW)) return rc;
-    }
-    HIPCHECK(hipMemcpy(D.valid, valid, (size_t)r * N, hipMemcpyHostToDevice));
-    HIPCHECK(hipMemcpy(D.wp, wp, (size_t)r * N * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHECK(hipMemcpy(D.has_na, H.has_na.data(), (size_t)r, hipMemcpyHostToDevice));
-    HIPCHECK(hipMemcpy(D.hit_ptr, hit_ptr, ((size_t)nks + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
-    if (nhits) {
-        HIPCHECK(hipMemcpy(D.hit_row, hit_row, nhits * sizeof(int32_t), hipMemcpyHostToDevice));
-        HIPCHECK(hipMemcpy(D.hit_is_miss, hit_is_miss, nhits, hipMemcpyHostToDevice));
-    }
-    HIPCHECK(hipMemcpy(D.M, H.M.data(), (size_t)nks * sizeof(int32_t), hipMemcpyHostToDevice));
-    HIPCHECK(hipMemset(D.exceed, 0, (size_t)nq * sizeof(long long)));
-    HIPCHECK(hipEventCreate(&D.ev0));
-    HIPCHECK(hipEventCreate(&D.ev1));
-    tl_gsea_times_ms[0] += ms_since(t0);
-
-    GseaArgs a;
-    a.N = N; a.r = r; a.nS = nS; a.pad = H.pad; a.valid = D.valid; a.has_na = D.has_na; a.wp = D.wp; a.hit_ptr = D.hit_ptr;
-    a.hit_row = D.hit_row; a.hit_is_miss = D.hit_is_miss; a.M = D.M; a.words = D.words; a.prefix = D.prefix;
-    const size_t lds = (size_t)kGseaLdsFixed + (size_t)kGseaLdsPerHit * (size_t)H.pad;
-    float kms = 0.0f;
-
-    // the observed scores: the identity permutation (R/gsea.R:57)
-    a.nb = 1; a.inv = nullptr; a.perms = nullptr; a.out = D.es;
-    HIPCHECK(hipEventRecord(D.ev0, nullptr));
-    D.queued = true;
-    hipLaunchKernelGGL(k_gsea_perm, dim3((unsigned)std::min<int64_t>(r, grid_max)), dim3(kGseaThreads), lds, nullptr, a);
-    HIPCHECK(hipGetLastError());
-    HIPCHECK(hipEventRecord(D.ev1, nullptr));
-    HIPCHECK(hipEventSynchronize(D.ev1));
-    HIPCHECK(hipEventElapsedTime(&kms, D.ev0, D.ev1));
-    tl_gsea_times_ms[1] += kms;
-
-    for (int64_t b0 = 0; b0 < nperm; b0 += chunk) {                                 // R/gsea.R:65-72
-        const int64_t nb = std::min(chunk, nperm - b0);
-        t0 = clock::now();
-        HIPCHECK(hipMemcpy(D.inv, H.inv.get() + b0 * N, (size_t)nb * N * sizeof(int32_t), hipMemcpyHostToDevice));
-        if (H.any_na) HIPCHECK(hipMemcpy(D.perms, perms + b0 * N, (size_t)nb * N * sizeof(int32_t), hipMemcpyHostToDevice));
-        tl_gsea_times_ms[0] += ms_since(t0);
-        a.nb = (int32_t)nb; a.inv = D.inv; a.perms = H.any_na ? D.perms : nullptr; a.out = D.null_es;
-        HIPCHECK(hipEventRecord(D.ev0, nullptr));
-        hipLaunchKernelGGL(k_gsea_perm, dim3((unsigned)std::min<int64_t>(nb * r, grid_max)), dim3(kGseaThreads), lds, nullptr, a);
-        HIPCHECK(hipGetLastError());
-        hipLaunchKernelGGL(k_gsea_count, dim3((unsigned)((nq + kGseaThreads - 1) / kGseaThreads)), dim3(kGseaThreads), 0, nullptr,
-                           D.es, D.null_es, (int32_t)nb, nq, D.exceed);
-        HIPCHECK(hipGetLastError());
-        HIPCHECK(hipEventRecord(D.ev1, nullptr));
-        HIPCHECK(hipEventSynchronize(D.ev1));
-        HIPCHECK(hipEventElapsedTime(&kms, D.ev0, D.ev1));
-        tl_gsea_times_ms[1] += kms;
-        if (null_es) {
-            t0 = clock::now();
-            HIPCHECK(hipMemcpy(null_es + b0 * nq, D.null_es, (size_t)nb * nq * sizeof(double), hipMemcpyDeviceToHost));
-            tl_gsea_times_ms[2] += ms_since(t0);
-        }
-    }
-    t0 = clock::now();
-    HIPCHECK(hipMemcpy(es, D.es, (size_t)nq * sizeof(double), hipMemcpyDeviceToHost));
-    HIPCHECK(hipMemcpy(exceed, D.exceed, (size_t)nq * sizeof(int64_t), hipMemcpyDeviceToHost));
-    D.queued = false;
-    for (int64_t q = 0; q < nq; q++)
-        if (es[q] != es[q]) exceed[q] = -1;
-    tl_gsea_times_ms[2] += ms_since(t0);
-    return VBNMF_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int vbnmf_gsea_perm(int32_t device, int64_t N, int32_t r, int32_t nS, const uint8_t *valid, const double *wp, const int64_t *hit_ptr,
-                    const int32_t *hit_row, const uint8_t *hit_is_miss, int64_t nperm, const int32_t *perms, double *es,
-                    int64_t *exceed, double *null_es)
-{
-    using clock = std::chrono::steady_clock;
-    for (double &v : tl_gsea_times_ms) v = 0.0;
-    if (N < 1 || N > 2147483584ll) return fail(VBNMF_ERR_BAD_ARG, "N = %lld rows is outside [1, 2^31 - 64]", (long long)N);
-    if (r < 1 || r > VBNMF_MAX_RANK) return fail(VBNMF_ERR_BAD_ARG, "rank %d is outside [1, %d]", r, VBNMF_MAX_RANK);
-    if (nS < 0 || nperm < 0) return fail(VBNMF_ERR_BAD_ARG, "negative number of sets or permutations");
-    if (!valid || !wp || !hit_ptr || (nS > 0 && (!es || !exceed)) || (nperm > 0 && !perms)) return fail(VBNMF_ERR_BAD_ARG, "NULL argument");
-    try {
-        const auto t0 = clock::now();
-        GseaHost H;
-        if (int rc = gsea_check(N, r, nS, valid, wp, hit_ptr, hit_row, hit_is_miss, nperm, perms, H)) return rc;
-        tl_gsea_times_ms[3] = std::chrono::duration<double, std::milli>(clock::now() - t0).count();
-        if (int rc = check_device(device)) return rc;
-        if (nS == 0) return VBNMF_OK;
-        return gsea_run(device, N, r, nS, valid, wp, hit_ptr, hit_row, hit_is_miss, nperm, perms, H, es, exceed, null_es);
-    } catch (const std::bad_alloc &) {
-        return fail(VBNMF_ERR_OOM, "out of host memory inverting %lld permutations of %lld rows", (long long)nperm, (long long)N);
-    } catch (const std::exception &ex) {
-        return fail(VBNMF_ERR_HIP, "vbnmf_gsea_perm: %s", ex.what());
-    }
-}
-
-int vbnmf_gsea_info(int64_t N, int32_t *wave_width, int32_t *workgroup_size, int32_t *max_set_hits, int64_t *chunk_perms, double *times_ms)
-{
-    if (wave_width) *wave_width = kGseaWave;
-    if (workgroup_size) *workgroup_size = kGseaThreads;
-    if (max_set_hits) *max_set_hits = kGseaMaxSetHits;
-    if (chunk_perms) *chunk_perms = gsea_chunk_perms(N);
-    if (times_ms)
-        for (int k = 0; k < 4; k++) times_ms[k] = tl_gsea_times_ms[k];
-    return VBNMF_OK;
-}
-
-}  // extern "C"
-
-// ---- the t-SNE map behind visualize_clusters (tsne.h): arguments are checked and x is normalised on the host, the affinities
-// are one launch at creation, an iteration of the descent is a force launch and an update launch on the handle's stream.
-struct vbnmf_tsne {
-    int device = 0;
-    int32_t n = 0, d = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;
-    double *xt = nullptr, *beta = nullptr, *sum_p = nullptr, *inv_s = nullptr;
-    int32_t *trips = nullptr;
-    double *state = nullptr;       // [6][n]: y0 y1 u0 u1 g0 g1
-    double *sums = nullptr;        // [kTsneForceSums][n]
-    double *cost_i = nullptr;      // [n]
-    double *costs = nullptr;       // [costs_cap] the run's cost values
-    int64_t costs_cap = 0;
-    int aff_grid = 0, force_grid = 0;
-    bool has_state = false;
-    double times_ms[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-};
-
-namespace {
-
-thread_local double tl_tsne_create_ms[3] = {0.0, 0.0, 0.0};
-
-int tsne_use(vbnmf_tsne *t)
-{
-    if (!t) return fail(VBNMF_ERR_BAD_ARG, "NULL t-SNE handle");
-    HIPCHECK(hipSetDevice(t->device));
-    return VBNMF_OK;
-}
-
-int tsne_launch_force(vbnmf_tsne *t, int cost)
-{
-    const int64_t n = t->n;
-    TsneForceArgs a;
-    a.n = t->n; a.d = t->d; a.cost = cost; a.xt = t->xt; a.beta = t->beta; a.inv_s = t->inv_s;
-    a.y0 = t->state; a.y1 = t->state + n; a.inv_2n = 1.0 / (2.0 * (double)n); a.sums = t->sums;
-    const dim3 grid((unsigned)t->force_grid), block(kTsneThreads);
-    const size_t lds = tsne_force_lds(t->d);
-    const int DR = tsne_force_width(t->d);
-    if (DR == 8) hipLaunchKernelGGL(k_tsne_force<8>, grid, block, lds, t->stream, a);
-    else if (DR == 16) hipLaunchKernelGGL(k_tsne_force<16>, grid, block, lds, t->stream, a);
-    else if (DR == 32) hipLaunchKernelGGL(k_tsne_force<32>, grid, block, lds, t->stream, a);
-    else hipLaunchKernelGGL(k_tsne_force<0>, grid, block, lds, t->stream, a);
-    HIPCHECK(hipGetLastError());
-    return VBNMF_OK;
-}
-
-int tsne_launch_update(vbnmf_tsne *t, int do_step, int do_cost, double e, double m, double eta, double min_gain, double *cost_out)
-{
-    const int64_t n = t->n;
-    TsneUpdArgs a;
-    a.n = t->n; a.do_step = do_step; a.do_cost = do_cost; a.e = e; a.m = m; a.eta = eta; a.min_gain = min_gain; a.sums = t->sums;
-    a.y0 = t->state; a.y1 = t->state + n; a.u0 = t->state + 2 * n; a.u1 = t->state + 3 * n; a.g0 = t->state + 4 * n; a.g1 = t->state + 5 * n;
-    a.cost_i = t->cost_i; a.cost_out = cost_out;
-    hipLaunchKernelGGL(k_tsne_update, dim3(1), dim3(kTsneUpdThreads), 0, t->stream, a);
-    HIPCHECK(hipGetLastError());
-    return VBNMF_OK;
-}
-
-int tsne_costs_reserve(vbnmf_tsne *t, int64_t count)
-{
-    if (count <= t->costs_cap) return VBNMF_OK;
-    HIPCHECK(hipStreamSynchronize(t->stream));
-    dev_free(t->costs);
-    t->costs = nullptr; t->costs_cap = 0;
-    if (int rc = dev_alloc(&t->costs, (size_t)count)) return rc;
-    t->costs_cap = count;
-    return VBNMF_OK;
-}
-
-// n x 2 row-major <-> two columns
-void tsne_split(const double *a, int64_t n, double *c0, double *c1)
-{
-    for (int64_t i = 0; i < n; i++) { c0[i] = a[2 * i]; c1[i] = a[2 * i + 1]; }
-}
-void tsne_join(const double *c0, const double *c1, int64_t n, double *a)
-{
-    for (int64_t i = 0; i < n; i++) { a[2 * i] = c0[i]; a[2 * i + 1] = c1[i]; }
-}
-
-int tsne_create(vbnmf_tsne *t, int32_t device, const std::vector<double> &xt, double perplexity)
-{
-    using clock = std::chrono::steady_clock;
-    const int64_t n = t->n;
-    const int d = t->d;
-    t->device = device;
-    HIPCHECK(hipSetDevice(device));
-    int cus = 0;
-    HIPCHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
-    if (cus <= 0) cus = 256;
-    const auto t0 = clock::now();
-    HIPCHECK(hipStreamCreate(&t->stream));
-    HIPCHECK(hipEventCreate(&t->ev0));
-    HIPCHECK(hipEventCreate(&t->ev1));
-    HIPCHECK(hipEventCreate(&t->ev2));
-    HIPCHECK(hipEventCreate(&t->ev3));
-    int rc;
-    if ((rc = dev_alloc(&t->xt, (size_t)n * d)) || (rc = dev_alloc(&t->beta, (size_t)n)) || (rc = dev_alloc(&t->sum_p, (size_t)n)) ||
-        (rc = dev_alloc(&t->inv_s, (size_t)n)) || (rc = dev_alloc(&t->trips, (size_t)n)) || (rc = dev_alloc(&t->state, 6 * (size_t)n)) ||
-        (rc = dev_alloc(&t->sums, (size_t)kTsneForceSums * n)) || (rc = dev_alloc(&t->cost_i, (size_t)n)))
-        return rc;
-    t->aff_grid = (int)std::min<int64_t>(n, (int64_t)cus * 4);
-    t->force_grid = (int)((n + kTsneIBlock - 1) / kTsneIBlock);
-    double *scratch = nullptr;
-    if (n > kTsneLdsRow) { if ((rc = dev_alloc(&scratch, (size_t)t->aff_grid * (size_t)n))) return rc; }
-    hipError_t err = hipMemcpy(t->xt, xt.data(), (size_t)n * d * sizeof(double), hipMemcpyHostToDevice);
-    tl_tsne_create_ms[1] = std::chrono::duration<double, std::milli>(clock::now() - t0).count();
-    if (err == hipSuccess) {
-        TsneAffArgs a;
-        a.n = t->n; a.d = d; a.xt = t->xt; a.scratch = scratch; a.log_u = std::log(perplexity);
-        a.beta = t->beta; a.sum_p = t->sum_p; a.inv_s = t->inv_s; a.trips = t->trips;
-        err = hipEventRecord(t->ev0, t->stream);
-        hipLaunchKernelGGL(k_tsne_affinity, dim3((unsigned)t->aff_grid), dim3(kTsneThreads), 0, t->stream, a);
-        if (err == hipSuccess) err = hipGetLastError();
-        if (err == hipSuccess) err = hipEventRecord(t->ev1, t->stream);
-    }
-    const hipError_t serr = hipStreamSynchronize(t->stream);                  // scratch is free after this whatever happened
-    dev_free(scratch);
-    if (err == hipSuccess) err = serr;
-    if (err != hipSuccess) return fail(VBNMF_ERR_HIP, "vbnmf_tsne_create: %s", hipGetErrorString(err));
-    float ms = 0.0f;
-    HIPCHECK(hipEventElapsedTime(&ms, t->ev0, t->ev1));
-    tl_tsne_create_ms[2] = ms;
-    for (int k = 0; k < 3; k++) t->times_ms[k] = tl_tsne_create_ms[k];
-    return VBNMF_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int vbnmf_tsne_create(int32_t device, int64_t n, int32_t d, const double *x, double perplexity, int32_t normalize, vbnmf_tsne **handle)
-{
-    using clock = std::chrono::steady_clock;
-    for (double &v : tl_tsne_create_ms) v = 0.0;
-    if (!handle) return fail(VBNMF_ERR_BAD_ARG, "NULL argument");
-    *handle = nullptr;
-    if (!x) return fail(VBNMF_ERR_BAD_ARG, "NULL argument");
-    if (n < 1 || n > 2147481600ll) return fail(VBNMF_ERR_BAD_ARG, "n = %lld points is outside [1, 2^31 - 2048]", (long long)n);   // (int loop counters step by <= 1024)
-    if (d < 1 || d > VBNMF_MAX_RANK) return fail(VBNMF_ERR_BAD_ARG, "d = %d is outside [1, %d]", d, VBNMF_MAX_RANK);
-    if (!std::isfinite(perplexity) || perplexity < 1.0) return fail(VBNMF_ERR_BAD_ARG, "the perplexity must be finite and >= 1");
-    if (!(3.0 * perplexity < (double)(n - 1)))
-        return fail(VBNMF_ERR_BAD_ARG, "the perplexity %g is too large for %lld points: 3 perplexity < n - 1 is required", perplexity, (long long)n);
-    try {
-        const auto t0 = clock::now();
-        for (int64_t q = 0; q < n * d; q++)
-            if (!std::isfinite(x[q])) return fail(VBNMF_ERR_BAD_ARG, "x[%lld, %lld] is not finite", (long long)(q / d), (long long)(q % d));
-        // the device's copy is xt[d][n]; the normalisation runs on it in a fixed order: column means, then the largest |value|
-        std::vector<double> xt((size_t)n * d);
-        for (int64_t i = 0; i < n; i++)
-            for (int k = 0; k < d; k++) xt[(size_t)k * n + i] = x[i * d + k];
-        if (normalize) {
-            double mx = 0.0;
-            for (int k = 0; k < d; k++) {
-                double *c = xt.data() + (size_t)k * n;
-                double s = 0.0;
-                for (int64_t i = 0; i < n; i++) s += c[i];
-                const double mean = s / (double)n;
-                for (int64_t i = 0; i < n; i++) { c[i] -= mean; mx = std::max(mx, std::fabs(c[i])); }
-            }
-            if (mx > 0.0)
-                for (double &v : xt) v /= mx;
-        }
-        tl_tsne_create_ms[0] = std::chrono::duration<double, std::milli>(clock::now() - t0).count();
-        if (int rc = check_device(device)) return rc;
-        std::unique_ptr<vbnmf_tsne, void (*)(vbnmf_tsne *)> t(new vbnmf_tsne(), vbnmf_tsne_destroy);
-        t->n = (int32_t)n; t->d = d;
-        if (int rc = tsne_create(t.get(), device, xt, perplexity)) return rc;
-        *handle = t.release();
-        return VBNMF_OK;
-    } catch (const std::bad_alloc &) {
-        return fail(VBNMF_ERR_OOM, "out of host memory for %lld x %d points", (long long)n, d);
-    }
-}
-
-void vbnmf_tsne_destroy(vbnmf_tsne *t)
-{
-    if (!t) return;
-    int cur = -1;
-    (void)hipGetDevice(&cur);
-    (void)hipSetDevice(t->device);
-    if (t->stream) (void)hipStreamSynchronize(t->stream);
-    dev_free(t->xt); dev_free(t->beta); dev_free(t->sum_p); dev_free(t->inv_s); dev_free(t->trips); dev_free(t->state);
-    dev_free(t->sums); dev_free(t->cost_i); dev_free(t->costs);
-    if (t->ev0) (void)hipEventDestroy(t->ev0);
-    if (t->ev1) (void)hipEventDestroy(t->ev1);
-    if (t->ev2) (void)hipEventDestroy(t->ev2);
-    if (t->ev3) (void)hipEventDestroy(t->ev3);
-    if (t->stream) (void)hipStreamDestroy(t->stream);
-    if (cur >= 0) (void)hipSetDevice(cur);
-    delete t;
-}
-
-int vbnmf_tsne_affinity(vbnmf_tsne *t, double *beta, double *sum_p, int32_t *trips)
-{
-    if (int rc = tsne_use(t)) return rc;
-    const size_t n = (size_t)t->n;
-    if (beta) HIPCHECK(hipMemcpy(beta, t->beta, n * sizeof(double), hipMemcpyDeviceToHost));
-    if (sum_p) HIPCHECK(hipMemcpy(sum_p, t->sum_p, n * sizeof(double), hipMemcpyDeviceToHost));
-    if (trips) HIPCHECK(hipMemcpy(trips, t->trips, n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return VBNMF_OK;
-}
-
-int vbnmf_tsne_set_state(vbnmf_tsne *t, const double *Y, const double *uY, const double *gains)
-{
-    if (!t || !Y) return fail(VBNMF_ERR_BAD_ARG, "NULL argument");
-    const int64_t n = t->n;
-    for (int64_t q = 0; q < 2 * n; q++)
-        if (!std::isfinite(Y[q]) || (uY && !std::isfinite(uY[q])) || (gains && !std::isfinite(gains[q])))
-            return fail(VBNMF_ERR_BAD_ARG, "the state is not finite at point %lld", (long long)(q / 2));
-    try {
-        std::vector<double> s(6 * (size_t)n, 0.0);
-        tsne_split(Y, n, s.data(), s.data() + n);
-        if (uY) tsne_split(uY, n, s.data() + 2 * n, s.data() + 3 * n);
-        if (gains) tsne_split(gains, n, s.data() + 4 * n, s.data() + 5 * n);
-        else std::fill(s.begin() + 4 * n, s.end(), 1.0);
-        if (int rc = tsne_use(t)) return rc;
-        HIPCHECK(hipStreamSynchronize(t->stream));
-        HIPCHECK(hipMemcpy(t->state, s.data(), s.size() * sizeof(double), hipMemcpyHostToDevice));
-    } catch (const std::bad_alloc &) {
-        return fail(VBNMF_ERR_OOM, "out of host memory");
-    }
-    t->has_state = true;
-    return VBNMF_OK;
-}
-
-int vbnmf_tsne_get_state(vbnmf_tsne *t, double *Y, double *uY, double *gains)
-{
-    if (int rc = tsne_use(t)) return rc;
-    if (!t->has_state) return fail(VBNMF_ERR_STATE, "the handle has no state yet: call vbnmf_tsne_set_state");
-    const int64_t n = t->n;
-    try {
-        std::vector<double> s(6 * (size_t)n);
-        HIPCHECK(hipStreamSynchronize(t->stream));
-        HIPCHECK(hipMemcpy(s.data(), t->state, s.size() * sizeof(double), hipMemcpyDeviceToHost));
-        if (Y) tsne_join(s.data(), s.data() + n, n, Y);
-        if (uY) tsne_join(s.data() + 2 * n, s.data() + 3 * n, n, uY);
-        if (gains) tsne_join(s.data() + 4 * n, s.data() + 5 * n, n, gains);
-    } catch (const std::bad_alloc &) {
-        return fail(VBNMF_ERR_OOM, "out of host memory");
-    }
-    return VBNMF_OK;
-}
-
-int vbnmf_tsne_forces(vbnmf_tsne *t, double exaggeration, double *A, double *R, double *z, double *cost_i)
-{
-    if (!t) return fail(VBNMF_ERR_BAD_ARG, "NULL t-SNE handle");
-    if (!std::isfinite(exaggeration)) return fail(VBNMF_ERR_BAD_ARG, "the exaggeration is not finite");
-    if (int rc = tsne_use(t)) return rc;
-    if (!t->has_state) return fail(VBNMF_ERR_STATE, "the handle has no state yet: call vbnmf_tsne_set_state");
-    const int64_t n = t->n;
-    if (int rc = tsne_costs_reserve(t, 1)) return rc;
-    if (int rc = tsne_launch_force(t, 1)) return rc;
-    if (int rc = tsne_launch_update(t, 0, 1, 1.0, 0.0, 0.0, 0.0, t->costs)) return rc;
-    HIPCHECK(hipStreamSynchronize(t->stream));
-    try {
-        std::vector<double> s(5 * (size_t)n);
-        HIPCHECK(hipMemcpy(s.data(), t->sums, s.size() * sizeof(double), hipMemcpyDeviceToHost));
-        if (A) {
-            tsne_join(s.data(), s.data() + n, n, A);
-            for (int64_t q = 0; q < 2 * n; q++) A[q] = exaggeration * A[q];
-        }
-        if (R) tsne_join(s.data() + 2 * n, s.data() + 3 * n, n, R);
-        if (z) std::copy(s.begin() + 4 * n, s.end(), z);
-        if (cost_i) HIPCHECK(hipMemcpy(cost_i, t->cost_i, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
-    } catch (const std::bad_alloc &) {
-        return fail(VBNMF_ERR_OOM, "out of host memory");
-    }
-    return VBNMF_OK;
-}
-
-int vbnmf_tsne_run(vbnmf_tsne *t, int32_t first_iter, int32_t n_iter, double exaggeration, int32_t stop_lying_iter,
-                   int32_t mom_switch_iter, double momentum, double final_momentum, double eta, double min_gain, int32_t cost_every,
-                   double *itercosts, int32_t *cost_iters, int32_t *n_costs)
-{
-    using clock = std::chrono::steady_clock;
-    if (!t || !itercosts || !cost_iters || !n_costs) return fail(VBNMF_ERR_BAD_ARG, "NULL argument");
-    *n_costs = 0;
-    if (first_iter < 1 || n_iter < 0 || (int64_t)first_iter + n_iter > 2147483647ll)
-        return fail(VBNMF_ERR_BAD_ARG, "iterations %d .. %d + %d are outside [1, 2^31)", first_iter, first_iter, n_iter);
-    if (!std::isfinite(exaggeration) || !std::isfinite(momentum) || !std::isfinite(final_momentum) || !std::isfinite(eta) || !std::isfinite(min_gain))
-        return fail(VBNMF_ERR_BAD_ARG, "a schedule value is not finite");
-    if (int rc = tsne_use(t)) return rc;
-    if (!t->has_state) return fail(VBNMF_ERR_STATE, "the handle has no state yet: call vbnmf_tsne_set_state");
-    if (n_iter == 0) return VBNMF_OK;
-    const int32_t last = first_iter + n_iter - 1;
-    auto due = [&](int32_t it) { return it == last || (cost_every > 0 && it % cost_every == 0); };
-    int32_t count = 0;
-    for (int32_t it = first_iter; it <= last; it++) count += due(it) ? 1 : 0;
-    if (int rc = tsne_costs_reserve(t, count)) return rc;
-    HIPCHECK(hipEventRecord(t->ev0, t->stream));
-    int32_t slot = 0;
-    for (int32_t it = first_iter; it <= last; it++) {
-        // the cost of the Y that iteration it - 1 left is formed by this iteration's force launch
-        const int cost = it > first_iter && due(it - 1) ? 1 : 0;
-        const double e = it <= stop_lying_iter ? exaggeration : 1.0, m = it <= mom_switch_iter ? momentum : final_momentum;
-        if (it == last) HIPCHECK(hipEventRecord(t->ev2, t->stream));            // the last iteration's two launches, each by itself
-        if (int rc = tsne_launch_force(t, cost)) return rc;
-        if (it == last) HIPCHECK(hipEventRecord(t->ev3, t->stream));
-        if (int rc = tsne_launch_update(t, 1, cost, e, m, eta, min_gain, t->costs + slot)) return rc;
-        if (it == last) HIPCHECK(hipEventRecord(t->ev1, t->stream));
-        if (cost) cost_iters[slot++] = it - 1;
-    }
-    if (int rc = tsne_launch_force(t, 1)) return rc;
-    if (int rc = tsne_launch_update(t, 0, 1, 1.0, 0.0, 0.0, 0.0, t->costs + slot)) return rc;
-    cost_iters[slot++] = last;
-    HIPCHECK(hipStreamSynchronize(t->stream));
-    float ms = 0.0f;
-    HIPCHECK(hipEventElapsedTime(&ms, t->ev0, t->ev1));                         // the iterations, without the closing cost evaluation
-    t->times_ms[3] = ms;
-    HIPCHECK(hipEventElapsedTime(&ms, t->ev2, t->ev3));
-    t->times_ms[5] = ms;
-    HIPCHECK(hipEventElapsedTime(&ms, t->ev3, t->ev1));
-    t->times_ms[6] = ms;
-    const auto t0 = clock::now();
-    HIPCHECK(hipMemcpy(itercosts, t->costs, (size_t)slot * sizeof(double), hipMemcpyDeviceToHost));
-    t->times_ms[4] = std::chrono::duration<double, std::milli>(clock::now() - t0).count();
-    *n_costs = slot;
-    return VBNMF_OK;
-}
-
-int vbnmf_tsne_info(vbnmf_tsne *t, int32_t *ints, double *times_ms)
-{
-    if (ints) {
-        const int32_t v[8] = {kTsneWave, kTsneThreads, kTsneIBlock, kTsneJTile, kTsneLdsRow, t ? t->aff_grid : 0, t ? t->force_grid : 0, kTsneUpdThreads};
-        for (int k = 0; k < 8; k++) ints[k] = v[k];
-    }
-    if (times_ms)
-        for (int k = 0; k < 7; k++) times_ms[k] = t ? t->times_ms[k] : (k < 3 ? tl_tsne_create_ms[k] : 0.0);
-    return VBNMF_OK;
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 // gsea.h -- gfx950 kernels behind assign_celltype: the enrichment score of every (permutation, cluster, gene set) of the
-// reference's p-value loop in one launch per chunk of permutations (included once, by engine.hip).
+// reference's p-value loop in one launch per chunk of permutations (included once, by gsea.hip).
 //
 // Reference: gsea() (R/gsea.R:79-115) as assignCelltype() calls it nperm + 1 times (:57, :65-72), for one cluster k, one set s:
 //   :92-94   the rows of the (permuted) meta table whose weight is not NA, in table order                 -> valid, rank
@@ -37,7 +37,7 @@
 // (b, k, s) with T = 0 or M = 0: NaN written, nothing computed.
 //
 // No floating-point atomics and no order that depends on the grid: the same inputs give the same bits on every call.  Every
-// loop is bounded by N, T, P or the item count; every index is checked by the host (engine.hip, gsea_check) before the launch.
+// loop is bounded by N, T, P or the item count; every index is checked by the host (gsea.hip, gsea_check) before the launch.
 #pragma once
 #include <hip/hip_runtime.h>
 

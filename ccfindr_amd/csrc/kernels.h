@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "hyper.h"                // wave_sum, block_sum, dev_hyper_update_pair (shared with vbproject.h)
 #include "special.h"
 
 namespace vbnmf {
@@ -309,36 +310,7 @@ __device__ __forceinline__ void renorm_product(SweepRegs<R> &S)
 // with which column depends on the lane number alone, and the tree is fixed: a slice's sums depend on nothing but its
 // tasks -- bit-reproducible.
 // XOR4: level 4 must pair lane ^ 4 (ranks above 32: the mirror pairing joins lanes that hold different columns of a task)
-template <int MASK, bool XOR4 = false>
-__device__ __forceinline__ double lane_pair_value(double v)
-{
-    static_assert(MASK == 8 || MASK == 4 || MASK == 2 || MASK == 1, "DPP levels");
-    if constexpr (MASK == 4 && XOR4) return __shfl_xor(v, 4, 64);
-    constexpr int ctrl = MASK == 8 ? 0x128 : MASK == 4 ? 0x141 : MASK == 2 ? 0x4E : 0xB1;
-    return __hiloint2double(__builtin_amdgcn_mov_dpp(__double2hiint(v), ctrl, 0xF, 0xF, false),
-                            __builtin_amdgcn_mov_dpp(__double2loint(v), ctrl, 0xF, 0xF, false));
-}
-// wave sum without LDS round trips: DPP inside the rows of 16 lanes (quads, half rows, rows), then gfx950's permlane swaps
-// across the rows.  Valid in every lane; a fixed tree.
-__device__ __forceinline__ double wave_sum_dpp(double v)
-{
-    v += lane_pair_value<1>(v);
-    v += lane_pair_value<2>(v);
-    v += lane_pair_value<4>(v);
-    v += lane_pair_value<8>(v);
-    {   // rows 0+1, 2+3: v_permlane16_swap of the value with a copy of itself leaves (own row, partner row) in the two registers
-        const int lo = __double2loint(v), hi = __double2hiint(v);
-        const auto r0 = __builtin_amdgcn_permlane16_swap(lo, lo, false, false), r1 = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-        v = __hiloint2double(r1[0], r0[0]) + __hiloint2double(r1[1], r0[1]);
-    }
-    {   // the two halves of the wave
-        const int lo = __double2loint(v), hi = __double2hiint(v);
-        const auto r0 = __builtin_amdgcn_permlane32_swap(lo, lo, false, false), r1 = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-        v = __hiloint2double(r1[0], r0[0]) + __hiloint2double(r1[1], r0[1]);
-    }
-    return v;
-}
-
+// (lane_pair_value, the partner's value at a DPP level, and wave_sum_dpp: hyper.h)
 // lower lanes of the level: lo + partner's lo ; upper lanes: hi + partner's hi
 template <int MASK, bool XOR4 = false>
 __device__ __forceinline__ double lane_pair_split(double lo, double hi, bool up)
@@ -837,8 +809,6 @@ constexpr int kUpdateThreads = 1024;
 constexpr int kStageIds = 14336;       // task ids of a block's majors staged in LDS by k_update (56 KB) ...
 constexpr int kStagePtr = 2048;        // ... and their pointer stretch (8 KB); a block with more falls back to global reads
 
-__device__ __forceinline__ double wave_sum(double v) { return wave_sum_dpp(v); }     // (valid in every lane; no LDS round trips)
-
 // Column sums of a block-partials table bp[nb][ncol] (nb <= 256) into out[0..ncol) (LDS or
 // global): wave w takes columns w, w+nwaves, ...; lane l adds rows l, l+64, ... in order.
 __device__ __forceinline__ void bp_colsums(const double *__restrict__ bp, int nb, int ncol, double *out, int nthreads)
@@ -908,11 +878,6 @@ struct LoopCtl {
     int32_t criterion;             // 1: stop on the labels, not on the likelihood
     int32_t zstep, ncnn_step;      // steps in a row without a changed pair / how many of them end the run
 };
-
-template <bool TRACE = false>
-__device__ inline int dev_hyper_update_pair(const int32_t *flags, const double *stats, double *hyper, int lane,
-                                            double *trace = nullptr, int32_t *iters = nullptr);
-__device__ __forceinline__ double block_sum(double s, double *sm);
 
 // Device-driven loop of an unpartitioned engine: the control step (k_control below: the evidence of the step just swept,
 // hyper_update, the stopping rule, the history row) FOLDED into the gene-side update of the NEXT step -- one launch
@@ -1537,30 +1502,6 @@ __global__ __launch_bounds__(256) void k_group_sum_at(const double *const *__res
     for (int p = 0; p < parts; p++) recv[p][off + i] = s;
 }
 
-// Sum of v[0..count) by one 1024-thread block, fixed order: thread t adds t, t+1024, ...; a shuffle tree per wave; the
-// 16 wave sums through LDS and one more shuffle tree.  Two barriers (the ten-round LDS tree it replaces cost k_control
-// and k_final about a microsecond each).
-__device__ __forceinline__ double block_sum(double s, double *sm);
-__device__ __forceinline__ double block_vec_sum(const double *__restrict__ v, int64_t count, double *sm)
-{
-    double s = 0.0;
-    for (int64_t q = threadIdx.x; q < count; q += 1024) s += v[q];
-    return block_sum(s, sm);
-}
-// the block's total of one value per thread (1024 threads), same order as above
-__device__ __forceinline__ double block_sum(double s, double *sm)
-{
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    s = wave_sum(s);
-    if (lane == 0) sm[wave] = s;
-    __syncthreads();
-    double r = lane < 16 ? sm[lane] : 0.0;
-    r = wave_sum(r);                                  // every wave forms the same total in its lane 0 ...
-    r = __shfl(r, 0, 64);                             // ... and hands it to all its lanes
-    __syncthreads();                                  // sm may be reused by the caller
-    return r;
-}
-
 // tail = [rowSum(eh)_k (R) | sum H-terms | sum log lh | data term | sum lgamma(x+1)] of THIS partition.
 __global__ __launch_bounds__(1024) void k_tail(const double *__restrict__ bpH, int nbH, int R,
                                                const double *__restrict__ epart, int64_t nepart, double lgx,
@@ -1624,55 +1565,9 @@ __global__ __launch_bounds__(1024) void k_final(const double *__restrict__ bpW, 
 }
 
 // ------------------------------------------------------------------------------------
-// Device-resident driver loop: hyper_update (reference R/bayesian.R:2-53) and the loop control of
-// vb_iterate (R/bayesian.R:342-348) after each step, by one thread.
+// Device-resident driver loop: hyper_update (reference R/bayesian.R:2-53; hyper.h: dev_hyper_update_pair) and the loop
+// control of vb_iterate (R/bayesian.R:342-348) after each step, by one thread.
 // ------------------------------------------------------------------------------------
-// (digamma, trigamma and one side's share of a Newton iteration: special.h, dev_digamma1 / dev_trigamma / hyper_newton_side.)
-// hyper_update (R/bayesian.R:2-53) by lanes 0 and 1 of a wave side by side: lane 0 iterates aw, lane 1 ah -- the two
-// Newton recurrences (:19-27) only meet in the convergence test (:37), which the lanes form by exchanging their
-// terms, so both run the same number of iterations as the sequential form and reach the same values.  A dependent fp64
-// chain (log, digamma, trigamma) costs microseconds on one lane; this halves it.
-// Returns 0, or 1 when the Newton iteration does not converge ("Hyper-parameter update failed to converge", :43);
-// lane 0 stores the four new hyper-parameters.
-// TRACE (the test hook k_test_hyper_update only; the loops instantiate TRACE = false, which compiles the stores away):
-// each lane stores its a1 of iteration k (0-based) to trace[100 * lane + k], lane 0 the number of iterations to *iters.
-template <bool TRACE>
-__device__ inline int dev_hyper_update_pair(const int32_t *flags, const double *stats, double *hyper, int lane, double *trace,
-                                            int32_t *iters)
-{
-    if (flags[0] + flags[1] + flags[2] + flags[3] == 0) return 0;                          // :4
-    double a0 = hyper[2 * lane];                           // aw (lane 0) or ah (lane 1)
-    const double b0 = hyper[2 * lane + 1];                 // bw or bh
-    const double lm = lane ? stats[1] : stats[0], em = lane ? stats[3] : stats[2];   // mean log l, mean e of this side (:8-11)
-    const int fa = flags[2 * lane];
-    double a1 = a0;
-    int failed = 0;
-    [[maybe_unused]] int done = 0;                         // iterations run (TRACE)
-    if (flags[0] + flags[2] > 0) {                                                         // :15
-        int i = 1;
-        while (i < 100) {                                                                  // Niter = 100 (:343)
-            // A non-finite step is reported as a failed hyper-parameter update (reason 3): see hyper_newton_side.
-            int hv, bad;
-            a1 = hyper_newton_side(a0, b0, lm, em, fa, &hv, &bad);                         // :18-35
-            if constexpr (TRACE) trace[100 * lane + done++] = a1;
-            const double u = bad ? 0.0 : 1.0 - a1 / a0;
-            const double uw = __shfl(u, 0, 64), uh = __shfl(u, 1, 64);
-            bad = __shfl(bad, 0, 64) | __shfl(bad, 1, 64);
-            if (bad) { failed = 1; break; }
-            if (uw * uw + uh * uh < 1e-3) break;                                           // Tol = 1e-3 (:344)
-            a0 = a1; i++;
-        }
-        if (i == 100) failed = 1;
-    }
-    if constexpr (TRACE) { if (lane == 0) *iters = done; }
-    const double aw1 = __shfl(a1, 0, 64), ah1 = __shfl(a1, 1, 64);
-    if (lane == 0 && !failed) {
-        hyper[0] = aw1; hyper[1] = flags[1] ? stats[2] : hyper[1];                         // :48-49
-        hyper[2] = ah1; hyper[3] = stats[3];                                               // :50-51 (both branches assign ehm)
-    }
-    return failed;
-}
-
 // One block after each sweep of a device-driven loop: the reductions of k_final, then
 //   it <- it+1 ; hyper_update if it > n0 and it %% dn == 0 (:342-344) ; break on NaN (:345) ;
 //   break if it > 1, it > n0, lkh >= lk0 and |1 - lkh/lk0| < Tol (:346-347, lk0 NOT refreshed) ; lk0 <- lkh (:348).

@@ -1,5 +1,5 @@
-// project.h -- gfx950 kernel that places new cells on a fitted basis: ML-NMF with W held fixed (included once, by engine.hip,
-// after mlnmf.h).
+// project.h -- gfx950 kernel that places new cells on a fitted basis: ML-NMF with W held fixed (included once, by
+// project.hip: its kernels are templates, but one unit launches them).
 //
 // Reference: the H half of nmf_updateR, R/factorize.R:8-15, iterated with w untouched, likelihood (:40-49) taken column by
 // column, and factorize()'s stopping test (:208) applied to every cell on its own:
@@ -27,7 +27,10 @@
 // inside the wave (offsets SP, 2 SP, .. 32), the four waves in order 0..3.  No floating-point atomics.  Every loop is
 // bounded by an entry count or by max_it: a NaN cannot hold one open.
 #pragma once
-#include "mlnmf.h"
+#include <hip/hip_runtime.h>
+
+#include "common.h"               // rank_shares
+#include "special.h"              // dev_log
 
 namespace vbnmf {
 

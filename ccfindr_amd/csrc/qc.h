@@ -1,5 +1,5 @@
 // qc.h -- gfx950 kernel behind filter_genes: per-gene statistics of the count matrix in one launch over the genes' rows
-// (included once, by engine.hip).
+// (included once, by qc.hip).
 //
 // Reference: what filter_genes() needs of every gene (R/utils.R:134-194):
 //   :139      ncexpr_i = number of stored entries of row i                                              -> nnz

@@ -1,4 +1,4 @@
-// tsne.h -- gfx950 kernels behind visualize_clusters: the exact (theta = 0) t-SNE map of the cells (included once, by engine.hip).
+// tsne.h -- gfx950 kernels behind visualize_clusters: the exact (theta = 0) t-SNE map of the cells (included once, by tsne.hip).
 //
 // Reference: visualize_clusters() (R/utils.R:692-712) hands t(h) to Rtsne (:700), a CPU package.  What is computed here is the
 // t-SNE authors' published algorithm in its exact O(n^2) form, stated in DESIGN.md 5k; Rtsne itself is not pinned.

@@ -1,5 +1,5 @@
 // vbproject.h -- gfx950 kernel that places new cells on a VB fit's posterior basis: the H half of the VB-NMF update with
-// q(W) held fixed (included once, by engine.hip, after project.h).
+// q(W) held fixed (included once, by project.hip: k_vbp_control is no template, so a second unit would define it again).
 //
 // Reference: the H half of vbnmf_updateR, R/bayesian.R:71-95, iterated with lw, ew untouched, the evidence taken column by
 // column (the cell's column of U1, :90-91, plus its column of U3, :94-95; U2 belongs to W), and vb_iterate's stopping test
@@ -33,7 +33,7 @@
 // over k of the evidence are added by every thread alike, k ascending.  A cell's bits depend on its own entries and on r
 // only.  No floating-point atomics.  Every loop is bounded by an entry count or by max_it.
 #pragma once
-#include "kernels.h"              // block_sum, dev_hyper_update_pair (the coupled form at the end of this file)
+#include "hyper.h"                // block_sum, dev_hyper_update_pair (the coupled form at the end of this file)
 #include "project.h"
 #include "special.h"
 

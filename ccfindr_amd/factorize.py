@@ -17,7 +17,7 @@ from .consensus import METHODS as TABLE_LINKAGES
 from .consensus import Consensus
 from .engine import CountMatrix, VBEngine, auto_batch
 
-BATCH_MAX_RANK = 16          # ranks the batch kernels are built for (csrc/engine.hip: kBatchMaxPaddedRank)
+BATCH_MAX_RANK = 16          # ranks the batch kernels are built for (csrc/rank.h: kBatchMaxPaddedRank)
 
 # Above this many cell pairs the O(m^2) connectivity vector (R/factorize.R:51-60) is not formed: dispersion
 # and cophenetic come from the label tables instead (consensus.py; ``factorize(consensus=...)``).

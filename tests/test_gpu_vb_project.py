@@ -239,7 +239,7 @@ def test_halves_and_permutation_bitwise():
 
 # ---- more cells than workgroups: the persistent grid goes round ----------------------------------------------------------
 def grid_workgroups():
-    """Workgroups of the kernel's persistent grid: as many as the CUs hold threads for (engine.hip: CUs x 2048 / 256)."""
+    """Workgroups of the kernel's persistent grid: as many as the CUs hold threads for (project.hip, project_grid: CUs x 2048 / 256)."""
     import torch
     return torch.cuda.get_device_properties(0).multi_processor_count * 8
 
