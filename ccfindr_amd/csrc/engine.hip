@@ -3513,6 +3513,9 @@ int vbnmf_test_special_host(int32_t kind, int64_t n, const double *x, double *y)
             case 2: dev_psi_lgamma(x[i], &psi, &lg); y[i] = lg; break;
             case 6: { static LogTabEntry tab[kLogTabSize]; static bool init = false; if (!init) { fill_log_table(tab); init = true; } y[i] = dev_log_tab(x[i], tab); break; }
             case 7: y[i] = dev_trigamma(x[i]); break;
+            case 8:                                          // the pair form: quads wa, wb, xa, xb in; qa, qb, r, 0 out
+                if (i % 4 == 0 && i + 3 < n) { y[i + 2] = dev_div_pair(x[i + 2], x[i], x[i + 3], x[i + 1], &y[i], &y[i + 1]); y[i + 3] = 0.0; }
+                break;
             default: y[i] = dev_div(1.0, x[i]); break;
         }
     }

@@ -294,6 +294,79 @@ __device__ __forceinline__ void renorm_product(SweepRegs<R> &S)
     S.pexp += k;
 }
 
+// Two stored entries on ONE reciprocal (special.h: dev_div_pair).  v_rcp_f64 costs about three fp64 issue slots
+// (profiles/r01_ubench.txt: 7.47 ns against 2.3-2.9 ns for an FMA), and r = 1 / (wa wb) serves both divisions:
+// qa = (xa wb) r, qb = (xb wa) r.  The head forms both dot products -- each with its two interleaved partial sums and its
+// share_sum, so wa and wb are bit for bit what sweep_entry forms -- the shared reciprocal, both quotients and the
+// logarithm terms; the rows are then accumulated one by one (sweep_row_acc), which is what lets the trip reload a row
+// buffer between the two.  MODE as in the trip: 1 = both entries are stored ones (x is not read: qa = wb r, qb = wa r, and
+// the product wa wb that the reciprocal needs anyway is what the running product takes -- one multiply per pair), 2 = ones
+// or twos (the running product takes wth or wth^2, entry by entry with a renormalisation after each: wa^2 wb^2 in one
+// factor would leave the fp64 range at wth ~ 2^+-480, inside the documented domain), 0 = general (both table logarithms,
+// in entry order).  Divisor domain: dev_div_pair's, the running product's own.
+template <int R, int SP, int MODE>
+__device__ __forceinline__ void sweep_pair_head(SweepRegs<R> &S, const double2 *__restrict__ ldsG, const double2 (&ga)[R / 2],
+                                                const double2 (&gb)[R / 2], double xa, double xb, bool logterm, double &qa, double &qb)
+{
+    double a0 = S.F[0] * ga[0].x, a1 = S.F[1] * ga[0].y;
+    double b0 = S.F[0] * gb[0].x, b1 = S.F[1] * gb[0].y;
+#pragma unroll
+    for (int kk = 1; kk < R / 2; kk++) {
+        a0 = fma(S.F[2 * kk], ga[kk].x, a0);
+        a1 = fma(S.F[2 * kk + 1], ga[kk].y, a1);
+    }
+#pragma unroll
+    for (int kk = 1; kk < R / 2; kk++) {
+        b0 = fma(S.F[2 * kk], gb[kk].x, b0);
+        b1 = fma(S.F[2 * kk + 1], gb[kk].y, b1);
+    }
+    const double wa = share_sum<SP>(a0 + a1), wb = share_sum<SP>(b0 + b1);
+    if (MODE == 1) {
+        dev_div_pair(1.0, wa, 1.0, wb, &qa, &qb);
+        if (logterm) { S.prod *= wa * wb; renorm_product<R>(S); }
+        return;
+    }
+    dev_div_pair(xa, wa, xb, wb, &qa, &qb);
+    if (!logterm) return;
+    if (MODE == 2) {
+        S.prod *= (xa == 2.0) ? wa * wa : wa; renorm_product<R>(S);
+        S.prod *= (xb == 2.0) ? wb * wb : wb; renorm_product<R>(S);
+        return;
+    }
+    S.lsum = fma(xa, dev_log_tab(wa, reinterpret_cast<const LogTabEntry *>(ldsG)), S.lsum);
+    S.lsum = fma(xb, dev_log_tab(wb, reinterpret_cast<const LogTabEntry *>(ldsG)), S.lsum);
+}
+template <int R>
+__device__ __forceinline__ void sweep_row_acc(SweepRegs<R> &S, const double2 (&gv)[R / 2], double q)
+{
+#pragma unroll
+    for (int kk = 0; kk < R / 2; kk++) {
+        S.acc[2 * kk] = fma(q, gv[kk].x, S.acc[2 * kk]);
+        S.acc[2 * kk + 1] = fma(q, gv[kk].y, S.acc[2 * kk + 1]);
+    }
+}
+
+// Which sweep instantiations pair their entries: padded lane rank R, NT threads, WIDE entries, SP lanes per task.  On where
+// the paired kernel keeps its parent's waves per SIMD without scratch (DESIGN section 5 lists every instantiation) and its
+// measured step is faster (section 7, "One reciprocal per pair").  One trait for k_sweep, k_sweep1, their batch forms and
+// the ML sweeps: engines that must agree bit for bit run the same instantiation of sweep_side, so they pair alike.  The
+// one-buffer loop (padded rank >= VBNMF_ONEBUF_FROM, packed entries) never holds two rows and stays per entry.
+#ifndef VBNMF_PAIR_RECIP
+#define VBNMF_PAIR_RECIP 1          // 0 builds every sweep per entry (A/B)
+#endif
+template <int R, int NT, bool WIDE, int SP>
+constexpr bool sweep_pairs()
+{
+    if (!VBNMF_PAIR_RECIP || VBNMF_PREFETCH2) return false;            // (the look-ahead experiment lives in the per-entry trip)
+    if ((R >= VBNMF_ONEBUF_FROM || R <= VBNMF_ONEBUF_UPTO) && !WIDE) return false;
+    if (NT == 768 && R >= 12) return false;                // 12, 14: already at the 168 VGPRs of three waves, the pair spills
+    if (SP > 1) return WIDE && R == 20;                    // shared ranks: the packed forms and R >= 24 spill at 256 VGPRs
+    if (WIDE) return R <= 24;                              // wide 26 and up spill
+    if (R == 16) return false;                             // measured, headline matrix at rank 16: 0.33382 -> 0.33311 ms per step in
+                                                           // one session, 0.33562 -> 0.33727 in the next: no gain (profiles/pair_recip_ab.txt)
+    return R != 4 && R <= 20;                              // packed 4: k_sweep_batch<4> spills at 128; 22-26 spill at 256
+}
+
 // Column sums over the 64 lanes of a wave of N values per lane, by recursive halving: at every level the lanes pair up, the
 // pair splits the columns -- one lane keeps the lower half, its partner the upper half, each adding the other's copy -- so
 // about N + log2(64) exchanges instead of 6 N; once one value per lane is left the remaining levels are plain pair sums
@@ -435,6 +508,7 @@ __device__ __forceinline__ void sweep_side(const SweepSide &S, double2 *__restri
     // ONE launch run both posterior updates (k_update2): the H update's rate needs colSums(ew_new) (reference
     // src/vbnmf_update.cpp:53), and sum_i ew_ik = (n aw + sum_i sw_ik) / bew_k is known without the W update having run.
     constexpr bool CS = (EV == 1) && LOGTERM;
+    constexpr bool PAIR = EV != 3 && sweep_pairs<R, NT, WIDE, SP>();   // (k_spmm does not divide: per entry)
     const bool cs_on = CS && S.csl != nullptr;             // (workgroup-uniform)
     const int snt = S.stream_nt;                           // the entry stream's cache policy (ld_stream)
     // The per-slice rows are added up per workgroup by colsum_finish(): NOT here -- their read-back is a global round trip,
@@ -506,7 +580,8 @@ __device__ __forceinline__ void sweep_side(const SweepSide &S, double2 *__restri
             double2 g0[R / 2];
             if ((R >= VBNMF_ONEBUF_FROM || R <= VBNMF_ONEBUF_UPTO) && !WIDE) {
                 // very large ranks: the factor row, the accumulators and ONE gathered row already fill
-                // the register file, so no second row buffer and no look-ahead here
+                // the register file, so no second row buffer and no look-ahead here -- and no pairing of the entries on one
+                // reciprocal either (sweep_pairs): a pair's head needs both rows resident, so this loop stays per entry
                 const uint4 *E = reinterpret_cast<const uint4 *>(S.packed + off) + tlane;
                 const int ngf = (EV == 3) ? 0 : min(ng, (S.slice_fast[s] & 0xFFFF) >> 2);      // groups inside the leading stretch of ones
                 int g = 0;
@@ -528,7 +603,60 @@ __device__ __forceinline__ void sweep_side(const SweepSide &S, double2 *__restri
                 }
                 if (LOGTERM && ngf > 0)
                     T.lsum += fma((double)T.pexp, 6.93147180559945286227e-01, dev_log_tab(T.prod, reinterpret_cast<const LogTabEntry *>(ldsG)));
+            } else if (!WIDE && PAIR) {
+                // The two-buffer trip with one reciprocal per pair of entries (sweep_pair_head): a trip is four pairs.  Both rows
+                // of a pair are resident at its head; row j + 2 is fetched into a buffer as soon as acc_j has released it, row
+                // j + 3 after acc_{j+1}, the first two rows of the next trip at the end of this one (both preloaded in front of
+                // the loop).  A row's LDS reads are covered by one row accumulate and the other waves of the SIMD.
+                double2 g1[R / 2];
+                const uint4 *E = reinterpret_cast<const uint4 *>(S.packed + off) + tlane;
+                Group4 a = unpack4<R>(ld_stream(E, snt), share), b = unpack4<R>(ld_stream(E + (size_t)min(1, ng - 1) * 64, snt), share);
+                lds_row<R>(ldsG, a.o0, g0);
+                lds_row<R>(ldsG, a.o1, g1);
+                double qa, qb;
+                // FENCE keeps the machine scheduler from sinking a row's LDS reads down to their first use
+#define VBNMF_FENCE() __builtin_amdgcn_sched_barrier(0)
+                // one pair: head, then each row's accumulate followed by the reload of its buffer (NEXT0 / NEXT1; BETWEEN: what the
+                // trip does once the pair's counts are consumed)
+#define VBNMF_PAIR(MODE, ca, cb, NEXT0, BETWEEN, NEXT1)                                           \
+                    sweep_pair_head<R, SP, MODE>(T, ldsG, g0, g1, (double)(ca), (double)(cb), LOGTERM, qa, qb); \
+                    BETWEEN                                                                       \
+                    sweep_row_acc<R>(T, g0, qa);                                                  \
+                    NEXT0; VBNMF_FENCE();                                                         \
+                    sweep_row_acc<R>(T, g1, qb);                                                  \
+                    NEXT1; VBNMF_FENCE();
+#define VBNMF_TRIP(MODE, PIN)                                                                     \
+                {                                                                                 \
+                    /* the next trip's groups; past the end: the last group again (an odd one is the tail's) */ \
+                    const uint4 ec = ld_stream(E + (size_t)min(2 * p + 2, ng - 1) * 64, snt), ed = ld_stream(E + (size_t)min(2 * p + 3, ng - 1) * 64, snt); \
+                    VBNMF_PAIR(MODE, a.c0, a.c1, lds_row<R>(ldsG, a.o2, g0), , lds_row<R>(ldsG, a.o3, g1)) \
+                    VBNMF_PAIR(MODE, a.c2, a.c3, lds_row<R>(ldsG, b.o0, g0), , lds_row<R>(ldsG, b.o1, g1)) \
+                    VBNMF_PAIR(MODE, b.c0, b.c1, lds_row<R>(ldsG, b.o2, g0), , lds_row<R>(ldsG, b.o3, g1)) \
+                    VBNMF_PAIR(MODE, b.c2, b.c3, lds_row<R>(ldsG, a.o0, g0), a = unpack4<R>(ec, share); PIN(a);, lds_row<R>(ldsG, a.o1, g1)) \
+                    b = unpack4<R>(ed, share);                                                    \
+                    PIN(b);                                                                       \
+                }
+                const int sfast = S.slice_fast[s];
+                const int npf = min(np, (sfast & 0xFFFF) >> 3);
+                const int npf2 = !LOGTERM ? npf : min(np, sfast >> 19);   // trips of ones or twos (>= npf)
+                int p = 0;
+                for (; p < npf - 1; p++) VBNMF_TRIP(1, pin_offsets)
+                if (p < npf) { VBNMF_TRIP(1, pin) p++; }                  // the next trip reads the counts again
+                for (; p < npf2; p++) VBNMF_TRIP(2, pin)
+                for (; p < np; p++) VBNMF_TRIP(0, pin)
+                if (ng & 1) {                                             // the odd last group: `a` holds it, its first two rows are in g0, g1
+                    VBNMF_PAIR(0, a.c0, a.c1, lds_row<R>(ldsG, a.o2, g0), , lds_row<R>(ldsG, a.o3, g1))
+                    sweep_pair_head<R, SP, 0>(T, ldsG, g0, g1, (double)a.c2, (double)a.c3, LOGTERM, qa, qb);
+                    sweep_row_acc<R>(T, g0, qa);
+                    sweep_row_acc<R>(T, g1, qb);
+                }
+                if (LOGTERM && npf2 > 0)                                  // the deferred logarithm of the leading ones and twos
+                    T.lsum += fma((double)T.pexp, 6.93147180559945286227e-01, dev_log_tab(T.prod, reinterpret_cast<const LogTabEntry *>(ldsG)));
+#undef VBNMF_TRIP
+#undef VBNMF_PAIR
+#undef VBNMF_FENCE
             } else if (!WIDE) {
+                // the per-entry two-buffer trip: the instantiations that do not pair (sweep_pairs) and the sparse product
                 double2 g1[R / 2];
                 const uint4 *E = reinterpret_cast<const uint4 *>(S.packed + off) + tlane;
                 Group4 a = unpack4<R>(ld_stream(E, snt), share), b = unpack4<R>(ld_stream(E + (size_t)min(1, ng - 1) * 64, snt), share);
@@ -617,6 +745,18 @@ __device__ __forceinline__ void sweep_side(const SweepSide &S, double2 *__restri
                     const double2 v0 = ld_stream(V + (size_t)g * 128, snt), v1 = ld_stream(V + (size_t)g * 128 + 1, snt);
                     lds_row<R>(ldsG, c.x * rowb + share, g0);
                     lds_row<R>(ldsG, c.y * rowb + share, g1);
+                    if constexpr (PAIR) {                                 // both rows are held before the first entry: paired alike
+                        double qa, qb;
+                        sweep_pair_head<R, SP, 0>(T, ldsG, g0, g1, v0.x, v0.y, LOGTERM, qa, qb);
+                        sweep_row_acc<R>(T, g0, qa);
+                        lds_row<R>(ldsG, c.z * rowb + share, g0);
+                        sweep_row_acc<R>(T, g1, qb);
+                        lds_row<R>(ldsG, c.w * rowb + share, g1);
+                        sweep_pair_head<R, SP, 0>(T, ldsG, g0, g1, v1.x, v1.y, LOGTERM, qa, qb);
+                        sweep_row_acc<R>(T, g0, qa);
+                        sweep_row_acc<R>(T, g1, qb);
+                        continue;
+                    }
                     sweep_entry<R, EV == 3, false, SP>(T, ldsG, g0, v0.x, LOGTERM);
                     lds_row<R>(ldsG, c.z * rowb + share, g0);
                     sweep_entry<R, EV == 3, false, SP>(T, ldsG, g1, v0.y, LOGTERM);
@@ -1652,6 +1792,9 @@ __global__ void k_test_special(int kind, int64_t n, const double *__restrict__ x
         case 4: y[i] = sp_rcp_seed(x[i]); break;             // raw v_rcp_f64
         case 5: y[i] = (double)__builtin_amdgcn_rcpf((float)x[i]); break;   // raw v_rcp_f32
         case 7: y[i] = dev_trigamma(x[i]); break;
+        case 8:                                              // the pair form: quads wa, wb, xa, xb in; qa, qb, r, 0 out
+            if (i % 4 == 0 && i + 3 < n) { y[i + 2] = dev_div_pair(x[i + 2], x[i], x[i + 3], x[i + 1], &y[i], &y[i + 1]); y[i + 3] = 0.0; }
+            break;
         default: y[i] = dev_log_tab(x[i], tab); break;
     }
 }

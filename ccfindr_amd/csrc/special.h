@@ -70,6 +70,27 @@ __host__ __device__ __forceinline__ double dev_div_fast(double x, double w)
     return fma(fma(-w, q, x), rc, q);
 }
 
+// xa / wa and xb / wb from ONE reciprocal: r = 1 / (wa wb) (seed plus ONE Newton step, returned), then
+// 1 / wa = wb r and 1 / wb = wa r, so qa = (xa wb) r and qb = (xb wa) r -- one seed, one product, two FMAs and four
+// multiplies for the pair (two of them fold away where x is the constant 1) instead of two seeds and six operations.
+//   error      : r = (1 - e^2) / (wa wb) with e the seed's relative error of the PRODUCT (<= 2^-24.4 on the device, 2^-23 with
+//                the host's coarsened seed), and four roundings on the way to a quotient (the product, r, x w, the last
+//                multiply): 2^-48 relative on the device, 2^-46 on the host -- dev_div_fast's bound, a quarter of an ulp of
+//                rounding more.  One-sided like it: the quotients are (x / w)(1 - e^2) up to those roundings.
+//   zeros      : x = 0 gives an exact 0 and leaves the partner's quotient alone (the sweep's padding slots).
+//   domain     : wa wb and its reciprocal must be normal doubles: |log2 wa| + |log2 wb| <= 1000, i.e. any two divisors
+//                in 2^+-500 -- the domain of the sweep's running product (kernels.h, sweep_entry).  x w_other cannot
+//                leave the range where the quotient itself does not.
+__host__ __device__ __forceinline__ double dev_div_pair(double xa, double wa, double xb, double wb, double *qa, double *qb)
+{
+    const double p = wa * wb;
+    const double rc = sp_rcp_seed(p);
+    const double r = fma(fma(-p, rc, 1.0), rc, rc);
+    *qa = (xa * wb) * r;
+    *qb = (xb * wa) * r;
+    return r;
+}
+
 // ---- table-driven ln for the sweep's inner loop ------------------------------------------
 // x = m 2^k, m in [0.5, 1) cut into 128 intervals; per interval c = 1/midpoint (rounded) and
 // -ln(c); r = m c - 1 is exact in one fma and |r| <= 2^-8, so
