@@ -1,6 +1,7 @@
 # Builds the MI355X (gfx950) library and the CPU oracle.  `python -c "import __graft_entry__ as g; g.build()"`
 # runs the same commands.  One object per source of ccfindr_amd/csrc (build/, git-ignored): every *.cpp as plain C++, every
-# *.hip for gfx950 -- one unit per feature, so a change to one feature recompiles that unit and not the engine's kernels.
+# *.hip for gfx950 -- one unit per feature and per kernel family of the engine (engine, batch, mlnmf, svd, labels, hooks), each
+# kernel in one unit, so a change to one of them recompiles that unit and not the others' kernels.
 HIPCC ?= /opt/rocm/bin/hipcc
 ARCH ?= gfx950
 CSRC := ccfindr_amd/csrc

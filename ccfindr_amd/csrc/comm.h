@@ -1,4 +1,4 @@
-// comm.h -- the communicator of cell-partitioned runs (included once, by engine.hip).
+// comm.h -- the communicator of cell-partitioned runs (engine.hip, and mlnmf.hip for the exchanges of its own loop).
 //
 // The reference's only inter-process mechanism is Rmpi::mpi.applyLB over restarts (reference R/bayesian.R:262-263),
 // with no communication while iterating.  A single factorisation whose cells are partitioned over the GPUs of a node
@@ -68,6 +68,8 @@ inline RcclApi &rccl_api()
     });
     return api;
 }
+
+int rccl_check(ncclResult_t r, const char *what);      // a failed RCCL call as a status (engine.hip)
 
 }  // namespace vbnmf
 

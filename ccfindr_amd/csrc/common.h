@@ -20,7 +20,7 @@ void set_error(const char *fmt, ...);
 int fail(int code, const char *fmt, ...);
 int env_int(const char *name, int dflt);    // an integer environment switch (unset or empty: dflt)
 
-// The consensus accumulator's label matrix on the host (engine.hip, for consensus.cpp): labels[run * m + cell], runs rows.
+// The consensus accumulator's label matrix on the host (labels.hip, for consensus.cpp): labels[run * m + cell], runs rows.
 // device (when not null): the HIP device the accumulator lives on.
 int consensus_download(vbnmf_consensus *c, std::vector<uint8_t> &labels, int64_t &m, int32_t &runs, int32_t &unlabelled, int32_t *device = nullptr);
 

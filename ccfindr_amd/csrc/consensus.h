@@ -1,5 +1,5 @@
 // consensus.h -- device kernels of the consensus accumulator (vbnmf_consensus_*, include/vbnmf.h; included once, by
-// engine.hip).  factorize() reports, per rank, the dispersion and the cophenetic correlation of the consensus matrix
+// labels.hip).  factorize() reports, per rank, the dispersion and the cophenetic correlation of the consensus matrix
 // C_ij = share of the R runs in which cells i and j carry the same arg-max label (reference R/factorize.R:51-78,
 // :218-230).  The reference forms the O(m^2) pair vector; its sums follow from the label vectors alone:
 //   sum_{i<j} C_ij   = S1 / R,    S1 = sum_a sum_k pairs(n_k(a))

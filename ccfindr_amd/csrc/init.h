@@ -1,96 +1,15 @@
-// init.h -- device kernels either side of the update path (included once, by engine.hip):
-//   * the 'random' initial state of vb_init (reference R/bayesian.R:111-115: w ~ Gamma(shape aw, scale bw/aw),
-//     h ~ Gamma(ah, bh/ah)) drawn on the device: Philox4x32-10 counters + Marsaglia-Tsang.  R's RNG stream cannot be
-//     matched outside R; the draws are a function of (seed, factor, element) only, so they do not depend on the
-//     launch geometry, the device or the rank count of a partitioned run;
-//   * the consensus stopping count of factorize() (reference R/factorize.R:198-208: sum(cnn != cnn0) over all pairs
-//     of cells, cnn from connectivity(), :51-60) without the O(m^2) vectors: a contingency table of the old and new
-//     arg-max labels, pairs(row sums) + pairs(column sums) - 2 pairs(table);
-//   * the dense pieces of the truncated SVD behind the 'svd2' initialiser (reference R/bayesian.R:150-159, irlba):
-//     Gram matrix of a tall [N][R] block, Cholesky factor / Jacobi eigen-decomposition of the k x k result, and the
-//     product of the tall block with a k x k matrix -- so that the subspace stays on the device between the sparse
-//     products (k_spmm) and nothing crosses PCIe inside the iteration.
+// init.h -- the dense pieces of the truncated SVD behind the 'svd2' initialiser (reference R/bayesian.R:150-159, irlba;
+// SURVEY.md section 8f-3; included once, by svd.hip): the standard normal block of the range finder (philox.h), the Gram
+// matrix of a tall [N][R] block, Cholesky factor / Jacobi eigen-decomposition of the k x k result, and the product of the
+// tall block with a k x k matrix -- so that the subspace stays on the device between the sparse products (k_spmm) and
+// nothing crosses PCIe inside the iteration.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "philox.h"
+
 namespace vbnmf {
-
-// ---------------------------------------------------------------- Philox4x32-10
-struct Philox {
-    uint32_t c[4], k[2];
-};
-__host__ __device__ __forceinline__ void philox_round(uint32_t (&c)[4], const uint32_t (&k)[2])
-{
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k[0], n1 = (uint32_t)p1;
-    const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k[1], n3 = (uint32_t)p0;
-    c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-}
-// 4 x 32 random bits for counter (i0, i1, i2, i3) under key (k0, k1)
-__host__ __device__ __forceinline__ void philox4x32(uint32_t i0, uint32_t i1, uint32_t i2, uint32_t i3, uint32_t k0, uint32_t k1,
-                                                    uint32_t (&out)[4])
-{
-    uint32_t c[4] = {i0, i1, i2, i3}, k[2] = {k0, k1};
-#pragma unroll
-    for (int r = 0; r < 10; r++) {
-        philox_round(c, k);
-        k[0] += 0x9E3779B9u; k[1] += 0xBB67AE85u;
-    }
-    out[0] = c[0]; out[1] = c[1]; out[2] = c[2]; out[3] = c[3];
-}
-// uniform in (0, 1): 53 bits, never 0 or 1
-__host__ __device__ __forceinline__ double u53(uint32_t hi, uint32_t lo)
-{
-    const uint64_t v = ((uint64_t)hi << 21) ^ (uint64_t)(lo >> 11);              // 53 bits
-    return ((double)v + 0.5) * (1.0 / 9007199254740992.0);
-}
-
-// One Gamma(shape a, scale s) variate for stream (element, factor) of key seed.  Marsaglia & Tsang (2000): for a >= 1,
-// d = a - 1/3, c = 1/sqrt(9d): x ~ N(0,1), v = (1 + c x)^3, accept if v > 0 and log u < x^2/2 + d - d v + d log v;
-// a < 1: Gamma(a + 1) u^(1/a).  Attempt t of the stream uses counter (element lo, element hi, factor, t).
-__device__ inline double gamma_draw(double a, double scale, uint64_t element, uint32_t factor, uint32_t k0, uint32_t k1)
-{
-    const double a1 = a < 1.0 ? a + 1.0 : a;
-    const double d = a1 - 1.0 / 3.0, c = 1.0 / sqrt(9.0 * d);
-    double g = 0.0;
-    uint32_t r[4];
-    for (uint32_t t = 0; t < 64; t++) {                       // acceptance > 0.95 per attempt: 64 never runs out in practice
-        philox4x32((uint32_t)element, (uint32_t)(element >> 32), factor, 2 * t, k0, k1, r);
-        const double u1 = u53(r[0], r[1]), u2 = u53(r[2], r[3]);
-        const double x = sqrt(-2.0 * log(u1)) * cos(6.283185307179586476925 * u2);     // Box-Muller
-        philox4x32((uint32_t)element, (uint32_t)(element >> 32), factor, 2 * t + 1, k0, k1, r);
-        const double u = u53(r[0], r[1]);
-        const double v1 = 1.0 + c * x;
-        if (v1 <= 0.0) continue;
-        const double v = v1 * v1 * v1;
-        if (log(u) < 0.5 * x * x + d - d * v + d * log(v)) {
-            g = d * v;
-            if (a < 1.0) g *= pow(u53(r[2], r[3]), 1.0 / a);
-            break;
-        }
-    }
-    return g * scale;
-}
-
-// f[major][k] = e[major][k] = Gamma(shape a, scale b / a) for k < r (pad columns 0); factor 0 = W, 1 = H.  The element
-// index is the GLOBAL (major, k) position (major0 = first cell of a partition), so a partitioned run draws the same H.
-__global__ __launch_bounds__(256) void k_gamma_init(double *__restrict__ f, double *__restrict__ e, double *__restrict__ dvar,
-                                                    int64_t nmaj, int64_t major0, int r, int R, double a, double b,
-                                                    uint32_t factor, uint32_t k0, uint32_t k1, const int32_t *__restrict__ perm)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= nmaj * R) return;
-    const int64_t M = i / R;
-    const int k = (int)(i - M * R);
-    double v = 0.0;
-    // (perm: the layout's order of the cells -- row M of the array is the caller's major perm[M]; the draw is keyed by the
-    // CALLER's global element index, so it does not depend on the order, the launch geometry or the partitioning)
-    if (k < r) v = gamma_draw(a, b / a, (uint64_t)(major0 + (perm ? (int64_t)perm[M] : M)) * (uint64_t)r + (uint64_t)k, factor, k0, k1);
-    f[i] = v;
-    if (e) e[i] = v;
-    if (dvar) dvar[i] = 0.0;
-}
 
 // standard normal block for the range finder of the truncated SVD: g[major][k], k < r
 __global__ __launch_bounds__(256) void k_normal_init(double *__restrict__ g, int64_t nmaj, int r, int R, uint32_t k0, uint32_t k1)
@@ -107,36 +26,6 @@ __global__ __launch_bounds__(256) void k_normal_init(double *__restrict__ g, int
         v = sqrt(-2.0 * log(u53(q[0], q[1]))) * cos(6.283185307179586476925 * u53(q[2], q[3]));
     }
     g[i] = v;
-}
-
-// ---------------------------------------------------------------- connectivity change count
-// table[old][new] += 1 per cell (integer atomics: order-independent).  ids are 1-based, 0 = no label (all-NaN column).
-__global__ __launch_bounds__(256) void k_label_table(const int32_t *__restrict__ ids_old, const int32_t *__restrict__ ids_new,
-                                                     int64_t m, int r, unsigned long long *__restrict__ table)
-{
-    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (j >= m) return;
-    const int a = ids_old[j], b = ids_new[j];
-    atomicAdd(&table[(size_t)a * (r + 1) + b], 1ull);
-}
-// pairs together in exactly one of the two labelings = pairs(rows) + pairs(cols) - 2 pairs(cells of the table)
-__global__ void k_label_pairs(const unsigned long long *__restrict__ table, int r, unsigned long long *__restrict__ out)
-{
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    const int q = r + 1;
-    auto pairs = [](unsigned long long c) { return c * (c - (c > 0 ? 1ull : 0ull)) / 2ull; };
-    unsigned long long both = 0, rows = 0, cols = 0;
-    for (int a = 0; a < q; a++) {
-        unsigned long long rs = 0;
-        for (int b = 0; b < q; b++) { const unsigned long long c = table[(size_t)a * q + b]; rs += c; both += pairs(c); }
-        rows += pairs(rs);
-    }
-    for (int b = 0; b < q; b++) {
-        unsigned long long cs = 0;
-        for (int a = 0; a < q; a++) cs += table[(size_t)a * q + b];
-        cols += pairs(cs);
-    }
-    out[0] = rows + cols - 2ull * both;
 }
 
 // ---------------------------------------------------------------- dense pieces of the truncated SVD

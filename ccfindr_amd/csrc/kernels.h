@@ -1,4 +1,6 @@
-// kernels.h -- hand-written gfx950 kernels of the VB-NMF step (included once, by engine.hip).
+// kernels.h -- hand-written gfx950 kernels of the VB-NMF step: the sweep machinery and the template kernels, which every
+// unit on the engine includes (engine.h) and which are emitted where they are launched; the step's kernels that are no
+// templates are in step.h, for engine.hip alone.
 //
 // Device state layout (all fp64, "index-major": one factor row = R contiguous doubles,
 // R = rank padded to even, pad columns hold 0):
@@ -1573,95 +1575,6 @@ __global__ __launch_bounds__(kUpdateThreads) void k_prime(int64_t nmaj, int r, c
     if (t == 0) { o[R] = 0.0; o[R + 1] = 0.0; }
 }
 
-// ------------------------------------------------------------------------------------
-// Cell-partitioned runs: the gene-side statistics and the cell-side scalars go into the
-// reduce buffer [swsum n*R | tail R+4] that the caller all-reduces.
-// ------------------------------------------------------------------------------------
-// out[major][k] = sum of the major's task partials, fixed order.
-__global__ __launch_bounds__(256) void k_pack(const double *__restrict__ part, const int32_t *__restrict__ row_ptr,
-                                              const uint32_t *__restrict__ row_task, int64_t nmaj, int R,
-                                              double *__restrict__ out)
-{
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= nmaj * R) return;
-    const int64_t M = e / R;
-    const int k = (int)(e - M * R);
-    out[e] = task_sum(part, row_task, row_ptr[M], row_ptr[M + 1], R, k);
-}
-
-// k_pack and k_tail_h in one launch (the device-driven partitioned loop): one extra block forms the cell side's column sums.
-__global__ __launch_bounds__(256) void k_pack_tail(const double *__restrict__ part, const int32_t *__restrict__ row_ptr,
-                                                   const uint32_t *__restrict__ row_task, int64_t nmaj, int R,
-                                                   double *__restrict__ out, const double *__restrict__ bpH, int nbH,
-                                                   const int32_t *__restrict__ stop)
-{
-    if (blockIdx.x == gridDim.x - 1) {
-        if (stop && *stop) return;                         // (as k_tail_h: steps queued past the stop leave the tail as it is)
-        bp_colsums(bpH, nbH, R + 2, out + nmaj * R, 256);
-        return;
-    }
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= nmaj * R) return;
-    const int64_t M = e / R;
-    const int k = (int)(e - M * R);
-    out[e] = task_sum(part, row_task, row_ptr[M], row_ptr[M + 1], R, k);
-}
-
-// Device-driven loop of a cell-partitioned engine: the reduce buffer is sent in two pieces.  The first,
-// [swsum n*R | rowSum(eh)_k (R) | sum H-terms | sum log lh], is complete once the gene-side sweep and the H update are
-// done (k_pack + k_tail_h) and travels while the cell-side sweep runs; the second, [data term | sum lgamma(x+1)], needs
-// both sweeps (k_tail_data) and is two doubles.
-__global__ __launch_bounds__(1024) void k_tail_h(const double *__restrict__ bpH, int nbH, int R, double *__restrict__ tail,
-                                                 const int32_t *__restrict__ stop)
-{
-    if (stop && *stop) return;
-    bp_colsums(bpH, nbH, R + 2, tail, 1024);
-}
-
-// In-process stand-in for the all-reduce between partition engines that share one device (tests, single-GPU
-// rehearsals of a partitioned run): recv[p][i] = send[0][i] + send[1][i] + ... in partition order, for every p.
-__global__ __launch_bounds__(256) void k_group_sum(const double *const *__restrict__ send, double *const *__restrict__ recv,
-                                                   int parts, int64_t count)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= count) return;
-    double s = send[0][i];
-    for (int p = 1; p < parts; p++) s += send[p][i];
-    for (int p = 0; p < parts; p++) recv[p][i] = s;
-}
-
-// The same on `count` doubles from offset `off` of every partition's buffer (the two-double exchange of the partitioned ML loop,
-// mlnmf.h, whose offset does not depend on the VB loop's fold as the send / receive tables of its own small exchange do).
-__global__ __launch_bounds__(256) void k_group_sum_at(const double *const *__restrict__ send, double *const *__restrict__ recv,
-                                                      int parts, int64_t off, int64_t count)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= count) return;
-    double s = send[0][off + i];
-    for (int p = 1; p < parts; p++) s += send[p][off + i];
-    for (int p = 0; p < parts; p++) recv[p][off + i] = s;
-}
-
-// tail = [rowSum(eh)_k (R) | sum H-terms | sum log lh | data term | sum lgamma(x+1)] of THIS partition.
-__global__ __launch_bounds__(1024) void k_tail(const double *__restrict__ bpH, int nbH, int R,
-                                               const double *__restrict__ epart, int64_t nepart, double lgx,
-                                               double *__restrict__ tail)
-{
-    __shared__ double sm[1024];
-    bp_colsums(bpH, nbH, R + 2, tail, 1024);
-    const double data = block_vec_sum(epart, nepart, sm);
-    if (threadIdx.x == 0) { tail[R + 2] = data; tail[R + 3] = lgx; }
-}
-
-__global__ __launch_bounds__(1024) void k_tail_data(const double *__restrict__ epart, int64_t nepart, double lgx,
-                                                    double *__restrict__ out2, const int32_t *__restrict__ stop)
-{
-    __shared__ double sm[1024];
-    if (stop && *stop) return;
-    const double data = block_vec_sum(epart, nepart, sm);
-    if (threadIdx.x == 0) { out2[0] = data; out2[1] = lgx; }
-}
-
 // Evidence and the four hyper statistics.  One block.
 //   W side : colSum(ew)_k, sum W-terms, sum log lw  = column sums of bpW (replicated in every partition)
 //   tail   : as k_tail writes it; either given (summed over partitions by the caller) or, when
@@ -1772,44 +1685,6 @@ __global__ __launch_bounds__(1024) void k_control(const double *__restrict__ bpW
     __threadfence_system();
     reinterpret_cast<volatile double *>(out_host)[6] = (double)reason;
     reinterpret_cast<volatile double *>(out_host)[7] = (double)it;
-}
-
-// Loads the control block of a device-driven loop (stream-ordered, no host copy to wait for).
-__global__ void k_ctl_init(LoopCtl *ctl, const LoopCtl v) { *ctl = v; }
-
-// Device-side evaluation of the special functions, for tests (tests/test_gpu_special.py).
-__global__ void k_test_special(int kind, int64_t n, const double *__restrict__ x, double *__restrict__ y,
-                               const LogTabEntry *__restrict__ tab)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    double psi, lg;
-    switch (kind) {
-        case 0: y[i] = dev_log(x[i]); break;
-        case 1: dev_psi_lgamma(x[i], &psi, &lg); y[i] = psi; break;
-        case 2: dev_psi_lgamma(x[i], &psi, &lg); y[i] = lg; break;
-        case 3: y[i] = dev_div(1.0, x[i]); break;
-        case 4: y[i] = sp_rcp_seed(x[i]); break;             // raw v_rcp_f64
-        case 5: y[i] = (double)__builtin_amdgcn_rcpf((float)x[i]); break;   // raw v_rcp_f32
-        case 7: y[i] = dev_trigamma(x[i]); break;
-        case 8:                                              // the pair form: quads wa, wb, xa, xb in; qa, qb, r, 0 out
-            if (i % 4 == 0 && i + 3 < n) { y[i + 2] = dev_div_pair(x[i + 2], x[i], x[i + 3], x[i + 1], &y[i], &y[i + 1]); y[i + 3] = 0.0; }
-            break;
-        default: y[i] = dev_log_tab(x[i], tab); break;
-    }
-}
-
-// Device-side evaluation of hyper_update, for tests (tests/test_gpu_hyper_update.py): one wave per case, lanes 0 and 1 in
-// the loops' own dev_hyper_update_pair, traced.  hyper: [count][4] in / out; trace: [count][2][100]; iters, failed: [count].
-__global__ __launch_bounds__(64) void k_test_hyper_update(int count, const int32_t *__restrict__ flags, const double *__restrict__ stats,
-                                                          double *hyper, int32_t *__restrict__ failed, int32_t *__restrict__ iters,
-                                                          double *trace)
-{
-    const int c = blockIdx.x, lane = threadIdx.x;
-    if (c >= count || lane > 1) return;
-    const int f = dev_hyper_update_pair<true>(flags + 4 * (size_t)c, stats + 4 * (size_t)c, hyper + 4 * (size_t)c, lane,
-                                              trace + 200 * (size_t)c, iters + c);
-    if (lane == 0) failed[c] = f;
 }
 
 }  // namespace vbnmf

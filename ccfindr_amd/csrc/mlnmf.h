@@ -1,4 +1,4 @@
-// mlnmf.h -- gfx950 kernels of the maximum-likelihood NMF step (included once, by engine.hip, after kernels.h).
+// mlnmf.h -- gfx950 kernels of the maximum-likelihood NMF step (included once, by mlnmf.hip).
 //
 // Reference: R/factorize.R:2-27 (nmf_updateR) and :40-49 (likelihood), behind factorize() (:140-320).
 //   :8-15   h <- h .* (t(w) %*% (x / (w %*% h))) / colSums(w)   [+ Gamma prior: up + a - 1, down + a/b] ; clip at eps
@@ -14,7 +14,7 @@
 //   k_ml_update(H) -> k_sweep1(gene) -> k_pack_tail -> ALL-REDUCE [statistics n*R | rowSums(h_new)] -> k_ml_update(W, dense form)
 //   -> k_sweep1(cell) -> k_tail_data -> ALL-REDUCE [sum x log(wh) | constant] -> k_ml_control / k_ml_final on the reduced values
 // (criterion = 'connectivity': k_ml_tail_conn in k_tail_data's place, and the second all-reduce is [. | . | label table (r+1)^2])
-// (engine.hip: queue_ml_step; host-stepped: vbnmf_engine_ml_step_local / ml_step_finish).
+// (mlnmf.hip: queue_ml_step; host-stepped: vbnmf_engine_ml_step_local / ml_step_finish).
 #pragma once
 #include "kernels.h"
 
@@ -33,7 +33,7 @@ namespace vbnmf {
 // its h_new -- which.max(h_new[, j]), k_argmax's rules, from the values its threads have just written -- and adds every
 // cell to entry [label of step t-1][label of step t] of an (r+1) x (r+1) table (integer atomics: no order in the result).
 // The control step of step t (in the NEXT launch of this kernel, or k_ml_control) reads the finished table:
-//   nchange = pairs(rows) + pairs(cols) - 2 pairs(cells)   (k_label_pairs' arithmetic, init.h);  it == 1: m (m - 1) / 2
+//   nchange = pairs(rows) + pairs(cols) - 2 pairs(cells)   (k_label_pairs' arithmetic, below);  it == 1: m (m - 1) / 2
 //   zstep   = nchange == 0 ? zstep + 1 : 0 ;  stop (reason 2) at zstep == ncnn_step, else (reason 4) at max_it
 // Nothing is read and written in one launch: labels alternate between two arrays by step parity, tables rotate among four
 // -- step t fills table t & 3, its control reads (t - 1) & 3, and it zeroes (t + 1) & 3 for the next step; a period of
@@ -449,6 +449,36 @@ __global__ __launch_bounds__(256) void k_argmax(const double *__restrict__ h, in
         if (v == v && (best == 0 || v > bv)) { best = k + 1; bv = v; }
     }
     ids[j] = best;
+}
+
+// ---------------------------------------------------------------- connectivity change count
+// table[old][new] += 1 per cell (integer atomics: order-independent).  ids are 1-based, 0 = no label (all-NaN column).
+__global__ __launch_bounds__(256) void k_label_table(const int32_t *__restrict__ ids_old, const int32_t *__restrict__ ids_new,
+                                                     int64_t m, int r, unsigned long long *__restrict__ table)
+{
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= m) return;
+    const int a = ids_old[j], b = ids_new[j];
+    atomicAdd(&table[(size_t)a * (r + 1) + b], 1ull);
+}
+// pairs together in exactly one of the two labelings = pairs(rows) + pairs(cols) - 2 pairs(cells of the table)
+__global__ void k_label_pairs(const unsigned long long *__restrict__ table, int r, unsigned long long *__restrict__ out)
+{
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const int q = r + 1;
+    auto pairs = [](unsigned long long c) { return c * (c - (c > 0 ? 1ull : 0ull)) / 2ull; };
+    unsigned long long both = 0, rows = 0, cols = 0;
+    for (int a = 0; a < q; a++) {
+        unsigned long long rs = 0;
+        for (int b = 0; b < q; b++) { const unsigned long long c = table[(size_t)a * q + b]; rs += c; both += pairs(c); }
+        rows += pairs(rs);
+    }
+    for (int b = 0; b < q; b++) {
+        unsigned long long cs = 0;
+        for (int a = 0; a < q; a++) cs += table[(size_t)a * q + b];
+        cols += pairs(cs);
+    }
+    out[0] = rows + cols - 2ull * both;
 }
 
 }  // namespace vbnmf

@@ -5,6 +5,7 @@ import glob
 import os
 import re
 import subprocess
+import tempfile
 
 import __graft_entry__ as g
 
@@ -34,6 +35,30 @@ def test_every_header_is_a_dependency_of_the_build():
     headers = on_disk("*.h")
     assert headers and headers <= set(g.HIP_DEPS)
     assert os.path.join(ROOT, "include", "vbnmf.h") in g.HIP_DEPS and set(g.HIP_SOURCES) <= set(g.HIP_DEPS)
+
+
+def test_every_kernel_is_emitted_by_one_unit():
+    """A kernel that two units emit is compiled twice and loaded twice: a non-template __global__ in a header that two units
+    include, or a template that two units launch.  The names come from the metadata note of each object's gfx950 code object."""
+    g.build(quiet=True)
+    llvm = os.path.dirname(READELF)
+    home = {}
+    for obj in sorted(glob.glob(os.path.join(g.OBJ, "*.o"))):
+        if ".hip_fatbin" not in subprocess.run([READELF, "-S", obj], capture_output=True, text=True, check=True).stdout:
+            continue
+        with tempfile.TemporaryDirectory() as d:
+            fat, co = os.path.join(d, "fat.bin"), os.path.join(d, "dev.co")
+            subprocess.run([os.path.join(llvm, "llvm-objcopy"), "--dump-section", ".hip_fatbin=" + fat, obj, os.path.join(d, "copy.o")], check=True)
+            subprocess.run([os.path.join(llvm, "clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + fat,
+                            "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co], check=True)
+            if os.path.getsize(co) == 0:      # a unit without kernels
+                continue
+            notes = subprocess.run([READELF, "--notes", co], capture_output=True, text=True, check=True).stdout
+        for name in re.findall(r"^    \.name:\s+(\S+)$", notes, flags=re.M):      # (a kernel's own key: its arguments' sit deeper)
+            home.setdefault(name, []).append(os.path.basename(obj))
+    assert len(home) > 100 and len({v[0] for v in home.values()}) >= 10, sorted({v[0] for v in home.values()})
+    twice = {k: v for k, v in home.items() if len(v) > 1}
+    assert not twice, twice
 
 
 def test_the_library_holds_one_buffer_pool():

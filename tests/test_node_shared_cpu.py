@@ -126,7 +126,7 @@ MASK = (1 << 64) - 1
 
 
 def _chunk_digest(words, seed, c=0):
-    """ccfindr_amd/csrc/engine.hip hash_bytes2, one chunk of whole 8-byte words: four chains, word q feeds chain q mod 4 (a
+    """ccfindr_amd/csrc/stateless.cpp hash_bytes2, one chunk of whole 8-byte words: four chains, word q feeds chain q mod 4 (a
     last incomplete group of words feeds chains 0, 1, ... in order), the chains combined in order.  Returns the digest and,
     per word, the state of ITS chain before the word entered."""
     K, KL, KC = 0xFF51AFD7ED558CCD, 0xA24BAED4963EE407, 0xC4CEB9FE1A85EC53

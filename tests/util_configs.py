@@ -30,7 +30,7 @@ VB_PATHS = ("steps", "run", "batch", "group", "init")
 ML_PATHS = ("ml_steps", "ml_run", "batch_ml")
 PATHS = VB_PATHS + ML_PATHS
 BATCH_PATHS = ("batch", "batch_ml")
-BATCH_MAX_WIDTH = 16                                   # engine.hip kBatchMaxPaddedRank
+BATCH_MAX_WIDTH = 16                                   # rank.h kBatchMaxPaddedRank
 # forced geometries (VBNMF_LDS_KB, VBNMF_NWG, VBNMF_MAX_LEN): small LDS blocks, few workgroups (not a multiple of 8), short tasks
 FORCED = ((32, 5, 16), (48, 3, 8), (64, 9, 32))
 FORCED_KEYS = ("VBNMF_LDS_KB", "VBNMF_NWG", "VBNMF_MAX_LEN")
