@@ -18,8 +18,6 @@ struct vbnmf_comm;
 
 namespace vbnmf {
 
-constexpr int kHostOut = 16;        // doubles in the pinned result block of an engine
-
 // The layout's arrays on the device.  Engines made from a cached layout (same matrix, same geometry, same device)
 // share one of these; the per-engine part is DeviceSide::part.
 struct DeviceArrays {
@@ -106,7 +104,7 @@ struct vbnmf_engine {
     std::vector<hipEvent_t> ev_ring;  // events ordering the two streams, cycled (a step uses 3)
     size_t ev_next = 0;
     double *d_out = nullptr;          // [8]
-    double *h_out = nullptr;          // pinned, device-visible [kHostOut]; [7] = sequence flag; [8..12] = hyper, lk0 of a device-driven loop
+    double *h_out = nullptr;          // pinned, device-visible [kHostOut]: the slots are HostOutSlot's (kernels.h)
     double *h_out_dev = nullptr;      // device address of h_out
     double *h_stage = nullptr;        // pinned staging of set_state / get_state (index-major copies of the state arrays)
     size_t h_stage_count = 0;

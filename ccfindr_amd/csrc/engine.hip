@@ -494,7 +494,7 @@ double wait_timeout_s()
 // Wait for k_final's sequence flag in pinned memory; falls back to the stream if it takes long.
 int wait_result(vbnmf_engine *e)
 {
-    volatile double *flag = e->h_out + 7;
+    volatile double *flag = e->h_out + kOutSeq;
     const auto t0 = std::chrono::steady_clock::now();
     const double limit = wait_timeout_s();
     for (long spins = 0; *flag != e->seq; spins++) {
@@ -1244,8 +1244,8 @@ int vbnmf_engine_step_finish(vbnmf_engine *e, double *lkh, double *stats)
     if (int rc = wait_result(e)) return rc;
     e->step_pending = false;
     if (int rc = harvest_timing(e)) return rc;
-    if (lkh) *lkh = e->h_out[0];
-    if (stats) for (int q = 0; q < 4; q++) stats[q] = e->h_out[1 + q];
+    if (lkh) *lkh = e->h_out[kOutLkh];
+    if (stats) for (int q = 0; q < 4; q++) stats[q] = e->h_out[kOutStats + q];
     return VBNMF_OK;
 }
 
@@ -1528,20 +1528,21 @@ void launch_ctl_init(hipStream_t stream, LoopCtl *ctl, const LoopCtl &v)
     hipLaunchKernelGGL(k_ctl_init, dim3(1), dim3(1), 0, stream, ctl, v);
 }
 
-// The results the last live control step of each of `count` engines left in its h_out: [5] steps, [6] reason, [0] the last
-// likelihood (lk: lkh of the VB loop, lk of the ML loop -- [0] itself stays, ml_likelihood() keeps answering for the pair
-// held now), [12] lk0 and [8..11] the hyper-parameters (VB); history: `rows` rows of `width` doubles per engine.
+// The results the last live control step of each of `count` engines left in its h_out (HostOutSlot, kernels.h): kOutIt steps,
+// kOutReason, kOutLkh the last likelihood (lk: lkh of the VB loop, lk of the ML loop -- the slot itself stays, ml_likelihood()
+// keeps answering for the pair held now), kOutLk0 and kOutHyper, the hyper-parameters (VB); history: `rows` rows of `width`
+// doubles per engine.
 void read_out(vbnmf_engine *const *engs, int count, int32_t *it_out, double *lk0_out, double *lk_out, int32_t *reason_out,
               double *hyper, double *history, int64_t rows, int width)
 {
     for (int b = 0; b < count; b++) {
         const double *ho = engs[b]->h_out;
-        const int it = (int)ho[5];
-        if (hyper) for (int q = 0; q < 4; q++) hyper[(size_t)b * 4 + q] = ho[8 + q];
+        const int it = (int)ho[kOutIt];
+        if (hyper) for (int q = 0; q < 4; q++) hyper[(size_t)b * 4 + q] = ho[kOutHyper + q];
         if (it_out) it_out[b] = it;
-        if (lk0_out) lk0_out[b] = ho[12];
-        if (lk_out) lk_out[b] = ho[0];
-        if (reason_out) reason_out[b] = (int)ho[6];
+        if (lk0_out) lk0_out[b] = ho[kOutLk0];
+        if (lk_out) lk_out[b] = ho[kOutLkh];
+        if (reason_out) reason_out[b] = (int)ho[kOutReason];
         if (history && it > 0) std::memcpy(history + (size_t)b * rows * width, engs[b]->h_hist, (size_t)it * width * sizeof(double));
     }
 }

@@ -105,75 +105,26 @@ __device__ __forceinline__ void pin_offsets(Group4 &g)
 // The entry stream is read exactly once per sweep (400 MB at the headline size, two sides): loaded with the non-temporal
 // policy so that it does not push what IS re-read -- the factor rows, the per-task partial rows the update kernels gather
 // back, the state -- out of the 4 MB L2s and the 256 MB Infinity Cache (MI355X_MICROARCH.md: a table stays resident only
-// while everything moved between two uses of a line fits in about 256 MiB).  VBNMF_STREAM_NT=0 builds the plain loads (A/B).
-#ifndef VBNMF_STREAM_NT
-#define VBNMF_STREAM_NT 1
-#endif
-#ifndef VBNMF_PREFETCH2
-#define VBNMF_PREFETCH2 0
-#endif
-#ifndef VBNMF_END_WB
-#define VBNMF_END_WB 0
-#endif
+// while everything moved between two uses of a line fits in about 256 MiB).
 // nt (wave-uniform, SweepSide::stream_nt): the engine sets it when the step's streams do NOT fit the Infinity Cache.  Where they do
 // (C2: 130 MB of entries; 5 000 x 20 000: 61 MB) the default policy keeps the stream itself on the die from one step to the next, and
 // the non-temporal loads cost 1-3.5 % (profiles/r05_small_nt_ab.txt).
 __device__ __forceinline__ uint4 ld_stream(const uint4 *p, int nt)
 {
-#if VBNMF_STREAM_NT
     if (nt) {
         typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
         const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(p));
         return make_uint4(v.x, v.y, v.z, v.w);
     }
-#endif
     return *p;
-}
-// The per-task partial rows (75 MB per sweep at the headline size) are written once and gathered back by the update kernels.
-// VBNMF_PART_NT=1 stores them with the non-temporal policy (experiment: profiles/r05_part_nt_ab.txt).
-#ifndef VBNMF_PART_NT
-#define VBNMF_PART_NT 0
-#endif
-__device__ __forceinline__ void st_part(double2 *p, double2 v)
-{
-#if VBNMF_PART_NT
-    typedef double f64x2 __attribute__((ext_vector_type(2)));
-    f64x2 w; w.x = v.x; w.y = v.y;
-    __builtin_nontemporal_store(w, reinterpret_cast<f64x2 *>(p));
-#else
-    *p = v;
-#endif
-}
-// The update kernels gather every partial row once and write the means / variances (e, d) that nothing on the device reads
-// again before the next update: VBNMF_UPD_NT=1 gives both the non-temporal policy (experiment: profiles/r05_upd_nt_ab.txt).
-#ifndef VBNMF_UPD_NT
-#define VBNMF_UPD_NT 0
-#endif
-__device__ __forceinline__ double ld_part(const double *p)
-{
-#if VBNMF_UPD_NT
-    return __builtin_nontemporal_load(p);
-#else
-    return *p;
-#endif
-}
-__device__ __forceinline__ void st_once(double *p, double v)
-{
-#if VBNMF_UPD_NT
-    __builtin_nontemporal_store(v, p);
-#else
-    *p = v;
-#endif
 }
 __device__ __forceinline__ double2 ld_stream(const double2 *p, int nt)
 {
-#if VBNMF_STREAM_NT
     if (nt) {
         typedef double f64x2 __attribute__((ext_vector_type(2)));
         const f64x2 v = __builtin_nontemporal_load(reinterpret_cast<const f64x2 *>(p));
         return make_double2(v.x, v.y);
     }
-#endif
     return *p;
 }
 // LDS image of the sweep: [0, kLdsTabBytes) the ln table, then kLdsEvSlots per-slice evidence
@@ -359,7 +310,7 @@ __device__ __forceinline__ void sweep_row_acc(SweepRegs<R> &S, const double2 (&g
 template <int R, int NT, bool WIDE, int SP>
 constexpr bool sweep_pairs()
 {
-    if (!VBNMF_PAIR_RECIP || VBNMF_PREFETCH2) return false;            // (the look-ahead experiment lives in the per-entry trip)
+    if (!VBNMF_PAIR_RECIP) return false;
     if ((R >= VBNMF_ONEBUF_FROM || R <= VBNMF_ONEBUF_UPTO) && !WIDE) return false;
     if (NT == 768 && R >= 12) return false;                // 12, 14: already at the 168 VGPRs of three waves, the pair spills
     if (SP > 1) return WIDE && R == 20;                    // shared ranks: the packed forms and R >= 24 spill at 256 VGPRs
@@ -662,12 +613,6 @@ __device__ __forceinline__ void sweep_side(const SweepSide &S, double2 *__restri
                 double2 g1[R / 2];
                 const uint4 *E = reinterpret_cast<const uint4 *>(S.packed + off) + tlane;
                 Group4 a = unpack4<R>(ld_stream(E, snt), share), b = unpack4<R>(ld_stream(E + (size_t)min(1, ng - 1) * 64, snt), share);
-#if VBNMF_PREFETCH2
-                // the entry stream TWO trips ahead: the groups of trip p + 1 are on their way (ec, ed) when trip p issues the
-                // loads of trip p + 2 -- with the stream read non-temporally every group comes from HBM, 1.5-2 us under load,
-                // about what ONE trip of three interleaved waves takes
-                uint4 ec = ld_stream(E + (size_t)min(2, ng - 1) * 64, snt), ed = ld_stream(E + (size_t)min(3, ng - 1) * 64, snt);
-#endif
                 lds_row<R>(ldsG, a.o0, g0);
                 // FENCE keeps the machine scheduler from sinking a row's LDS reads down to their first
                 // use: the reads of entry j+1 stay in front of the arithmetic of entry j, which hides them.
@@ -676,17 +621,10 @@ __device__ __forceinline__ void sweep_side(const SweepSide &S, double2 *__restri
                 // stored ones (layout: slice_fast), PIN = the matching pin of the next trip's unpacked groups.
                 // MODE: 0 general, 1 the leading ones, 2 the ones-or-twos behind them (gene side only: it defers the logarithm)
 #define VBNMF_ENTRY(MODE, gv, cnt) sweep_entry<R, EV == 3, (MODE) == 1, SP, (MODE) == 2>(T, ldsG, gv, (double)(cnt), LOGTERM); if ((MODE) == 2 && LOGTERM) renorm_product<R>(T); VBNMF_FENCE()
-#if VBNMF_PREFETCH2
-#define VBNMF_TRIP_LOADS const uint4 fc = ld_stream(E + (size_t)min(2 * p + 4, ng - 1) * 64, snt), fd = ld_stream(E + (size_t)min(2 * p + 5, ng - 1) * 64, snt);
-#define VBNMF_TRIP_ROTATE ec = fc; ed = fd;
-#else
-#define VBNMF_TRIP_LOADS const uint4 ec = ld_stream(E + (size_t)min(2 * p + 2, ng - 1) * 64, snt), ed = ld_stream(E + (size_t)min(2 * p + 3, ng - 1) * 64, snt);
-#define VBNMF_TRIP_ROTATE
-#endif
 #define VBNMF_TRIP(MODE, PIN)                                                                     \
                 {                                                                                 \
                     /* the next trip's groups; past the end: the last group again (an odd one is the tail's) */ \
-                    VBNMF_TRIP_LOADS                                                              \
+                    const uint4 ec = ld_stream(E + (size_t)min(2 * p + 2, ng - 1) * 64, snt), ed = ld_stream(E + (size_t)min(2 * p + 3, ng - 1) * 64, snt); \
                     lds_row<R>(ldsG, a.o1, g1); VBNMF_FENCE();                                    \
                     VBNMF_ENTRY(MODE, g0, a.c0);                                                   \
                     lds_row<R>(ldsG, a.o2, g0); VBNMF_FENCE();                                    \
@@ -711,7 +649,6 @@ __device__ __forceinline__ void sweep_side(const SweepSide &S, double2 *__restri
                     if ((MODE) == 1 && LOGTERM) renorm_product<R>(T);                                     \
                     b = unpack4<R>(ed, share);                                                    \
                     PIN(b);                                                                       \
-                    VBNMF_TRIP_ROTATE                                                             \
                 }
                 const int sfast = S.slice_fast[s];
                 const int npf = (EV == 3) ? 0 : min(np, (sfast & 0xFFFF) >> 3);
@@ -733,8 +670,6 @@ __device__ __forceinline__ void sweep_side(const SweepSide &S, double2 *__restri
                 if (LOGTERM && npf2 > 0)                                  // the deferred logarithm of the leading ones and twos
                     T.lsum += fma((double)T.pexp, 6.93147180559945286227e-01, dev_log_tab(T.prod, reinterpret_cast<const LogTabEntry *>(ldsG)));
 #undef VBNMF_TRIP
-#undef VBNMF_TRIP_LOADS
-#undef VBNMF_TRIP_ROTATE
 #undef VBNMF_ENTRY
 #undef VBNMF_FENCE
             } else {
@@ -799,7 +734,7 @@ __device__ __forceinline__ void sweep_side(const SweepSide &S, double2 *__restri
             if (lead) {
                 double2 *P = reinterpret_cast<double2 *>(S.part + ((size_t)s * 64 + tlane) * RT + hp * R);
 #pragma unroll
-                for (int kk = 0; kk < R / 2; kk++) st_part(P + kk, make_double2(T.acc[2 * kk], T.acc[2 * kk + 1]));
+                for (int kk = 0; kk < R / 2; kk++) P[kk] = make_double2(T.acc[2 * kk], T.acc[2 * kk + 1]);
             }
             if (EV == 1 && M != kIdle && lead) {
                 const double2 *L2 = reinterpret_cast<const double2 *>(S.llF + (size_t)M * RT + hp * R);
@@ -861,11 +796,6 @@ __global__ __launch_bounds__(NT) void k_sweep(const SweepSide A, const SweepSide
     if (A.stop && *A.stop) return;               // the driver loop has ended: leave the statistics as they are
     sweep_side<R, WIDE, true, NT, 1, SP>(A, ldsG);      // lanes own genes: statistics sw + the sum x log(wth) (+ rows of column sums)
     sweep_side<R, WIDE, false, NT, 1, SP>(B, ldsG, &A); // lanes own cells: statistics sh (+ the gene side's column sums added up)
-#if VBNMF_END_WB
-    // experiment (profiles/r05_end_wb_ab.txt): every workgroup asks its XCD's L2 to write back when IT is done, so that the
-    // release at the kernel's end -- the 6.5 us between this kernel and the next -- finds little left to write
-    if (threadIdx.x == 0) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-#endif
 }
 
 // The sweeps of a batch of engines (k_update2_batch above): jobs[2 b] = gene side, jobs[2 b + 1] = cell side of engine b.
@@ -919,7 +849,7 @@ __device__ __forceinline__ double task_sum(const double *__restrict__ part, cons
 #pragma unroll
         for (int u = 0; u < NF; u++) id[u] = row_task[min(q + u, q1 - 1)];
 #pragma unroll
-        for (int u = 0; u < NF; u++) v[u] = ld_part(part + (size_t)id[u] * R + k);
+        for (int u = 0; u < NF; u++) v[u] = part[(size_t)id[u] * R + k];
 #pragma unroll
         for (int u = 0; u < NF; u++) s += (q + u < q1) ? v[u] : 0.0;
     }
@@ -936,7 +866,7 @@ __device__ __forceinline__ double task_sum_lds(const double *__restrict__ part, 
     for (int q = q0; q < q1; q += NF) {
         double v[NF];
 #pragma unroll
-        for (int u = 0; u < NF; u++) v[u] = ld_part(part + (size_t)ids[min(q + u, q1 - 1)] * R + k);
+        for (int u = 0; u < NF; u++) v[u] = part[(size_t)ids[min(q + u, q1 - 1)] * R + k];
 #pragma unroll
         for (int u = 0; u < NF; u++) s += (q + u < q1) ? v[u] : 0.0;
     }
@@ -1061,6 +991,155 @@ __device__ unsigned long long g_upd_stamps[2 * kUpdateBlocks * 12];
 #define UPD2_STAMP(i) do { } while (0)
 #endif
 
+// ------------------------------------------------------------------------------------
+// The pieces every update / control kernel shares, each defined once.  The library builds with -ffp-contract=off, so a
+// __forceinline__ function that keeps its order of operations gives the same bits wherever it is inlined: the folded and
+// the stand-alone control steps, the one- and two-launch updates agree bit for bit because they run these bodies.
+// ------------------------------------------------------------------------------------
+// The pinned, device-visible result block of an engine (vbnmf_engine::h_out, ControlFold::out_host): kHostOut doubles.
+constexpr int kHostOut = 16;
+enum HostOutSlot : int {
+    kOutLkh = 0,                   // evidence (VB) / likelihood (ML) of the last step
+    kOutStats = 1,                 // [4] mean log lw, mean log lh, mean ew, mean eh (k_ml_final: sum x log(wh), sum(wh), 0, 0)
+    kOutIt = 5,                    // steps of the device-driven loop so far (payload)
+    kOutReason = 6,                // why the device-driven loop stopped (LoopCtl::reason), 0 while it runs
+    kOutSeq = 7,                   // the flag the host polls: a control step's step count, a host-stepped step's sequence number
+    kOutHyper = 8,                 // [4] hyper-parameters after the control step (VB)
+    kOutLk0 = 12,                  // the lagging evidence / likelihood
+};
+// A control step handed to the host: the payload, a system-scope fence, then the two flags the host polls -- in that order.
+// st, hyper: 4 doubles each, or null (the ML loop publishes neither).
+__device__ __forceinline__ void publish_control_step(double *oh, double lkh, const double *st, const double *hyper, double lk0,
+                                                     int it, int reason)
+{
+    oh[kOutLkh] = lkh;
+    if (st) for (int q = 0; q < 4; q++) { oh[kOutStats + q] = st[q]; oh[kOutHyper + q] = hyper[q]; }
+    oh[kOutLk0] = lk0;
+    oh[kOutIt] = (double)it;
+    __threadfence_system();
+    reinterpret_cast<volatile double *>(oh)[kOutReason] = (double)reason;
+    reinterpret_cast<volatile double *>(oh)[kOutSeq] = (double)it;
+}
+
+// Evidence and the four hyper statistics from the column sums of the two sides' block partials (reference
+// src/vbnmf_update.cpp:78,90): sW, sT = [sum e per k (R) | sum of the prior/entropy terms | sum log l], data = the sweeps'
+// data term, lgx = sum lgamma(x + 1).  st = mean log lw, mean log lh, mean ew, mean eh.
+template <int R>
+__device__ __forceinline__ double vb_evidence(const double *sW, const double *sT, double data, double lgx, int r, double n,
+                                              double m_global, double (&st)[4])
+{
+    double cross = 0.0, sew = 0.0, seh = 0.0;
+    for (int k = 0; k < r; k++) { cross += sW[k] * sT[k]; sew += sW[k]; seh += sT[k]; }
+    const double U = -cross - data - lgx + sW[R] + sT[R];
+    st[0] = sW[R + 1] / (n * r); st[1] = sT[R + 1] / (m_global * r);
+    st[2] = sew / (n * r); st[3] = seh / (m_global * r);
+    return U / (n * m_global);
+}
+
+// The control step of vb_iterate (reference R/bayesian.R:342-348), entered by lanes 0 and 1 of a wave (the two Newton
+// recurrences of hyper_update side by side), from the control block as the previous step left it (read only):
+//   it <- it+1 ; hyper_update if it > n0 and it %% dn == 0 (:342-344; `hyper` is updated in place by lane 0) ; break on NaN (:345) ;
+//   break if it > 1, it > n0, lkh >= lk0 and |1 - lkh/lk0| < Tol (:346-347, lk0 NOT refreshed) ; lk0 <- lkh (:348).
+// Returns the reason (0: go on; lane 1's only says whether the Newton iteration failed); it, lk0: the block's new values.
+__device__ __forceinline__ int vb_control_step(const LoopCtl *pv, double lkh, const double (&st)[4], double *hyper, int lane,
+                                               int &it, double &lk0)
+{
+    int reason = 0;
+    it = pv->it + 1;
+    lk0 = pv->lk0;
+    if (it > pv->n0 && it % pv->dn == 0) {
+        if (dev_hyper_update_pair(pv->flags, st, hyper, lane)) reason = 3;
+    }
+    if (lane == 0 && !reason) {
+        if (lkh != lkh) reason = 1;
+        else if (it > 1 && it > pv->n0 && lkh >= lk0 && fabs(1.0 - lkh / lk0) < pv->tol) reason = 2;
+        else { lk0 = lkh; if (it >= pv->max_it) reason = 4; }
+    }
+    return reason;
+}
+// What thread 0 leaves of a VB control step: the history row it-1 = [lkh, 4 statistics, 4 hyper-parameters after the update]
+// and the host's result block.
+__device__ __forceinline__ void vb_publish(double *history, double *out_host, double lkh, const double (&st)[4],
+                                           const double *hyper, double lk0, int it, int reason)
+{
+    if (history) {
+        double *h = history + (size_t)(it - 1) * 9;
+        h[0] = lkh;
+        for (int q = 0; q < 4; q++) { h[1 + q] = st[q]; h[5 + q] = hyper[q]; }
+    }
+    publish_control_step(out_host, lkh, st, hyper, lk0, it, reason);
+}
+
+// A block's row of block partials travels on unchanged (a step queued past the stop: the tables alternate by launch).
+template <int R>
+__device__ __forceinline__ void carry_bp_row(double *__restrict__ bp, const double *__restrict__ bp_prev)
+{
+    const int t = threadIdx.x;
+    if (t < R + 2) bp[(size_t)blockIdx.x * (R + 2) + t] = bp_prev[(size_t)blockIdx.x * (R + 2) + t];
+}
+
+// Sum over the block's thread rows (thread t = row * R + k, RB = kUpdateThreads / R rows) of N LDS arrays of one value per
+// thread, by a fixed halving tree: row 0 ends with the column sums.  The arrays are complete (a barrier) on entry and on return.
+template <int R, int N>
+__device__ __forceinline__ void block_rows_sum(double *const (&s)[N])
+{
+    constexpr int RB = kUpdateThreads / R;
+    constexpr int P2 = (RB <= 32) ? 32 : (RB <= 64) ? 64 : (RB <= 128) ? 128 : (RB <= 256) ? 256 : 512;
+    const int t = threadIdx.x, row = t / R;
+    for (int h = P2 / 2; h >= 1; h >>= 1) {
+        if (row < h && row + h < RB) {
+#pragma unroll
+            for (int q = 0; q < N; q++) s[q][t] += s[q][t + h * R];
+        }
+        __syncthreads();
+    }
+}
+
+// The block's stretch of the inverse index into LDS (s_ptr: kStagePtr pointers, s_ids: kStageIds task ids), first thing in
+// an update: two dependent global round trips (pointers, then ids) that the prologue's own loads overlap with, instead of
+// two per ROUND of every major's gather.  bm0, bm1: the block's majors; q_lo: the stretch's first id.  False
+// (block-uniform): the stretch does not fit and the gather reads the global index.  (Whether an update stages at all is
+// tested at the call site, in front of the call: with that test handed in as an argument k_update<6, 10, 12, 14> spill
+// three registers that they do not spill otherwise.)
+__device__ __forceinline__ bool stage_block_ids(const int32_t *__restrict__ row_ptr, const uint32_t *__restrict__ row_task,
+                                                int64_t bm0, int64_t bm1, uint32_t *s_ids, int32_t *s_ptr, int &q_lo)
+{
+    const int t = threadIdx.x;
+    bool staged = false;
+    if (bm0 < bm1 && bm1 - bm0 < kStagePtr) {
+        q_lo = row_ptr[bm0];
+        const int q_hi = row_ptr[bm1];
+        staged = q_hi - q_lo <= kStageIds;
+        if (staged) {
+            for (int q = t; q <= (int)(bm1 - bm0); q += kUpdateThreads) s_ptr[q] = row_ptr[bm0 + q];
+            for (int q = q_lo + t; q < q_hi; q += kUpdateThreads) s_ids[q - q_lo] = row_task[q];
+        }
+    }
+    return staged;
+}
+
+// The posterior of one factor element (major, k) at offset o from its gathered statistic s (the formulas above k_update):
+// Gamma shape and rate, mean and variance, geometric mean, the four stores; ve, vt, vl take its contributions to sum e,
+// the sum of the prior/entropy terms and sum log l.  ab = a / b.
+__device__ __forceinline__ void posterior_entry(size_t o, double s, double a, double ab, double be, double lbe, double lga,
+                                                double fudge, double *l, double *ll, double *e, double *d,
+                                                double &ve, double &vt, double &vl)
+{
+    const double al = a + l[o] * s;
+    const double ev = al / be;
+    const double dv = al / be / be;
+    double psi, lgam;
+    dev_psi_lgamma(al, &psi, &lgam);
+    if (!(al > 0.0)) { psi = __builtin_nan(""); lgam = __builtin_nan(""); }
+    const double tmp = exp(psi) / be;
+    const double ln = (tmp > fudge ? tmp : fudge);
+    const double lg = log(ln);
+    ve += ev;
+    vt += -ab * ev + lga + al * (1.0 - lbe) + lgam;
+    vl += lg;
+    l[o] = ln; ll[o] = ln * lg; e[o] = ev; d[o] = dv;
+}
+
 template <int R>
 __global__ __launch_bounds__(kUpdateThreads) void k_update(
     const double *__restrict__ acc, const int32_t *__restrict__ row_ptr, const uint32_t *__restrict__ row_task,
@@ -1077,24 +1156,14 @@ __global__ __launch_bounds__(kUpdateThreads) void k_update(
     int stopped = 0;
     const int t = threadIdx.x;
     UPD_STAMP(0);
-    // The block's stretch of the inverse index into LDS, first thing: two dependent global round trips (pointers, then
-    // ids) that the prologue's own loads overlap with, instead of two per ROUND of every major's gather below.
+    // the block's stretch of the inverse index into LDS, first thing (stage_block_ids)
     const int64_t per0 = (nmaj + gridDim.x - 1) / gridDim.x;
     const int64_t bm0 = (int64_t)blockIdx.x * per0, bm1 = min(nmaj, bm0 + per0);
     int q_lo = 0;
-    bool staged = false;
-    if (stage_ids && row_ptr && !fold.control_only && bm0 < bm1 && bm1 - bm0 < kStagePtr) {
-        q_lo = row_ptr[bm0];
-        const int q_hi = row_ptr[bm1];
-        staged = q_hi - q_lo <= kStageIds;               // (block-uniform)
-        if (staged) {
-            for (int q = t; q <= (int)(bm1 - bm0); q += kUpdateThreads) s_ptr[q] = row_ptr[bm0 + q];
-            for (int q = q_lo + t; q < q_hi; q += kUpdateThreads) s_ids[q - q_lo] = row_task[q];
-        }
-    }
+    const bool staged = stage_ids && row_ptr && !fold.control_only && stage_block_ids(row_ptr, row_task, bm0, bm1, s_ids, s_ptr, q_lo);
     UPD_STAMP(1);
     if (fold.prev) {
-        // ---- the folded control step (see ControlFold; the arithmetic is k_control's, statement by statement) ----
+        // ---- the folded control step (ControlFold): vb_evidence, vb_control_step, vb_publish, from prev to next ----
         __shared__ double sW[R + 2], s_hy[4];
         __shared__ int s_stop;
         const LoopCtl *pv = fold.prev;
@@ -1112,7 +1181,7 @@ __global__ __launch_bounds__(kUpdateThreads) void k_update(
         UPD_STAMP(8);
         if (was_stopped) {                       // a step queued past the stop: the control block and this block's row of the
             if (blockIdx.x == 0 && t == 0) *fold.next = *pv;                  // gene-side partials travel on unchanged
-            if (t < R + 2 && !fold.control_only) bp[(size_t)blockIdx.x * (R + 2) + t] = fold.bpW_prev[(size_t)blockIdx.x * (R + 2) + t];
+            if (!fold.control_only) carry_bp_row<R>(bp, fold.bpW_prev);
             return;
         }
         const double data = block_sum(part, s_e);            // (two barriers: sW, s_other are complete behind it)
@@ -1123,47 +1192,18 @@ __global__ __launch_bounds__(kUpdateThreads) void k_update(
             double lkh = pv->lkh, new_lk0 = pv->lk0;
             double st[4] = {pv->stats[0], pv->stats[1], pv->stats[2], pv->stats[3]};
             if (fold.do_control) {
-                double cross = 0.0, sew = 0.0, seh = 0.0;
-                for (int k = 0; k < r; k++) { cross += sW[k] * s_other[k]; sew += sW[k]; seh += s_other[k]; }
-                const double lgx = fold.lgx_in ? *fold.lgx_in : fold.lgx;
-                const double U = -cross - data - lgx + sW[R] + s_other[R];
-                lkh = U / (fold.n * fold.m_global);
-                st[0] = sW[R + 1] / (fold.n * r); st[1] = s_other[R + 1] / (fold.m_global * r);
-                st[2] = sew / (fold.n * r); st[3] = seh / (fold.m_global * r);
-                it = pv->it + 1;
-                if (it > pv->n0 && it % pv->dn == 0) {
-                    if (dev_hyper_update_pair(pv->flags, st, s_hy, t)) reason = 3;
-                }
-                if (t == 0 && !reason) {
-                    const double lk0 = pv->lk0;
-                    if (lkh != lkh) reason = 1;
-                    else if (it > 1 && it > pv->n0 && lkh >= lk0 && fabs(1.0 - lkh / lk0) < pv->tol) reason = 2;
-                    else { new_lk0 = lkh; if (it >= pv->max_it) reason = 4; }
-                }
+                lkh = vb_evidence<R>(sW, s_other, data, fold.lgx_in ? *fold.lgx_in : fold.lgx, r, fold.n, fold.m_global, st);
+                reason = vb_control_step(pv, lkh, st, s_hy, t, it, new_lk0);
             }
             if (t == 0) {
                 s_stop = reason != 0;
-                if (blockIdx.x == 0) {
+                if (blockIdx.x == 0) {                  // prev -> next: block 0 writes the control block, the history row and the host's block
                     LoopCtl nx = *pv;
                     nx.it = it; nx.lkh = lkh; nx.lk0 = new_lk0;
                     for (int q = 0; q < 4; q++) { nx.stats[q] = st[q]; nx.hyper[q] = s_hy[q]; }
                     if (reason) { nx.reason = reason; nx.stop = 1; }
                     *fold.next = nx;
-                    if (fold.do_control) {
-                        if (fold.history) {
-                            double *h = fold.history + (size_t)(it - 1) * 9;
-                            h[0] = lkh;
-                            for (int q = 0; q < 4; q++) { h[1 + q] = st[q]; h[5 + q] = s_hy[q]; }
-                        }
-                        double *oh = fold.out_host;
-                        oh[0] = lkh;
-                        for (int q = 0; q < 4; q++) { oh[1 + q] = st[q]; oh[8 + q] = s_hy[q]; }
-                        oh[12] = new_lk0;
-                        oh[5] = (double)it;
-                        __threadfence_system();
-                        reinterpret_cast<volatile double *>(oh)[6] = (double)reason;
-                        reinterpret_cast<volatile double *>(oh)[7] = (double)it;
-                    }
+                    if (fold.do_control) vb_publish(fold.history, fold.out_host, lkh, st, s_hy, new_lk0, it, reason);
                 }
             }
         }
@@ -1171,7 +1211,7 @@ __global__ __launch_bounds__(kUpdateThreads) void k_update(
         __syncthreads();
         if (fold.control_only) return;
         if (s_stop) {                            // the loop ends here: no update, the partials' row travels on (as above)
-            if (t < R + 2) bp[(size_t)blockIdx.x * (R + 2) + t] = fold.bpW_prev[(size_t)blockIdx.x * (R + 2) + t];
+            carry_bp_row<R>(bp, fold.bpW_prev);
             return;
         }
         a = s_hy[2 * side]; b = s_hy[2 * side + 1];
@@ -1203,37 +1243,10 @@ __global__ __launch_bounds__(kUpdateThreads) void k_update(
         for (int64_t M = m0 + row; M < m1; M += RB) {
             const size_t o = (size_t)M * R + k;
             if (k < r) {
-#ifdef VBNMF_ABL_NOGATHER                                    /* ablation builds only (profiles/ubench/r04/upd_ablate.sh) */
-                const double s = 1.0 + 1e-9 * (double)k;
-#else
                 const double s = !row_ptr ? acc[o]
                                  : staged ? task_sum_lds(acc, s_ids, s_ptr[M - bm0] - q_lo, s_ptr[M - bm0 + 1] - q_lo, R, k)
                                           : task_sum(acc, row_task, row_ptr[M], row_ptr[M + 1], R, k);
-#endif
-                const double al = a + l[o] * s;
-                const double ev = al / be;
-                const double dv = al / be / be;
-                double psi, lgam;
-#ifdef VBNMF_ABL_NOSPECIAL
-                psi = al * 0.5; lgam = al * 0.25;
-                const double tmp = psi / be;
-                const double ln = (tmp > fudge ? tmp : fudge);
-                const double lg = ln * 0.125;
-#else
-                dev_psi_lgamma(al, &psi, &lgam);
-                if (!(al > 0.0)) { psi = __builtin_nan(""); lgam = __builtin_nan(""); }
-                const double tmp = exp(psi) / be;
-                const double ln = (tmp > fudge ? tmp : fudge);
-                const double lg = log(ln);
-#endif
-                ve += ev;
-                vt += -(a / b) * ev + lga + al * (1.0 - lbe) + lgam;
-                vl += lg;
-#ifdef VBNMF_ABL_NOWRITE
-                if (ln == 123.456) { l[o] = ln; ll[o] = ln * lg; e[o] = ev; d[o] = dv; }
-#else
-                l[o] = ln; ll[o] = ln * lg; st_once(e + o, ev); st_once(d + o, dv);
-#endif
+                posterior_entry(o, s, a, a / b, be, lbe, lga, fudge, l, ll, e, d, ve, vt, vl);
             } else {
                 l[o] = 0.0; ll[o] = 0.0; e[o] = 0.0; d[o] = 0.0;
             }
@@ -1243,11 +1256,8 @@ __global__ __launch_bounds__(kUpdateThreads) void k_update(
     s_e[t] = ve; s_t[t] = vt; s_l[t] = vl;
     __syncthreads();
     UPD_STAMP(5);
-    constexpr int P2 = (RB <= 32) ? 32 : (RB <= 64) ? 64 : (RB <= 128) ? 128 : (RB <= 256) ? 256 : 512;
-    for (int h = P2 / 2; h >= 1; h >>= 1) {
-        if (row < h && row + h < RB) { s_e[t] += s_e[t + h * R]; s_t[t] += s_t[t + h * R]; s_l[t] += s_l[t + h * R]; }
-        __syncthreads();
-    }
+    double *const red[3] = {s_e, s_t, s_l};
+    block_rows_sum<R, 3>(red);
     UPD_STAMP(6);
     double *o = bp + (size_t)blockIdx.x * (R + 2);
     if (t < R) o[t] = s_e[t];
@@ -1303,7 +1313,7 @@ constexpr int kUpdTabWords = 16384;        // LDS copy of a block's row of the t
 
 
 // The visits of one thread row to the majors of one side (the row's list holds its genes first, then its cells): column k
-// of every visited major -- gather of the task partials, Gamma posterior, geometric mean, evidence terms (k_update's body).
+// of every visited major -- gather of the task partials, then posterior_entry.
 template <int R>
 __device__ __forceinline__ int posterior_visits(const UpdSide &S, int64_t m0, const uint32_t *vis, int v, int V, uint32_t side,
                                                 const uint32_t *ids, int k, int r, double a, double ab, double be, double lbe,
@@ -1317,19 +1327,7 @@ __device__ __forceinline__ int posterior_visits(const UpdSide &S, int64_t m0, co
         const size_t o = (size_t)M * R + k;
         if (k < r) {
             const double s = task_sum_lds(S.part, ids, q0, q1, R, k);
-            const double al = a + S.l[o] * s;
-            const double ev = al / be;
-            const double dv = al / be / be;
-            double psi, lgam;
-            dev_psi_lgamma(al, &psi, &lgam);
-            if (!(al > 0.0)) { psi = __builtin_nan(""); lgam = __builtin_nan(""); }
-            const double tmp = exp(psi) / be;
-            const double ln = (tmp > fudge ? tmp : fudge);
-            const double lg = log(ln);
-            ve += ev;
-            vt += -ab * ev + lga + al * (1.0 - lbe) + lgam;
-            vl += lg;
-            S.l[o] = ln; S.ll[o] = ln * lg; st_once(S.e + o, ev); st_once(S.d + o, dv);
+            posterior_entry(o, s, a, ab, be, lbe, lga, fudge, S.l, S.ll, S.e, S.d, ve, vt, vl);
         } else {
             S.l[o] = 0.0; S.ll[o] = 0.0; S.e[o] = 0.0; S.d[o] = 0.0;
         }
@@ -1362,7 +1360,7 @@ __device__ __forceinline__ void update2_body(
     int stopped = 0;
     UPD2_STAMP(1);
     if (fold.prev) {
-        // ---- the folded control step (k_update's, statement by statement; the cell side's sums come from H.bp_prev) ----
+        // ---- the folded control step (as k_update's; the cell side's sums come from H.bp_prev) ----
         const LoopCtl *pv = fold.prev;
         const int was_stopped = pv->stop;
         double part = 0.0;
@@ -1371,72 +1369,40 @@ __device__ __forceinline__ void update2_body(
         UPD2_STAMP(8);
         if (was_stopped) {                       // a step queued past the stop: the control block and both partial tables travel on
             if (blockIdx.x == 0 && t == 0) *fold.next = *pv;
-            if (t < R + 2) {
-                W.bp[(size_t)blockIdx.x * (R + 2) + t] = W.bp_prev[(size_t)blockIdx.x * (R + 2) + t];
-                H.bp[(size_t)blockIdx.x * (R + 2) + t] = H.bp_prev[(size_t)blockIdx.x * (R + 2) + t];
-            }
+            carry_bp_row<R>(W.bp, W.bp_prev);
+            carry_bp_row<R>(H.bp, H.bp_prev);
             return;
         }
 #pragma unroll
         for (int u = 0; u < 4; u++) { const int q = t + u * kUpdateThreads; if (q < T.stride4) s_tab4[q] = tb[u]; }
         const double data = block_sum(part, s_red[0]);       // (two barriers: sW, s_other, s_cs and the table are complete behind it)
         UPD2_STAMP(9);
-        if (t < 2) {
+        if (t < 2) {                              // lanes 0 and 1: the two Newton recurrences of hyper_update side by side
             if (t == 0) for (int q = 0; q < 4; q++) s_hy[q] = pv->hyper[q];
             int reason = 0, it = pv->it;
             double lkh = pv->lkh, new_lk0 = pv->lk0;
             double st[4] = {pv->stats[0], pv->stats[1], pv->stats[2], pv->stats[3]};
             if (fold.do_control) {
-                double cross = 0.0, sew = 0.0, seh = 0.0;
-                for (int k = 0; k < r; k++) { cross += sW[k] * s_other[k]; sew += sW[k]; seh += s_other[k]; }
-                const double U = -cross - data - fold.lgx + sW[R] + s_other[R];
-                lkh = U / (fold.n * fold.m_global);
-                st[0] = sW[R + 1] / (fold.n * r); st[1] = s_other[R + 1] / (fold.m_global * r);
-                st[2] = sew / (fold.n * r); st[3] = seh / (fold.m_global * r);
-                it = pv->it + 1;
-                if (it > pv->n0 && it % pv->dn == 0) {
-                    if (dev_hyper_update_pair(pv->flags, st, s_hy, t)) reason = 3;
-                }
-                if (t == 0 && !reason) {
-                    const double lk0 = pv->lk0;
-                    if (lkh != lkh) reason = 1;
-                    else if (it > 1 && it > pv->n0 && lkh >= lk0 && fabs(1.0 - lkh / lk0) < pv->tol) reason = 2;
-                    else { new_lk0 = lkh; if (it >= pv->max_it) reason = 4; }
-                }
+                lkh = vb_evidence<R>(sW, s_other, data, fold.lgx, r, fold.n, fold.m_global, st);
+                reason = vb_control_step(pv, lkh, st, s_hy, t, it, new_lk0);
             }
             if (t == 0) {
                 s_stop = reason != 0;
-                if (blockIdx.x == 0) {
+                if (blockIdx.x == 0) {                  // prev -> next: block 0 writes the control block, the history row and the host's block
                     LoopCtl nx = *pv;
                     nx.it = it; nx.lkh = lkh; nx.lk0 = new_lk0;
                     for (int q = 0; q < 4; q++) { nx.stats[q] = st[q]; nx.hyper[q] = s_hy[q]; }
                     if (reason) { nx.reason = reason; nx.stop = 1; }
                     *fold.next = nx;
-                    if (fold.do_control) {
-                        if (fold.history) {
-                            double *h = fold.history + (size_t)(it - 1) * 9;
-                            h[0] = lkh;
-                            for (int q = 0; q < 4; q++) { h[1 + q] = st[q]; h[5 + q] = s_hy[q]; }
-                        }
-                        double *oh = fold.out_host;
-                        oh[0] = lkh;
-                        for (int q = 0; q < 4; q++) { oh[1 + q] = st[q]; oh[8 + q] = s_hy[q]; }
-                        oh[12] = new_lk0;
-                        oh[5] = (double)it;
-                        __threadfence_system();
-                        reinterpret_cast<volatile double *>(oh)[6] = (double)reason;
-                        reinterpret_cast<volatile double *>(oh)[7] = (double)it;
-                    }
+                    if (fold.do_control) vb_publish(fold.history, fold.out_host, lkh, st, s_hy, new_lk0, it, reason);
                 }
             }
         }
         UPD2_STAMP(10);
         __syncthreads();
         if (s_stop) {                            // the loop ends here: no update, the partials' rows travel on (as above)
-            if (t < R + 2) {
-                W.bp[(size_t)blockIdx.x * (R + 2) + t] = W.bp_prev[(size_t)blockIdx.x * (R + 2) + t];
-                H.bp[(size_t)blockIdx.x * (R + 2) + t] = H.bp_prev[(size_t)blockIdx.x * (R + 2) + t];
-            }
+            carry_bp_row<R>(W.bp, W.bp_prev);
+            carry_bp_row<R>(H.bp, H.bp_prev);
             return;
         }
         aw = s_hy[0]; bw = s_hy[1]; ah = s_hy[2]; bh = s_hy[3];
@@ -1447,10 +1413,8 @@ __device__ __forceinline__ void update2_body(
         }
         bp_colsums3(nullptr, H.bp_prev, nb, R + 2, csum, ncs, R, nullptr, s_other, s_cs, kUpdateThreads);
         if (stopped) {                           // (both tables alternate by launch: the rows travel on)
-            if (t < R + 2) {
-                W.bp[(size_t)blockIdx.x * (R + 2) + t] = W.bp_prev[(size_t)blockIdx.x * (R + 2) + t];
-                H.bp[(size_t)blockIdx.x * (R + 2) + t] = H.bp_prev[(size_t)blockIdx.x * (R + 2) + t];
-            }
+            carry_bp_row<R>(W.bp, W.bp_prev);
+            carry_bp_row<R>(H.bp, H.bp_prev);
             return;
         }
 #pragma unroll
@@ -1486,14 +1450,8 @@ __device__ __forceinline__ void update2_body(
     for (int q = 0; q < 6; q++) s_red[q][t] = acc6[q];
     __syncthreads();
     UPD2_STAMP(5);
-    constexpr int P2 = (RB <= 32) ? 32 : (RB <= 64) ? 64 : (RB <= 128) ? 128 : (RB <= 256) ? 256 : 512;
-    for (int h = P2 / 2; h >= 1; h >>= 1) {
-        if (row < h && row + h < RB) {
-#pragma unroll
-            for (int q = 0; q < 6; q++) s_red[q][t] += s_red[q][t + h * R];
-        }
-        __syncthreads();
-    }
+    double *const red[6] = {s_red[0], s_red[1], s_red[2], s_red[3], s_red[4], s_red[5]};
+    block_rows_sum<R, 6>(red);
     UPD2_STAMP(6);
     double *oW = W.bp + (size_t)blockIdx.x * (R + 2), *oH = H.bp + (size_t)blockIdx.x * (R + 2);
     if (t < R) { oW[t] = s_red[0][t]; oH[t] = s_red[3][t]; }
@@ -1565,11 +1523,8 @@ __global__ __launch_bounds__(kUpdateThreads) void k_prime(int64_t nmaj, int r, c
     }
     s_e[t] = ve;
     __syncthreads();
-    constexpr int P2 = (RB <= 32) ? 32 : (RB <= 64) ? 64 : (RB <= 128) ? 128 : (RB <= 256) ? 256 : 512;
-    for (int h = P2 / 2; h >= 1; h >>= 1) {
-        if (row < h && row + h < RB) s_e[t] += s_e[t + h * R];
-        __syncthreads();
-    }
+    double *const red[1] = {s_e};
+    block_rows_sum<R, 1>(red);
     double *o = bp + (size_t)blockIdx.x * (R + 2);
     if (t < R) o[t] = s_e[t];
     if (t == 0) { o[R] = 0.0; o[R + 1] = 0.0; }
@@ -1579,7 +1534,7 @@ __global__ __launch_bounds__(kUpdateThreads) void k_prime(int64_t nmaj, int r, c
 //   W side : colSum(ew)_k, sum W-terms, sum log lw  = column sums of bpW (replicated in every partition)
 //   tail   : as k_tail writes it; either given (summed over partitions by the caller) or, when
 //            tail == nullptr, formed here from bpH / epart / lgx (single-GPU path, no extra launch).
-//   out    : lkh, mean log lw, mean log lh, mean ew, mean eh, then out[7] = seq (the host polls it).
+//   out    : lkh, mean log lw, mean log lh, mean ew, mean eh (kOutLkh, kOutStats), then out_host[kOutSeq] = seq (the host polls it).
 template <int R>
 __global__ __launch_bounds__(1024) void k_final(const double *__restrict__ bpW, int nbW, const double *__restrict__ tail_in,
                                                 const double *__restrict__ bpH, int nbH,
@@ -1602,18 +1557,12 @@ __global__ __launch_bounds__(1024) void k_final(const double *__restrict__ bpW, 
         __syncthreads();
     }
     if (threadIdx.x == 0) {
-        double cross = 0.0, sew = 0.0, seh = 0.0;
-        for (int k = 0; k < r; k++) { cross += sW[k] * sT[k]; sew += sW[k]; seh += sT[k]; }
-        const double U = -cross - sT[R + 2] - sT[R + 3] + sW[R] + sT[R];
-        double o[5];
-        o[0] = U / (n * m_global);
-        o[1] = sW[R + 1] / (n * r);
-        o[2] = sT[R + 1] / (m_global * r);
-        o[3] = sew / (n * r);
-        o[4] = seh / (m_global * r);
-        for (int q = 0; q < 5; q++) { out[q] = o[q]; out_host[q] = o[q]; }
+        double st[4];
+        const double lkh = vb_evidence<R>(sW, sT, sT[R + 2], sT[R + 3], r, n, m_global, st);
+        out[kOutLkh] = lkh; out_host[kOutLkh] = lkh;
+        for (int q = 0; q < 4; q++) { out[kOutStats + q] = st[q]; out_host[kOutStats + q] = st[q]; }
         __threadfence_system();
-        reinterpret_cast<volatile double *>(out_host)[7] = seq;
+        reinterpret_cast<volatile double *>(out_host)[kOutSeq] = seq;
     }
 }
 
@@ -1621,10 +1570,8 @@ __global__ __launch_bounds__(1024) void k_final(const double *__restrict__ bpW, 
 // Device-resident driver loop: hyper_update (reference R/bayesian.R:2-53; hyper.h: dev_hyper_update_pair) and the loop
 // control of vb_iterate (R/bayesian.R:342-348) after each step, by one thread.
 // ------------------------------------------------------------------------------------
-// One block after each sweep of a device-driven loop: the reductions of k_final, then
-//   it <- it+1 ; hyper_update if it > n0 and it %% dn == 0 (:342-344) ; break on NaN (:345) ;
-//   break if it > 1, it > n0, lkh >= lk0 and |1 - lkh/lk0| < Tol (:346-347, lk0 NOT refreshed) ; lk0 <- lkh (:348).
-// history row it-1 = [lkh, 4 statistics, 4 hyper-parameters after the update]; out_host = [lkh, 4 stats, it, reason, it].
+// One block after each sweep of a device-driven loop: the reductions of k_final, then vb_evidence, vb_control_step and
+// vb_publish on the control block in place (the updates' fold runs the same three from prev to next).
 // Cell-partitioned engines hand in the all-reduced pieces instead: tail_in = [rowSum(eh)_k | sum H-terms | sum log lh]
 // (R + 2 doubles) and small_in = [data term | sum lgamma(x+1)], both summed over the partitions; bpW is replicated.
 template <int R>
@@ -1653,38 +1600,15 @@ __global__ __launch_bounds__(1024) void k_control(const double *__restrict__ bpW
     }
     const int lane = threadIdx.x;
     if (lane > 1) return;                        // lanes 0 and 1 go on (the two Newton recurrences of hyper_update)
-    double cross = 0.0, sew = 0.0, seh = 0.0;
-    for (int k = 0; k < r; k++) { cross += sW[k] * sT[k]; sew += sW[k]; seh += sT[k]; }
-    const double U = -cross - data - lgx + sW[R] + sT[R];
-    const double lkh = U / (n * m_global);
-    double st[4] = {sW[R + 1] / (n * r), sT[R + 1] / (m_global * r), sew / (n * r), seh / (m_global * r)};
-    const int it = ctl->it + 1;
-    int reason = 0;
-    if (it > ctl->n0 && it % ctl->dn == 0) {
-        if (dev_hyper_update_pair(ctl->flags, st, ctl->hyper, lane)) reason = 3;
-    }
+    double st[4], lk0;
+    int it;
+    const double lkh = vb_evidence<R>(sW, sT, data, lgx, r, n, m_global, st);
+    const int reason = vb_control_step(ctl, lkh, st, ctl->hyper, lane, it, lk0);
     if (lane != 0) return;
-    const double lk0 = ctl->lk0;
-    if (!reason) {
-        if (lkh != lkh) reason = 1;
-        else if (it > 1 && it > ctl->n0 && lkh >= lk0 && fabs(1.0 - lkh / lk0) < ctl->tol) reason = 2;
-        else { ctl->lk0 = lkh; if (it >= ctl->max_it) reason = 4; }
-    }
-    ctl->it = it; ctl->lkh = lkh;
+    ctl->lk0 = lk0; ctl->it = it; ctl->lkh = lkh;           // the control block is updated in place
     for (int q = 0; q < 4; q++) ctl->stats[q] = st[q];
-    if (history) {
-        double *h = history + (size_t)(it - 1) * 9;
-        h[0] = lkh;
-        for (int q = 0; q < 4; q++) { h[1 + q] = st[q]; h[5 + q] = ctl->hyper[q]; }
-    }
     if (reason) { ctl->reason = reason; ctl->stop = 1; }
-    out_host[0] = lkh;
-    for (int q = 0; q < 4; q++) { out_host[1 + q] = st[q]; out_host[8 + q] = ctl->hyper[q]; }
-    out_host[12] = ctl->lk0;
-    out_host[5] = (double)it;
-    __threadfence_system();
-    reinterpret_cast<volatile double *>(out_host)[6] = (double)reason;
-    reinterpret_cast<volatile double *>(out_host)[7] = (double)it;
+    vb_publish(history, out_host, lkh, st, ctl->hyper, lk0, it, reason);
 }
 
 }  // namespace vbnmf

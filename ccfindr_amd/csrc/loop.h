@@ -59,9 +59,9 @@ int drive_loop(vbnmf_engine *const *engs, int polled, bool replicated, int max_i
         all_stopped = true;
         for (int p = 0; p < polled; p++) {
             volatile double *ho = engs[p]->h_out;
-            const bool stopped = ho[6] != 0.0;
+            const bool stopped = ho[kOutReason] != 0.0;
             all_stopped = all_stopped && stopped;
-            ok = ok && (stopped || (int)ho[7] >= target);
+            ok = ok && (stopped || (int)ho[kOutSeq] >= target);
         }
         return ok;
     };
@@ -98,13 +98,13 @@ int drive_loop(vbnmf_engine *const *engs, int polled, bool replicated, int max_i
                 if (waited > limit) {
                     e0->poisoned = true;
                     return fail(VBNMF_ERR_HIP, "timed out after %.1f s (VBNMF_WAIT_TIMEOUT_S) waiting for step %d of the device-driven loop; "
-                                "the last completed step is %d (%d queued)", waited, target, (int)e0->h_out[7], queued);
+                                "the last completed step is %d (%d queued)", waited, target, (int)e0->h_out[kOutSeq], queued);
                 }
                 if (int rc = idle_check(target)) return rc;
             }
         }
         volatile double *ho = e0->h_out;
-        if (replicated ? ho[6] != 0.0 && (int)ho[5] <= target : all_stopped) break;
+        if (replicated ? ho[kOutReason] != 0.0 && (int)ho[kOutIt] <= target : all_stopped) break;
         if (target >= max_it) break;
         if (int rc = queue_batch()) return rc;
     }
@@ -135,7 +135,7 @@ struct RunScope {
             launch_ctl_init(x->stream, x->fold && !plain_ctl ? x->ctl2 : x->ctl, ctl(p));
             x->fold_step = 0;
             volatile double *ho = x->h_out;
-            ho[5] = 0.0; ho[6] = 0.0; ho[7] = 0.0;
+            ho[kOutIt] = 0.0; ho[kOutReason] = 0.0; ho[kOutSeq] = 0.0;
             x->run_active = true;
         }
         hipError_t he = hipGetLastError();
@@ -162,7 +162,7 @@ struct RunScope {
             x->stream = own[p];
             x->run_active = false; x->timing = timing[p];
             x->stop_ptr = nullptr;
-            x->seq = 0.0; x->h_out[7] = 0.0;                       // the step path's sequence flag restarts
+            x->seq = 0.0; x->h_out[kOutSeq] = 0.0;                       // the step path's sequence flag restarts
         }
         return rc;
     }

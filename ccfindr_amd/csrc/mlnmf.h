@@ -84,6 +84,37 @@ __device__ __forceinline__ int conn_decide(const MlConn &cn, int it, int max_it,
     return it >= max_it ? 4 : 0;
 }
 
+// Likelihood (R/factorize.R:40-49) from colSums(w), rowSums(h) (sW, sH), data = sum x log(wh) and the constant xlx of X;
+// cross = sum(wh).
+__device__ __forceinline__ double ml_likelihood(const double *sW, const double *sH, double data, double xlx, int r, double n,
+                                                double m, double &cross)
+{
+    cross = 0.0;
+    for (int k = 0; k < r; k++) cross += sW[k] * sH[k];
+    return ((data - cross) + xlx) / n / m;
+}
+
+// The control step of factorize()'s loop (R/factorize.R:194-213), by the thread that writes the control block, from the
+// block as the previous step left it (read only): the likelihood, it <- it + 1, then under criterion = 'connectivity' the
+// labels' rule (conn_decide; counted: the changed pairs, read only then; write: this thread records them) and under
+// 'likelihood' `if (abs(lkold - lk0) < Tol * abs(lkold)) break ; lkold <- lk0` (:211-213; lkold starts at -Inf, so the
+// first pass never breaks; a NaN likelihood never satisfies the test either).  Returns the reason (0: go on); lk, it,
+// lk0 (lkold), zstep: the block's new values.
+__device__ __forceinline__ int ml_control_step(const LoopCtl *pv, const double *sW, const double *sH, double data, double xlx, int r,
+                                               double n, double m, const MlConn &cn, const unsigned long long *counted, bool write,
+                                               double &lk, int &it, double &lk0, int &zstep)
+{
+    double cross;
+    lk = ml_likelihood(sW, sH, data, xlx, r, n, m, cross);
+    it = pv->it + 1;
+    const double lkold = pv->lk0;
+    lk0 = lkold; zstep = pv->zstep;
+    if (cn.ids_out) { lk0 = lk; return conn_decide(cn, it, pv->max_it, pv->ncnn_step, *counted, zstep, write); }
+    if (fabs(lkold - lk) < pv->tol * fabs(lkold)) return 2;               // converged (:211)
+    lk0 = lk;
+    return it >= pv->max_it ? 4 : 0;
+}
+
 struct MlFold {
     const LoopCtl *prev;           // null: no fold
     LoopCtl *next;
@@ -117,22 +148,13 @@ __device__ __forceinline__ void ml_update_body(
     // over a gene's tasks AND over the partitions -- the reduce buffer behind the all-reduce, [nmaj][R] -- and other_bp is ONE
     // row, its reduced tail rowSums(h_new) of all cells.  No inverse index: nothing to stage, no further LDS.
     const bool dense = row_ptr == nullptr;               // (uniform over the launch)
-    // the block's stretch of the inverse index into LDS, first thing (as k_update, kernels.h)
+    // the block's stretch of the inverse index into LDS, first thing (kernels.h: stage_block_ids)
     const int64_t per0 = (nmaj + gridDim.x - 1) / gridDim.x;
     const int64_t bm0 = (int64_t)blockIdx.x * per0, bm1 = min(nmaj, bm0 + per0);
     int q_lo = 0;
-    bool staged = false;
-    if (stage_ids && !dense && !fold.control_only && bm0 < bm1 && bm1 - bm0 < kStagePtr) {
-        q_lo = row_ptr[bm0];
-        const int q_hi = row_ptr[bm1];
-        staged = q_hi - q_lo <= kStageIds;               // (block-uniform)
-        if (staged) {
-            for (int q = t; q <= (int)(bm1 - bm0); q += kUpdateThreads) s_ptr[q] = row_ptr[bm0 + q];
-            for (int q = q_lo + t; q < q_hi; q += kUpdateThreads) s_ids[q - q_lo] = row_task[q];
-        }
-    }
+    const bool staged = stage_ids && !dense && !fold.control_only && stage_block_ids(row_ptr, row_task, bm0, bm1, s_ids, s_ptr, q_lo);
     if (fold.prev) {
-        // ---- the folded control step: k_ml_control's arithmetic, statement by statement ----
+        // ---- the folded control step (ml_control_step, from prev to next) ----
         __shared__ double sH[R + 2];
         __shared__ int s_stop;
         const LoopCtl *pv = fold.prev;
@@ -142,7 +164,7 @@ __device__ __forceinline__ void ml_update_body(
         bp_colsums2(other_bp, fold.bpH_prev, other_nb, R + 2, s_other, sH, kUpdateThreads);   // colSums(w) (this update's `down`), colSums(h)
         if (was_stopped) {                       // a step queued past the stop: everything travels on unchanged
             if (blockIdx.x == 0 && t == 0) *fold.next = *pv;
-            if (t < R + 2 && !fold.control_only) bp[(size_t)blockIdx.x * (R + 2) + t] = fold.bpH_prev[(size_t)blockIdx.x * (R + 2) + t];
+            if (!fold.control_only) carry_bp_row<R>(bp, fold.bpH_prev);
             return;
         }
         __shared__ unsigned long long s_nch;
@@ -152,16 +174,9 @@ __device__ __forceinline__ void ml_update_body(
         if (t == 0) {
             int reason = 0, it = pv->it, zstep = pv->zstep;
             double lk = pv->lkh, new_lk0 = pv->lk0;
-            if (fold.do_control) {
-                double cross = 0.0;
-                for (int k = 0; k < r; k++) cross += s_other[k] * sH[k];
-                lk = ((data - cross) + fold.xlx) / fold.n / fold.m;
-                it = pv->it + 1;
-                const double lkold = pv->lk0;
-                if (conn) { new_lk0 = lk; reason = conn_decide(fold.cn, it, pv->max_it, pv->ncnn_step, s_nch, zstep, blockIdx.x == 0); }
-                else if (fabs(lkold - lk) < pv->tol * fabs(lkold)) reason = 2;      // converged (R/factorize.R:211)
-                else { new_lk0 = lk; if (it >= pv->max_it) reason = 4; }
-            }
+            if (fold.do_control)
+                reason = ml_control_step(pv, s_other, sH, data, fold.xlx, r, fold.n, fold.m, fold.cn, &s_nch, blockIdx.x == 0,
+                                         lk, it, new_lk0, zstep);
             s_stop = reason != 0;
             if (blockIdx.x == 0) {
                 LoopCtl nx = *pv;
@@ -170,20 +185,14 @@ __device__ __forceinline__ void ml_update_body(
                 *fold.next = nx;
                 if (fold.do_control) {
                     if (fold.history) fold.history[it - 1] = lk;
-                    double *oh = fold.out_host;
-                    oh[0] = lk;
-                    oh[12] = new_lk0;
-                    oh[5] = (double)it;
-                    __threadfence_system();
-                    reinterpret_cast<volatile double *>(oh)[6] = (double)reason;
-                    reinterpret_cast<volatile double *>(oh)[7] = (double)it;
+                    publish_control_step(fold.out_host, lk, nullptr, nullptr, new_lk0, it, reason);
                 }
             }
         }
         __syncthreads();
         if (fold.control_only) return;
         if (s_stop) {
-            if (t < R + 2) bp[(size_t)blockIdx.x * (R + 2) + t] = fold.bpH_prev[(size_t)blockIdx.x * (R + 2) + t];
+            carry_bp_row<R>(bp, fold.bpH_prev);
             return;
         }
     } else {
@@ -276,11 +285,8 @@ __device__ __forceinline__ void ml_update_body(
     }
     s_e[t] = ve;
     __syncthreads();
-    constexpr int P2 = (RB <= 32) ? 32 : (RB <= 64) ? 64 : (RB <= 128) ? 128 : (RB <= 256) ? 256 : 512;
-    for (int h = P2 / 2; h >= 1; h >>= 1) {
-        if (row < h && row + h < RB) s_e[t] += s_e[t + h * R];
-        __syncthreads();
-    }
+    double *const red[1] = {s_e};
+    block_rows_sum<R, 1>(red);
     double *o = bp + (size_t)blockIdx.x * (R + 2);
     if (t < R) o[t] = s_e[t];
     if (t == 0) { o[R] = 0.0; o[R + 1] = 0.0; }
@@ -327,7 +333,7 @@ __global__ __launch_bounds__(NT) void k_sweep1_batch(const SweepSide *__restrict
     sweep_side<R, WIDE, LOGTERM, NT, LOGTERM ? 2 : 0, 1>(S, ldsG);
 }
 
-// Likelihood (R/factorize.R:40-49).  One block.  out = [lk, sum x log(wh), sum(wh), 0, 0], out_host[7] = seq.
+// Likelihood (R/factorize.R:40-49).  One block.  out = [lk, sum x log(wh), sum(wh), 0, 0], out_host[kOutSeq] = seq.
 // Cell-partitioned engines (tail != null): rowSums(h), the data term and the constant arrive summed over the partitions --
 // tail = [rowSums(h)_k (R) | . | . | sum x log(wh) | sum_{x>0}(-x log x + x)], k_tail's shape behind the all-reduce -- and
 // colSums(w) from bpW, which is replicated; m is then the GLOBAL cell count.
@@ -351,19 +357,18 @@ __global__ __launch_bounds__(1024) void k_ml_final(const double *__restrict__ bp
     double data = block_sum(part, sm);           // (its barriers also publish sW / sH)
     if (tail) data = tail[R + 2];
     if (threadIdx.x == 0) {
-        double cross = 0.0;
-        for (int k = 0; k < r; k++) cross += sW[k] * sH[k];
-        double o[5] = {((data - cross) + xlx) / n / m, data, cross, 0.0, 0.0};
-        for (int q = 0; q < 5; q++) { out[q] = o[q]; out_host[q] = o[q]; }
+        double cross;
+        const double lk = ml_likelihood(sW, sH, data, xlx, r, n, m, cross);
+        const double st[4] = {data, cross, 0.0, 0.0};
+        out[kOutLkh] = lk; out_host[kOutLkh] = lk;
+        for (int q = 0; q < 4; q++) { out[kOutStats + q] = st[q]; out_host[kOutStats + q] = st[q]; }
         __threadfence_system();
-        reinterpret_cast<volatile double *>(out_host)[7] = seq;
+        reinterpret_cast<volatile double *>(out_host)[kOutSeq] = seq;
     }
 }
 
-// Device-driven loop of factorize() under criterion = 'likelihood' (R/factorize.R:194-213): after each step the
-// likelihood, then `if (abs(lkold - lk0) < Tol * abs(lkold)) break ; lkold <- lk0` (:211-213; lkold starts at -Inf, so
-// the first pass never breaks; a NaN likelihood never satisfies the test either, as in R's host loop mirror).
-// LoopCtl: lk0 holds lkold, lkh the last likelihood.  history[it-1] = lk.  out_host = [lk, ., ., ., ., it, reason, it].
+// Device-driven loop of factorize() (R/factorize.R:194-213): after each step ml_control_step on the control block in place.
+// LoopCtl: lk0 holds lkold, lkh the last likelihood.  history[it-1] = lk.  The host's block: publish_control_step.
 template <int R>
 __global__ __launch_bounds__(1024) void k_ml_control(const double *__restrict__ bpW, const double *__restrict__ bpH, int nb,
                                                      const double *__restrict__ epart, int64_t nepart, double xlx, int r,
@@ -396,29 +401,13 @@ __global__ __launch_bounds__(1024) void k_ml_control(const double *__restrict__ 
     double data = block_sum(part, sm);           // (its barriers also publish sW / sH)
     if (tail) { data = small[0]; xlx = small[1]; }
     if (threadIdx.x != 0) return;
-    double cross = 0.0;
-    for (int k = 0; k < r; k++) cross += sW[k] * sH[k];
-    const double lk = ((data - cross) + xlx) / n / m;
-    const int it = ctl->it + 1;
-    const double lkold = ctl->lk0;
-    int reason = 0;
-    if (cn.ids_out) {
-        int zstep = ctl->zstep;
-        ctl->lk0 = lk;
-        reason = conn_decide(cn, it, ctl->max_it, ctl->ncnn_step, s_nch, zstep, true);
-        ctl->zstep = zstep;
-    }
-    else if (fabs(lkold - lk) < ctl->tol * fabs(lkold)) reason = 2;      // converged (:211)
-    else { ctl->lk0 = lk; if (it >= ctl->max_it) reason = 4; }
-    ctl->it = it; ctl->lkh = lk;
+    double lk, lk0;
+    int it, zstep;
+    const int reason = ml_control_step(ctl, sW, sH, data, xlx, r, n, m, cn, &s_nch, true, lk, it, lk0, zstep);
+    ctl->lk0 = lk0; ctl->zstep = zstep; ctl->it = it; ctl->lkh = lk;      // the control block is updated in place
     if (history) history[it - 1] = lk;
     if (reason) { ctl->reason = reason; ctl->stop = 1; }
-    out_host[0] = lk;
-    out_host[12] = ctl->lk0;
-    out_host[5] = (double)it;
-    __threadfence_system();
-    reinterpret_cast<volatile double *>(out_host)[6] = (double)reason;
-    reinterpret_cast<volatile double *>(out_host)[7] = (double)it;
+    publish_control_step(out_host, lk, nullptr, nullptr, lk0, it, reason);
 }
 
 // The second exchange of a cell-partitioned step under criterion = 'connectivity' (one block; k_tail_data's two doubles, kernels.h,

@@ -146,7 +146,7 @@ void conn_finish(vbnmf_engine *const *engs, int count, int64_t *changes, int64_t
 {
     for (int b = 0; b < count; b++) {
         vbnmf_engine *e = engs[b];
-        const int it = (int)e->h_out[5];
+        const int it = (int)e->h_out[kOutIt];
         e->ids_cur = it & 1;
         e->ids_valid = it >= 1;
         if (changes && it > 0) std::memcpy(changes + (size_t)b * changes_rows, e->h_hist + e->chg_off, (size_t)it * sizeof(int64_t));
@@ -215,7 +215,7 @@ int vbnmf_engine_ml_likelihood(vbnmf_engine *e, double *lk)
 {
     if (!e || !lk) return fail(VBNMF_ERR_BAD_ARG, "NULL argument");
     if (!e->ml_ready) return fail(VBNMF_ERR_STATE, "ml_likelihood before ml_set_state");
-    *lk = e->h_out[0];                               // left there by the last k_ml_final (set_state or step)
+    *lk = e->h_out[kOutLkh];                               // left there by the last k_ml_final (set_state or step)
     return VBNMF_OK;
 }
 
@@ -235,7 +235,7 @@ int vbnmf_engine_ml_step(vbnmf_engine *e, int32_t prior, double gamma_a, double 
     if (int rc = launch_ml_final(e)) return rc;
     if (int rc = wait_result(e)) return rc;
     if (int rc = harvest_timing(e)) return rc;
-    if (lk) *lk = e->h_out[0];
+    if (lk) *lk = e->h_out[kOutLkh];
     return VBNMF_OK;
 }
 
@@ -277,7 +277,7 @@ int vbnmf_engine_ml_step_finish(vbnmf_engine *e, double *lk)
     if (int rc = wait_result(e)) return rc;
     e->ml_phase = 0;
     if (int rc = harvest_timing(e)) return rc;
-    if (lk) *lk = e->h_out[0];
+    if (lk) *lk = e->h_out[kOutLkh];
     return VBNMF_OK;
 }
 
@@ -464,9 +464,9 @@ int ml_run_group(const LoopGroup &G, int32_t prior, double gamma_a, double gamma
     if (G.comm) for (int p = 0; p < G.count; p++) G.e[p]->red_in = nullptr;
     if (rc) return rc;
     for (int p = 1; p < G.count; p++)                              // (replicated decisions: anything else is a broken exchange)
-        if (G.e[p]->h_out[5] != e->h_out[5] || G.e[p]->h_out[6] != e->h_out[6])
+        if (G.e[p]->h_out[kOutIt] != e->h_out[kOutIt] || G.e[p]->h_out[kOutReason] != e->h_out[kOutReason])
             return fail(VBNMF_ERR_STATE, "partition %d ended the loop at step %d (reason %d), partition 0 at step %d (reason %d)", p,
-                        (int)G.e[p]->h_out[5], (int)G.e[p]->h_out[6], (int)e->h_out[5], (int)e->h_out[6]);
+                        (int)G.e[p]->h_out[kOutIt], (int)G.e[p]->h_out[kOutReason], (int)e->h_out[kOutIt], (int)e->h_out[kOutReason]);
     read_out(G.e, 1, it_out, nullptr, lk_out, reason_out, nullptr, history, history_rows, 1);
     if (conn) {
         conn_finish(G.e, 1, changes, max_it);

@@ -1,7 +1,7 @@
 """The control step folded into the next step's gene-side update (csrc/kernels.h: ControlFold; the default of the
 unpartitioned device-driven loop) against the separate control kernel of rounds 1-2 (VBNMF_NO_CONTROL_FOLD=1, read when
-an engine is created): the arithmetic is the same statement by statement and every block of the update forms it from
-the same inputs, so the two loops must agree BIT FOR BIT -- iteration count, stop reason, every history row, the
+an engine is created): both run the same functions (kernels.h: vb_control_step, mlnmf.h: ml_control_step) and every
+block of the update forms the step from the same inputs, so the two loops must agree BIT FOR BIT -- iteration count, stop reason, every history row, the
 hyper-parameters, the lagging lk0, the state left behind -- for every place a run can end: after one step, inside a
 queued batch, on a batch boundary, on Itmax, on convergence.  Reference loop: R/bayesian.R:336-352."""
 import os
