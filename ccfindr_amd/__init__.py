@@ -17,6 +17,6 @@ from .project import Projection, VBProjection, posterior_basis, project, vb_proj
 from .consensus import Consensus, cophenetic_grouped  # noqa: F401
 from .qc import GeneStats, filter_cells, filter_genes, gene_stats, normalize_count  # noqa: F401
 from .annotate import MetaTable, assign_celltype, meta_gene_cv, meta_genes, write_meta  # noqa: F401
-from .embed import TSNE, ClusterMap, Embedding, tsne, tsne_info, visualize_clusters  # noqa: F401
+from .embed import TSNE, ClusterMap, Embedding, knn, tsne, tsne_info, tsne_knn_info, visualize_clusters  # noqa: F401
 
 __version__ = "0.1.0"

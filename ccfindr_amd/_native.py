@@ -174,6 +174,11 @@ SIGNATURES = {
     "vbnmf_tsne_forces": (ctypes.c_int, [_VP, _D, c_double_p, c_double_p, c_double_p, c_double_p]),
     "vbnmf_tsne_run": (ctypes.c_int, [_VP, _I32, _I32, _D, _I32, _I32, _D, _D, _D, _D, _I32, c_double_p, c_int32_p, c_int32_p]),
     "vbnmf_tsne_info": (ctypes.c_int, [_VP, c_int32_p, c_double_p]),
+    "vbnmf_tsne_create_knn": (ctypes.c_int, [_I32, _I64, _I32, c_double_p, _D, _I32, _I32, _VPP]),
+    "vbnmf_tsne_neighbors": (ctypes.c_int, [_VP, c_int32_p, c_double_p]),
+    "vbnmf_tsne_sparse_p": (ctypes.c_int, [_VP, c_int64_p, c_int64_p, c_int32_p, c_double_p]),
+    "vbnmf_knn": (ctypes.c_int, [_I32, _I64, _I32, c_double_p, _I32, c_int32_p, c_double_p]),
+    "vbnmf_tsne_knn_info": (ctypes.c_int, [_VP, c_int64_p, c_double_p]),
     "vbnmf_engine_cluster_ids": (ctypes.c_int, [_VP, c_int32_p]),
     "vbnmf_engine_spmm": (ctypes.c_int, [_VP, _I32, c_double_p, c_double_p]),
     "vbnmf_engine_cluster_changes": (ctypes.c_int, [_VP, c_int64_p, c_int32_p]),

@@ -720,6 +720,39 @@ int vbnmf_tsne_run(vbnmf_tsne *t, int32_t first_iter, int32_t n_iter, double exa
  * evaluation), the read-back, and the last iteration's force and update launch each by itself (device events). */
 int vbnmf_tsne_info(vbnmf_tsne *t, int32_t *ints, double *times_ms);
 
+/* The neighbour-limited map (csrc/tsne_knn.h): P supported on the k-nearest-neighbour graph of the points and
+ * stored sparse, the attraction a sum over the stored rows, the repulsion still exact over all pairs of Y (no tree, no
+ * threshold: the map stays bit-reproducible).  The handle is the one above: vbnmf_tsne_affinity, _set_state, _get_state,
+ * _forces, _run, _info and _destroy work on it with their signatures; for it vbnmf_tsne_info's last force time is the force
+ * stage as a whole (two launches).
+ * neighbors = K, or 0 for floor(3 perplexity).  x, n, d, perplexity, normalize as for vbnmf_tsne_create, whose checks hold,
+ * and 1 <= K <= n - 1, perplexity < K (K outcomes cannot carry an entropy of ln perplexity otherwise), K <= the kernel's limit
+ * (1024, vbnmf_tsne_knn_info): VBNMF_ERR_BAD_ARG, before a device is looked for.
+ * N_i = the K indices j != i with the smallest (D_ij, j) in lexicographic order, kept in that order (ties in distance go to
+ * the lower index); the bisection of vbnmf_tsne_create runs over N_i only (S_i = sum_{j in N_i} exp(-beta_i D_ij) + DBL_MIN);
+ * p_{j|i} = exp(-beta_i D_ij) * (1 / S_i) for j in N_i and 0 otherwise; P_ij = (p_{j|i} + p_{i|j}) * 1/(2n) on the pattern
+ * {(i, j): j in N_i or i in N_j}, stored by rows with ascending j (bit for bit symmetric).  The pattern is built on the host
+ * from the device's lists and exponentials. */
+int vbnmf_tsne_create_knn(int32_t device, int64_t n, int32_t d, const double *x, double perplexity, int32_t normalize, int32_t neighbors,
+                          vbnmf_tsne **handle);
+/* idx[n x K], dist[n x K] row-major: N_i and the squared distances D_ij, in the list's order; either may be NULL.
+ * VBNMF_ERR_STATE on a dense handle. */
+int vbnmf_tsne_neighbors(vbnmf_tsne *t, int32_t *idx, double *dist);
+/* The stored P in CSR: *nnz, indptr[n + 1], indices[nnz] (ascending in a row), values[nnz]; any may be NULL, and with
+ * indices == NULL only nnz and indptr are given (to size the second call).  VBNMF_ERR_STATE on a dense handle. */
+int vbnmf_tsne_sparse_p(vbnmf_tsne *t, int64_t *nnz, int64_t *indptr, int32_t *indices, double *values);
+/* The search by itself on the points as given (no normalisation, no perplexity): idx[n x k], dist[n x k] as above.
+ * n >= 2, 1 <= d <= VBNMF_MAX_RANK, 1 <= k <= n - 1, k <= the limit, x finite: VBNMF_ERR_BAD_ARG before a device is looked for. */
+int vbnmf_knn(int32_t device, int64_t n, int32_t d, const double *x, int32_t k, int32_t *idx, double *dist);
+/* ints[10]: the neighbour limit (1024: the K survivors of a row are sorted in LDS, over the next power of two), the search
+ * kernel's workgroup size (256), its LDS row capacity (2048 distances), the repulsion kernel's j-tile (1024 points a pass
+ * through LDS, 256 a wave) and i-block (64 points a workgroup), the rows of P of one attraction workgroup (4: a wave each);
+ * of the handle (0 for NULL) K, nnz, the longest row of P, the attraction grid.
+ * times_ms[5]: the search with the bisection (device events; t NULL: the calling thread's last vbnmf_knn or create), the
+ * pattern (host clock: read-back, build, upload), and of the last iteration of the last run the attraction, the repulsion
+ * and the update launch, each by itself (device events). */
+int vbnmf_tsne_knn_info(vbnmf_tsne *t, int64_t *ints, double *times_ms);
+
 /* Cluster of every cell from the coefficients the engine holds:
  * ids[j] = which.max(h[, j])[1], 1-based, first maximum on ties (R/factorize.R:55-56 inside
  * connectivity(), R/utils.R:906 cluster_id); h = the ML coefficient matrix, or E[H] of a VB
