@@ -45,6 +45,111 @@ __device__ inline double tsne_wave_sum(double v)
     return v;
 }
 
+// ---- what the dense and the neighbour path (tsne_knn.h) share ---------------------------------------------------------------
+// Stages x_i into s_xi and writes the row D_i. into `row`, k ascending; thread t writes (and later reads) the entries
+// j = t, t + 256, .. only, so a row in global memory needs no fence.
+__device__ __forceinline__ void tsne_distance_row(const double *xt, int n, int d, int i, double *s_xi, double *row)
+{
+    const int t = threadIdx.x;
+    __syncthreads();                                                           // the last point's reads of the shared arrays are done
+    if (t < d) s_xi[t] = xt[(int64_t)t * n + i];
+    __syncthreads();
+    for (int j = t; j < n; j += kTsneThreads) {
+        double D = 0.0;
+        for (int k = 0; k < d; k++) {
+            const double df = s_xi[k] - xt[(int64_t)k * n + j];
+            D += df * df;
+        }
+        row[j] = D;
+    }
+}
+
+struct TsneBisection { double beta, S; int trips; };                          // (trips: thread 0's)
+
+// The bisection on beta of one point, by the whole workgroup, over the `count` distances dist(q), the term q == skip left out
+// (-1: none).  A trip evaluates S = sum exp(-beta D) + DBL_MIN and sum D exp(-beta D) in the fixed tree: thread t adds the terms
+// t, t + 256, .. in ascending order, a wave its 64 lanes in the xor butterfly, the waves are added in wave order.  Thread 0
+// alone takes the branch from them and publishes beta and the state through s_ctl, every thread follows.
+// A point that converges keeps the beta and S of that trip.  A point that uses up its kTsneMaxTrips keeps the beta of the last
+// update and S is evaluated once more at it, so exp(-beta D) / S sums to 1 in either case.
+template <class Dist>
+__device__ __forceinline__ TsneBisection tsne_bisect(int count, int skip, Dist dist, double log_u, double *s_red, double *s_ctl)
+{
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    double beta = 1.0, lo = -DBL_MAX, hi = DBL_MAX, S = 0.0;                   // lo, hi, trips: thread 0's
+    int trips = 0, state = 0;                                                  // 0 bisecting, 1 converged, 2 out of trips
+    for (;;) {
+        double sp = 0.0, sdp = 0.0;
+        for (int q = t; q < count; q += kTsneThreads) {
+            if (q == skip) continue;
+            const double D = dist(q);
+            const double p = exp(-beta * D);
+            sp += p;
+            sdp += D * p;
+        }
+        sp = tsne_wave_sum(sp);
+        sdp = tsne_wave_sum(sdp);
+        __syncthreads();                                                       // s_red and s_ctl are free
+        if (lane == 0) { s_red[wave] = sp; s_red[kTsneWaves + wave] = sdp; }
+        __syncthreads();
+        sp = s_red[0]; sdp = s_red[kTsneWaves];
+#pragma unroll
+        for (int w = 1; w < kTsneWaves; w++) { sp += s_red[w]; sdp += s_red[kTsneWaves + w]; }
+        S = sp + DBL_MIN;
+        if (state == 2) break;
+        if (t == 0) {
+            const double H = beta * sdp / S + log(S);
+            const double delta = H - log_u;
+            trips++;
+            if (fabs(delta) < 1e-5) state = 1;
+            else {
+                if (delta > 0.0) { lo = beta; beta = hi == DBL_MAX ? beta * 2.0 : (beta + hi) / 2.0; }
+                else { hi = beta; beta = lo == -DBL_MAX ? beta / 2.0 : (beta + lo) / 2.0; }
+                if (trips == kTsneMaxTrips) state = 2;
+            }
+            s_ctl[0] = beta;
+            s_ctl[1] = (double)state;
+        }
+        __syncthreads();
+        beta = s_ctl[0];
+        state = (int)s_ctl[1];
+        if (state == 1) break;
+    }
+    return {beta, S, trips};
+}
+
+// The point of a lane in a kernel whose workgroup owns kTsneIBlock points, one per lane, the four waves sharing the j.
+struct TsneLanePoint { int i, ii; bool valid; };                              // ii: a lane past the end loads the last point and writes nothing
+__device__ __forceinline__ TsneLanePoint tsne_lane_point(int n, int lane)
+{
+    const int i = blockIdx.x * kTsneIBlock + lane;
+    return {i, i < n ? i : n - 1, i < n};
+}
+
+// Joins the four waves' partial sums of such a kernel: a lane's NS sums go to s_part[wave][s][lane] (the kernel's tile, which
+// is free after the barrier), and lane i of wave 0 writes (w0 + w1) + (w2 + w3) to the rows row0 .. row0 + NS - 1 of `sums`.
+// lane, wave: the kernel's own (formed here again from threadIdx.x they add 12 to 25 instructions to k_tsne_force).
+template <int NS>
+__device__ __forceinline__ void tsne_merge_waves(const double (&mine)[NS], double *s_part, double *sums, int row0, int n, TsneLanePoint p,
+                                                 int lane, int wave)
+{
+    __syncthreads();                                                           // the tile is free: the waves' partial sums go there
+#pragma unroll
+    for (int s = 0; s < NS; s++) s_part[(wave * NS + s) * kTsneWave + lane] = mine[s];
+    __syncthreads();
+    if (wave == 0 && p.valid) {
+#pragma unroll
+        for (int s = 0; s < NS; s++) {
+            const double p0 = s_part[(0 * NS + s) * kTsneWave + lane], p1 = s_part[(1 * NS + s) * kTsneWave + lane];
+            const double p2 = s_part[(2 * NS + s) * kTsneWave + lane], p3 = s_part[(3 * NS + s) * kTsneWave + lane];
+            sums[(int64_t)(row0 + s) * n + p.i] = (p0 + p1) + (p2 + p3);
+        }
+    }
+}
+
+// w_ij of one pair with d = y_i - y_j.  The division is IEEE: the tests' 6u on w rests on it.
+__device__ __forceinline__ double tsne_pair_w(double d0, double d1) { return 1.0 / (1.0 + d0 * d0 + d1 * d1); }
+
 // ---- affinities ------------------------------------------------------------------------------------------------------------
 struct TsneAffArgs {
     int32_t n, d;
@@ -55,78 +160,25 @@ struct TsneAffArgs {
     int32_t *trips;                // [n]
 };
 
-// One workgroup per point i, in grid strides.  The row D_i. is computed once: into LDS while n <= kTsneLdsRow, else into the
-// workgroup's own row of `scratch` (a thread reads back only what it wrote itself: no fence is needed).  A trip evaluates
-// S = sum_j exp(-beta D_ij) + DBL_MIN and sum_j D_ij exp(-beta D_ij) over all j != i in the fixed tree; thread 0 alone takes the
-// bisection's branch from them and publishes beta and the state, every thread follows.
-// A row that converges keeps the beta and S of that trip.  A row that uses up its kTsneMaxTrips keeps the beta of the last
-// update and S is evaluated once more at it, so p_{j|i} = exp(-beta_i D_ij) / S_i sums to 1 in either case.
+// One workgroup per point i, in grid strides.  The row D_i. is computed once (tsne_distance_row): into LDS while
+// n <= kTsneLdsRow, else into the workgroup's own row of `scratch`.  The bisection (tsne_bisect) runs over all j != i.
 __global__ __launch_bounds__(kTsneThreads) void k_tsne_affinity(const TsneAffArgs A)
 {
     __shared__ double s_row[kTsneLdsRow];
     __shared__ double s_xi[VBNMF_MAX_RANK];
     __shared__ double s_red[2 * kTsneWaves];
     __shared__ double s_ctl[2];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int n = A.n, d = A.d;
+    const int n = A.n;
     double *row = n <= kTsneLdsRow ? s_row : A.scratch + (int64_t)blockIdx.x * n;
 
     for (int i = blockIdx.x; i < n; i += gridDim.x) {
-        __syncthreads();                                                       // the last point's reads of s_xi and s_ctl are done
-        if (t < d) s_xi[t] = A.xt[(int64_t)t * n + i];
-        __syncthreads();
-        for (int j = t; j < n; j += kTsneThreads) {
-            double D = 0.0;
-            for (int k = 0; k < d; k++) {
-                const double df = s_xi[k] - A.xt[(int64_t)k * n + j];
-                D += df * df;
-            }
-            row[j] = D;
-        }
-        double beta = 1.0, lo = -DBL_MAX, hi = DBL_MAX, S = 0.0;               // lo, hi, trips: thread 0's
-        int trips = 0, state = 0;                                              // 0 bisecting, 1 converged, 2 out of trips
-        for (;;) {
-            double sp = 0.0, sdp = 0.0;
-            for (int j = t; j < n; j += kTsneThreads) {
-                if (j == i) continue;
-                const double D = row[j];
-                const double p = exp(-beta * D);
-                sp += p;
-                sdp += D * p;
-            }
-            sp = tsne_wave_sum(sp);
-            sdp = tsne_wave_sum(sdp);
-            __syncthreads();                                                   // s_red and s_ctl are free
-            if (lane == 0) { s_red[wave] = sp; s_red[kTsneWaves + wave] = sdp; }
-            __syncthreads();
-            sp = s_red[0]; sdp = s_red[kTsneWaves];
-#pragma unroll
-            for (int w = 1; w < kTsneWaves; w++) { sp += s_red[w]; sdp += s_red[kTsneWaves + w]; }
-            S = sp + DBL_MIN;
-            if (state == 2) break;
-            if (t == 0) {
-                const double H = beta * sdp / S + log(S);
-                const double delta = H - A.log_u;
-                trips++;
-                if (fabs(delta) < 1e-5) state = 1;
-                else {
-                    if (delta > 0.0) { lo = beta; beta = hi == DBL_MAX ? beta * 2.0 : (beta + hi) / 2.0; }
-                    else { hi = beta; beta = lo == -DBL_MAX ? beta / 2.0 : (beta + lo) / 2.0; }
-                    if (trips == kTsneMaxTrips) state = 2;
-                }
-                s_ctl[0] = beta;
-                s_ctl[1] = (double)state;
-            }
-            __syncthreads();
-            beta = s_ctl[0];
-            state = (int)s_ctl[1];
-            if (state == 1) break;
-        }
-        if (t == 0) {
-            A.beta[i] = beta;
-            A.sum_p[i] = S;
-            A.inv_s[i] = 1.0 / S;
-            A.trips[i] = trips;
+        tsne_distance_row(A.xt, n, A.d, i, s_xi, row);
+        const TsneBisection b = tsne_bisect(n, i, [row](int j) { return row[j]; }, A.log_u, s_red, s_ctl);
+        if (threadIdx.x == 0) {
+            A.beta[i] = b.beta;
+            A.sum_p[i] = b.S;
+            A.inv_s[i] = 1.0 / b.S;
+            A.trips[i] = b.trips;
         }
     }
 }
@@ -142,8 +194,8 @@ struct TsneForceArgs {
 
 // A workgroup owns the kTsneIBlock points i = blockIdx.x * 64 + lane and streams all j through LDS in tiles of kTsneJTile rows
 // (y_j0, y_j1, beta_j, 1/S_j, x_j0 .. x_j,d-1).  Wave w takes the rows w * 8 .. w * 8 + 7 of every tile, so a point's terms are
-// split over the four waves by j alone; each wave adds its terms in ascending j, and lane i of wave 0 adds the four partial
-// sums as (w0 + w1) + (w2 + w3) and writes the point's sums once.
+// split over the four waves by j alone; each wave adds its terms in ascending j, and tsne_merge_waves joins the four partial
+// sums and writes the point's sums once.
 // DR > 0: x_i sits in DR registers (d <= DR), the tile's rows are DR wide and both are zero past d, so the loop over k has no
 // bound to test and D_ij keeps its bits.  DR = 0: x_i is read per pair from xt (the loads of a wave are contiguous and
 // stay in L1 / L2); wide d pays for it, the usual ranks do not take this path.
@@ -153,9 +205,8 @@ __global__ __launch_bounds__(kTsneThreads) void k_tsne_force(const TsneForceArgs
     extern __shared__ __attribute__((aligned(16))) double tsne_smem[];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int n = A.n, d = A.d, stride = (DR > 0 ? DR : d) + kTsneTileHead;      // as tsne_force_lds() sizes it
-    const int i = blockIdx.x * kTsneIBlock + lane;
-    const bool valid = i < n;
-    const int ii = valid ? i : n - 1;                                          // a lane past the end loads the last point and writes nothing
+    const TsneLanePoint pt = tsne_lane_point(n, lane);
+    const int i = pt.i, ii = pt.ii;
     double xi[DR > 0 ? DR : 1];
     if (DR > 0) {
 #pragma unroll
@@ -195,12 +246,12 @@ __global__ __launch_bounds__(kTsneThreads) void k_tsne_force(const TsneForceArgs
                     D += df * df;
                 }
             }
-            if (valid && j != i) {
+            if (pt.valid && j != i) {
                 const double pij = exp(-bi * D) * si;
                 const double pji = exp(-T[2] * D) * T[3];
                 const double P = (pij + pji) * A.inv_2n;
                 const double d0 = yi0 - T[0], d1 = yi1 - T[1];
-                const double w = 1.0 / (1.0 + d0 * d0 + d1 * d1);
+                const double w = tsne_pair_w(d0, d1);
                 const double pw = P * w, ww = w * w;
                 a0 += pw * d0;
                 a1 += pw * d1;
@@ -215,20 +266,8 @@ __global__ __launch_bounds__(kTsneThreads) void k_tsne_force(const TsneForceArgs
             }
         }
     }
-    __syncthreads();                                                           // the tile is free: the waves' partial sums go there
-    double *s_part = tsne_smem;                                                // [kTsneWaves][kTsneForceSums][64]
     const double mine[kTsneForceSums] = {a0, a1, r0, r1, z, c1, c2, cp};
-#pragma unroll
-    for (int s = 0; s < kTsneForceSums; s++) s_part[(wave * kTsneForceSums + s) * kTsneWave + lane] = mine[s];
-    __syncthreads();
-    if (wave == 0 && valid) {
-#pragma unroll
-        for (int s = 0; s < kTsneForceSums; s++) {
-            const double p0 = s_part[(0 * kTsneForceSums + s) * kTsneWave + lane], p1 = s_part[(1 * kTsneForceSums + s) * kTsneWave + lane];
-            const double p2 = s_part[(2 * kTsneForceSums + s) * kTsneWave + lane], p3 = s_part[(3 * kTsneForceSums + s) * kTsneWave + lane];
-            A.sums[(int64_t)s * n + i] = (p0 + p1) + (p2 + p3);
-        }
-    }
+    tsne_merge_waves(mine, tsne_smem, A.sums, 0, n, pt, lane, wave);              // s_part [kTsneWaves][kTsneForceSums][64]
 }
 
 constexpr size_t kTsneForcePartBytes = (size_t)kTsneWaves * kTsneForceSums * kTsneWave * sizeof(double);

@@ -4,6 +4,8 @@
 // vbnmf_tsne_destroy and not through a DeviceCall.
 // A neighbour handle (vbnmf_tsne_create_knn, tsne_knn.h) is the same handle: its creation is the search with the
 // bisection in one launch and the sparse P's pattern built here on the host; its force stage is two launches.
+// Both kinds and vbnmf_knn share one preparation of the points (tsne_points), one opening of a handle (tsne_open) and one
+// launcher of the two row kernels (tsne_row_kernel); the slots of the two *_info calls are named by the enums below.
 #include <algorithm>
 #include <cmath>
 #include <memory>
@@ -15,11 +17,22 @@
 
 using namespace vbnmf;
 
+// The slots of what vbnmf_tsne_info and vbnmf_tsne_knn_info hand out, in the order include/vbnmf.h states them.
+enum TsneInfoSlot : int { kInfoWave, kInfoThreads, kInfoIBlock, kInfoJTile, kInfoLdsRow, kInfoAffGrid, kInfoForceGrid, kInfoUpdThreads };
+enum TsneTimeSlot : int { kTimeNormalise, kTimeUpload, kTimeAffinities, kTimeLoop, kTimeReadBack, kTimeLastForce, kTimeLastUpdate, kTsneTimeSlots };
+constexpr int kTsneCreateTimes = kTimeAffinities + 1;                         // the create's part of them
+enum TsneKnnInfoSlot : int { kKnnInfoLimit, kKnnInfoThreads, kKnnInfoLdsRow, kKnnInfoRepTile, kKnnInfoIBlock, kKnnInfoAttRows, kKnnInfoK, kKnnInfoNnz,
+                             kKnnInfoLongest, kKnnInfoAttGrid };
+enum TsneKnnTimeSlot : int { kKnnTimeSearch, kKnnTimePattern, kKnnTimeAttract, kKnnTimeRepulse, kKnnTimeUpdate, kTsneKnnTimeSlots };
+// The handle's events: around a row kernel or a run's iterations; of a run's last iteration, in front of its force stage, between
+// that stage's two launches (a neighbour handle's) and behind it.
+enum TsneEvent : int { kEvBegin, kEvEnd, kEvLast, kEvLastMid, kEvLastForce, kTsneEvents };
+
 struct vbnmf_tsne {
-    int device = 0;
+    int device = 0, cus = 0;
     int32_t n = 0, d = 0;
     hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;
+    hipEvent_t ev[kTsneEvents] = {};
     double *xt = nullptr, *beta = nullptr, *sum_p = nullptr, *inv_s = nullptr;
     int32_t *trips = nullptr;
     double *state = nullptr;       // [6][n]: y0 y1 u0 u1 g0 g1
@@ -29,10 +42,9 @@ struct vbnmf_tsne {
     int64_t costs_cap = 0;
     int aff_grid = 0, force_grid = 0;
     bool has_state = false;
-    double times_ms[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    double times_ms[kTsneTimeSlots] = {};
     // a neighbour handle's (K > 0)
     int32_t K = 0;
-    hipEvent_t ev4 = nullptr;
     int32_t *nb_idx = nullptr;     // [n][K]
     double *nb_dist = nullptr;     // [n][K]
     double *pcond = nullptr;       // [n][K] p_{j|i}
@@ -42,12 +54,13 @@ struct vbnmf_tsne {
     std::vector<int64_t> h_indptr;
     int64_t nnz = 0, max_row = 0;
     int att_grid = 0;
-    double knn_ms[5] = {0.0, 0.0, 0.0, 0.0, 0.0};      // search, pattern, last attract, last repulse, last update
+    double knn_ms[kTsneKnnTimeSlots] = {};
 };
 
 namespace {
 
-thread_local double tl_tsne_create_ms[3] = {0.0, 0.0, 0.0};
+thread_local double tl_tsne_create_ms[kTsneCreateTimes] = {};
+thread_local double tl_knn_search_ms = 0.0;
 
 int tsne_use(vbnmf_tsne *t)
 {
@@ -124,29 +137,57 @@ void tsne_join(const double *c0, const double *c1, int64_t n, double *a)
     for (int64_t i = 0; i < n; i++) { a[2 * i] = c0[i]; a[2 * i + 1] = c1[i]; }
 }
 
-thread_local double tl_knn_search_ms = 0.0;
+int tsne_elapsed(vbnmf_tsne *t, TsneEvent from, TsneEvent to, double *ms)
+{
+    float f = 0.0f;
+    HIPCHECK(hipEventElapsedTime(&f, t->ev[from], t->ev[to]));
+    *ms = f;
+    return VBNMF_OK;
+}
 
-// k_tsne_knn over the handle's xt into nb_idx, nb_dist (and, with `affinity`, beta, sum_p, inv_s, trips, pcond); waits for it
-int tsne_knn_search(vbnmf_tsne *t, int cus, int affinity, double log_u)
+// The device, its stream and events for a new handle.
+int tsne_open(vbnmf_tsne *t, int32_t device)
+{
+    t->device = device;
+    HIPCHECK(hipSetDevice(device));
+    if (int rc = device_cus(device, t->cus)) return rc;
+    HIPCHECK(hipStreamCreate(&t->stream));
+    for (hipEvent_t &e : t->ev) HIPCHECK(hipEventCreate(&e));
+    return VBNMF_OK;
+}
+
+// A row kernel (k_tsne_affinity, k_tsne_knn: one workgroup per point, in grid strides, a row of D each) over the handle's
+// points: launch(grid, scratch) queues it on the stream, `scratch` being the workgroups' rows where LDS does not hold one;
+// waits for it and leaves its device time in *ms.  `what` names the call in an error.
+template <class Launch>
+int tsne_row_kernel(vbnmf_tsne *t, const char *what, double *ms, Launch launch)
 {
     const int64_t n = t->n;
-    t->aff_grid = (int)std::min<int64_t>(n, (int64_t)cus * 4);
+    t->aff_grid = (int)std::min<int64_t>(n, (int64_t)t->cus * 4);
     double *scratch = nullptr;
     if (n > kTsneLdsRow) { if (int rc = dev_alloc(&scratch, (size_t)t->aff_grid * (size_t)n)) return rc; }
-    TsneKnnArgs a;
-    a.n = t->n; a.d = t->d; a.K = t->K; a.affinity = affinity; a.xt = t->xt; a.scratch = scratch; a.log_u = log_u;
-    a.idx = t->nb_idx; a.dist = t->nb_dist; a.beta = t->beta; a.sum_p = t->sum_p; a.inv_s = t->inv_s; a.trips = t->trips; a.pcond = t->pcond;
-    hipError_t err = hipEventRecord(t->ev0, t->stream);
-    hipLaunchKernelGGL(k_tsne_knn, dim3((unsigned)t->aff_grid), dim3(kTsneThreads), 0, t->stream, a);
+    hipError_t err = hipEventRecord(t->ev[kEvBegin], t->stream);
+    launch(dim3((unsigned)t->aff_grid), scratch);
     if (err == hipSuccess) err = hipGetLastError();
-    if (err == hipSuccess) err = hipEventRecord(t->ev1, t->stream);
+    if (err == hipSuccess) err = hipEventRecord(t->ev[kEvEnd], t->stream);
     const hipError_t serr = hipStreamSynchronize(t->stream);                  // scratch is free after this whatever happened
     dev_free(scratch);
     if (err == hipSuccess) err = serr;
-    if (err != hipSuccess) return fail(VBNMF_ERR_HIP, "the neighbour search: %s", hipGetErrorString(err));
-    float ms = 0.0f;
-    HIPCHECK(hipEventElapsedTime(&ms, t->ev0, t->ev1));
-    t->knn_ms[0] = tl_knn_search_ms = ms;
+    if (err != hipSuccess) return fail(VBNMF_ERR_HIP, "%s: %s", what, hipGetErrorString(err));
+    return tsne_elapsed(t, kEvBegin, kEvEnd, ms);
+}
+
+// k_tsne_knn over the handle's xt into nb_idx, nb_dist (and, with `affinity`, beta, sum_p, inv_s, trips, pcond); waits for it
+int tsne_knn_search(vbnmf_tsne *t, int affinity, double log_u)
+{
+    if (int rc = tsne_row_kernel(t, "the neighbour search", &t->knn_ms[kKnnTimeSearch], [&](dim3 grid, double *scratch) {
+            TsneKnnArgs a;
+            a.n = t->n; a.d = t->d; a.K = t->K; a.affinity = affinity; a.xt = t->xt; a.scratch = scratch; a.log_u = log_u;
+            a.idx = t->nb_idx; a.dist = t->nb_dist; a.beta = t->beta; a.sum_p = t->sum_p; a.inv_s = t->inv_s; a.trips = t->trips; a.pcond = t->pcond;
+            hipLaunchKernelGGL(k_tsne_knn, grid, dim3(kTsneThreads), 0, t->stream, a);
+        }))
+        return rc;
+    tl_knn_search_ms = t->knn_ms[kKnnTimeSearch];
     return VBNMF_OK;
 }
 
@@ -219,65 +260,72 @@ int tsne_knn_pattern(vbnmf_tsne *t)
     dev_free(t->pcond);                                                        // P holds them now
     t->pcond = nullptr;
     t->att_grid = (int)((n + kTsneAttRows - 1) / kTsneAttRows);
-    t->knn_ms[1] = ms_since(t0);
+    t->knn_ms[kKnnTimePattern] = ms_since(t0);
     return VBNMF_OK;
 }
 
+// x, checked to be finite, as the device keeps it: xt[d][n]; the normalisation runs on that in a fixed order: column means,
+// then the largest |value|
+int tsne_points(int64_t n, int d, const double *x, int normalize, std::vector<double> &xt)
+{
+    for (int64_t q = 0; q < n * d; q++)
+        if (!std::isfinite(x[q])) return fail(VBNMF_ERR_BAD_ARG, "x[%lld, %lld] is not finite", (long long)(q / d), (long long)(q % d));
+    xt.resize((size_t)n * d);
+    for (int64_t i = 0; i < n; i++)
+        for (int k = 0; k < d; k++) xt[(size_t)k * n + i] = x[i * d + k];
+    if (!normalize) return VBNMF_OK;
+    double mx = 0.0;
+    for (int k = 0; k < d; k++) {
+        double *c = xt.data() + (size_t)k * n;
+        double s = 0.0;
+        for (int64_t i = 0; i < n; i++) s += c[i];
+        const double mean = s / (double)n;
+        for (int64_t i = 0; i < n; i++) { c[i] -= mean; mx = std::max(mx, std::fabs(c[i])); }
+    }
+    if (mx > 0.0)
+        for (double &v : xt) v /= mx;
+    return VBNMF_OK;
+}
+
+int tsne_check_shape(int64_t n, int32_t d, int min_n)
+{
+    if (n < min_n || n > 2147481600ll)                                           // (int loop counters step by <= 1024)
+        return fail(VBNMF_ERR_BAD_ARG, "n = %lld points is outside [%d, 2^31 - 2048]", (long long)n, min_n);
+    if (d < 1 || d > VBNMF_MAX_RANK) return fail(VBNMF_ERR_BAD_ARG, "d = %d is outside [1, %d]", d, VBNMF_MAX_RANK);
+    return VBNMF_OK;
+}
+
+// open, allocate, upload, then the affinities: k_tsne_affinity, or the search with the bisection and the pattern
 int tsne_create(vbnmf_tsne *t, int32_t device, const std::vector<double> &xt, double perplexity)
 {
     const int64_t n = t->n;
-    const int d = t->d;
-    t->device = device;
-    HIPCHECK(hipSetDevice(device));
-    int cus = 0;
-    if (int rc = device_cus(device, cus)) return rc;
+    const size_t nk = (size_t)n * (size_t)t->K;
+    const char *name = t->K > 0 ? "vbnmf_tsne_create_knn" : "vbnmf_tsne_create";
     const auto t0 = host_clock::now();
-    HIPCHECK(hipStreamCreate(&t->stream));
-    HIPCHECK(hipEventCreate(&t->ev0));
-    HIPCHECK(hipEventCreate(&t->ev1));
-    HIPCHECK(hipEventCreate(&t->ev2));
-    HIPCHECK(hipEventCreate(&t->ev3));
     int rc;
-    if ((rc = dev_alloc(&t->xt, (size_t)n * d)) || (rc = dev_alloc(&t->beta, (size_t)n)) || (rc = dev_alloc(&t->sum_p, (size_t)n)) ||
+    if ((rc = tsne_open(t, device)) || (rc = dev_alloc(&t->xt, xt.size())) || (rc = dev_alloc(&t->beta, (size_t)n)) || (rc = dev_alloc(&t->sum_p, (size_t)n)) ||
         (rc = dev_alloc(&t->inv_s, (size_t)n)) || (rc = dev_alloc(&t->trips, (size_t)n)) || (rc = dev_alloc(&t->state, 6 * (size_t)n)) ||
         (rc = dev_alloc(&t->sums, (size_t)kTsneForceSums * n)) || (rc = dev_alloc(&t->cost_i, (size_t)n)))
         return rc;
-    t->aff_grid = (int)std::min<int64_t>(n, (int64_t)cus * 4);
+    if (t->K > 0 && ((rc = dev_alloc(&t->nb_idx, nk)) || (rc = dev_alloc(&t->nb_dist, nk)) || (rc = dev_alloc(&t->pcond, nk)))) return rc;
     t->force_grid = (int)((n + kTsneIBlock - 1) / kTsneIBlock);
+    const hipError_t uerr = hipMemcpy(t->xt, xt.data(), xt.size() * sizeof(double), hipMemcpyHostToDevice);
+    tl_tsne_create_ms[kTimeUpload] = ms_since(t0);
+    if (uerr != hipSuccess) return fail(VBNMF_ERR_HIP, "%s: %s", name, hipGetErrorString(uerr));
+    const double log_u = std::log(perplexity);
     if (t->K > 0) {
-        HIPCHECK(hipEventCreate(&t->ev4));
-        const size_t nk = (size_t)n * (size_t)t->K;
-        if ((rc = dev_alloc(&t->nb_idx, nk)) || (rc = dev_alloc(&t->nb_dist, nk)) || (rc = dev_alloc(&t->pcond, nk))) return rc;
-        hipError_t uerr = hipMemcpy(t->xt, xt.data(), (size_t)n * d * sizeof(double), hipMemcpyHostToDevice);
-        tl_tsne_create_ms[1] = ms_since(t0);
-        if (uerr != hipSuccess) return fail(VBNMF_ERR_HIP, "vbnmf_tsne_create_knn: %s", hipGetErrorString(uerr));
-        if ((rc = tsne_knn_search(t, cus, 1, std::log(perplexity)))) return rc;
-        if ((rc = tsne_knn_pattern(t))) return rc;
-        tl_tsne_create_ms[2] = t->knn_ms[0];
-        for (int k = 0; k < 3; k++) t->times_ms[k] = tl_tsne_create_ms[k];
-        return VBNMF_OK;
+        if ((rc = tsne_knn_search(t, 1, log_u)) || (rc = tsne_knn_pattern(t))) return rc;
+        tl_tsne_create_ms[kTimeAffinities] = t->knn_ms[kKnnTimeSearch];
+    } else {
+        rc = tsne_row_kernel(t, name, &tl_tsne_create_ms[kTimeAffinities], [&](dim3 grid, double *scratch) {
+            TsneAffArgs a;
+            a.n = t->n; a.d = t->d; a.xt = t->xt; a.scratch = scratch; a.log_u = log_u;
+            a.beta = t->beta; a.sum_p = t->sum_p; a.inv_s = t->inv_s; a.trips = t->trips;
+            hipLaunchKernelGGL(k_tsne_affinity, grid, dim3(kTsneThreads), 0, t->stream, a);
+        });
+        if (rc) return rc;
     }
-    double *scratch = nullptr;
-    if (n > kTsneLdsRow) { if ((rc = dev_alloc(&scratch, (size_t)t->aff_grid * (size_t)n))) return rc; }
-    hipError_t err = hipMemcpy(t->xt, xt.data(), (size_t)n * d * sizeof(double), hipMemcpyHostToDevice);
-    tl_tsne_create_ms[1] = ms_since(t0);
-    if (err == hipSuccess) {
-        TsneAffArgs a;
-        a.n = t->n; a.d = d; a.xt = t->xt; a.scratch = scratch; a.log_u = std::log(perplexity);
-        a.beta = t->beta; a.sum_p = t->sum_p; a.inv_s = t->inv_s; a.trips = t->trips;
-        err = hipEventRecord(t->ev0, t->stream);
-        hipLaunchKernelGGL(k_tsne_affinity, dim3((unsigned)t->aff_grid), dim3(kTsneThreads), 0, t->stream, a);
-        if (err == hipSuccess) err = hipGetLastError();
-        if (err == hipSuccess) err = hipEventRecord(t->ev1, t->stream);
-    }
-    const hipError_t serr = hipStreamSynchronize(t->stream);                  // scratch is free after this whatever happened
-    dev_free(scratch);
-    if (err == hipSuccess) err = serr;
-    if (err != hipSuccess) return fail(VBNMF_ERR_HIP, "vbnmf_tsne_create: %s", hipGetErrorString(err));
-    float ms = 0.0f;
-    HIPCHECK(hipEventElapsedTime(&ms, t->ev0, t->ev1));
-    tl_tsne_create_ms[2] = ms;
-    for (int k = 0; k < 3; k++) t->times_ms[k] = tl_tsne_create_ms[k];
+    for (int k = 0; k < kTsneCreateTimes; k++) t->times_ms[k] = tl_tsne_create_ms[k];
     return VBNMF_OK;
 }
 
@@ -293,8 +341,7 @@ static int tsne_create_any(int32_t device, int64_t n, int32_t d, const double *x
     if (!handle) return fail(VBNMF_ERR_BAD_ARG, "NULL argument");
     *handle = nullptr;
     if (!x) return fail(VBNMF_ERR_BAD_ARG, "NULL argument");
-    if (n < 1 || n > 2147481600ll) return fail(VBNMF_ERR_BAD_ARG, "n = %lld points is outside [1, 2^31 - 2048]", (long long)n);   // (int loop counters step by <= 1024)
-    if (d < 1 || d > VBNMF_MAX_RANK) return fail(VBNMF_ERR_BAD_ARG, "d = %d is outside [1, %d]", d, VBNMF_MAX_RANK);
+    if (int rc = tsne_check_shape(n, d, 1)) return rc;
     if (!std::isfinite(perplexity) || perplexity < 1.0) return fail(VBNMF_ERR_BAD_ARG, "the perplexity must be finite and >= 1");
     if (!(3.0 * perplexity < (double)(n - 1)))
         return fail(VBNMF_ERR_BAD_ARG, "the perplexity %g is too large for %lld points: 3 perplexity < n - 1 is required", perplexity, (long long)n);
@@ -309,25 +356,9 @@ static int tsne_create_any(int32_t device, int64_t n, int32_t d, const double *x
     }
     try {
         const auto t0 = host_clock::now();
-        for (int64_t q = 0; q < n * d; q++)
-            if (!std::isfinite(x[q])) return fail(VBNMF_ERR_BAD_ARG, "x[%lld, %lld] is not finite", (long long)(q / d), (long long)(q % d));
-        // the device's copy is xt[d][n]; the normalisation runs on it in a fixed order: column means, then the largest |value|
-        std::vector<double> xt((size_t)n * d);
-        for (int64_t i = 0; i < n; i++)
-            for (int k = 0; k < d; k++) xt[(size_t)k * n + i] = x[i * d + k];
-        if (normalize) {
-            double mx = 0.0;
-            for (int k = 0; k < d; k++) {
-                double *c = xt.data() + (size_t)k * n;
-                double s = 0.0;
-                for (int64_t i = 0; i < n; i++) s += c[i];
-                const double mean = s / (double)n;
-                for (int64_t i = 0; i < n; i++) { c[i] -= mean; mx = std::max(mx, std::fabs(c[i])); }
-            }
-            if (mx > 0.0)
-                for (double &v : xt) v /= mx;
-        }
-        tl_tsne_create_ms[0] = ms_since(t0);
+        std::vector<double> xt;
+        if (int rc = tsne_points(n, d, x, normalize, xt)) return rc;
+        tl_tsne_create_ms[kTimeNormalise] = ms_since(t0);
         if (int rc = check_device(device)) return rc;
         std::unique_ptr<vbnmf_tsne, void (*)(vbnmf_tsne *)> t(new vbnmf_tsne(), vbnmf_tsne_destroy);
         t->n = (int32_t)n; t->d = d; t->K = K;
@@ -357,29 +388,19 @@ int vbnmf_tsne_create_knn(int32_t device, int64_t n, int32_t d, const double *x,
 int vbnmf_knn(int32_t device, int64_t n, int32_t d, const double *x, int32_t k, int32_t *idx, double *dist)
 {
     if (!x || !idx || !dist) return fail(VBNMF_ERR_BAD_ARG, "NULL argument");
-    if (n < 2 || n > 2147481600ll) return fail(VBNMF_ERR_BAD_ARG, "n = %lld points is outside [2, 2^31 - 2048]", (long long)n);
-    if (d < 1 || d > VBNMF_MAX_RANK) return fail(VBNMF_ERR_BAD_ARG, "d = %d is outside [1, %d]", d, VBNMF_MAX_RANK);
+    if (int rc = tsne_check_shape(n, d, 2)) return rc;
     if (k < 1 || (int64_t)k > n - 1) return fail(VBNMF_ERR_BAD_ARG, "k = %d neighbours are outside [1, n - 1 = %lld]", k, (long long)(n - 1));
     if (k > kTsneKnnMax) return fail(VBNMF_ERR_BAD_ARG, "k = %d neighbours are more than the kernel's limit of %d", k, kTsneKnnMax);
     try {
-        for (int64_t q = 0; q < n * d; q++)
-            if (!std::isfinite(x[q])) return fail(VBNMF_ERR_BAD_ARG, "x[%lld, %lld] is not finite", (long long)(q / d), (long long)(q % d));
-        std::vector<double> xt((size_t)n * d);
-        for (int64_t i = 0; i < n; i++)
-            for (int c = 0; c < d; c++) xt[(size_t)c * n + i] = x[i * d + c];
-        if (int rc = check_device(device)) return rc;
-        std::unique_ptr<vbnmf_tsne, void (*)(vbnmf_tsne *)> t(new vbnmf_tsne(), vbnmf_tsne_destroy);      // the search's buffers only
-        t->n = (int32_t)n; t->d = d; t->K = k; t->device = device;
-        HIPCHECK(hipSetDevice(device));
-        int cus = 0;
-        if (int rc = device_cus(device, cus)) return rc;
-        HIPCHECK(hipStreamCreate(&t->stream));
-        HIPCHECK(hipEventCreate(&t->ev0));
-        HIPCHECK(hipEventCreate(&t->ev1));
-        const size_t nk = (size_t)n * (size_t)k;
+        std::vector<double> xt;
         int rc;
-        if ((rc = dev_upload(&t->xt, xt)) || (rc = dev_alloc(&t->nb_idx, nk)) || (rc = dev_alloc(&t->nb_dist, nk))) return rc;
-        if ((rc = tsne_knn_search(t.get(), cus, 0, 0.0))) return rc;
+        if ((rc = tsne_points(n, d, x, 0, xt)) || (rc = check_device(device))) return rc;
+        std::unique_ptr<vbnmf_tsne, void (*)(vbnmf_tsne *)> t(new vbnmf_tsne(), vbnmf_tsne_destroy);      // the search's buffers only
+        t->n = (int32_t)n; t->d = d; t->K = k;
+        const size_t nk = (size_t)n * (size_t)k;
+        if ((rc = tsne_open(t.get(), device)) || (rc = dev_upload(&t->xt, xt)) || (rc = dev_alloc(&t->nb_idx, nk)) ||
+            (rc = dev_alloc(&t->nb_dist, nk)) || (rc = tsne_knn_search(t.get(), 0, 0.0)))
+            return rc;
         HIPCHECK(hipMemcpy(idx, t->nb_idx, nk * sizeof(int32_t), hipMemcpyDeviceToHost));
         HIPCHECK(hipMemcpy(dist, t->nb_dist, nk * sizeof(double), hipMemcpyDeviceToHost));
         return VBNMF_OK;
@@ -412,12 +433,13 @@ int vbnmf_tsne_sparse_p(vbnmf_tsne *t, int64_t *nnz, int64_t *indptr, int32_t *i
 int vbnmf_tsne_knn_info(vbnmf_tsne *t, int64_t *ints, double *times_ms)
 {
     if (ints) {
-        const int64_t v[10] = {kTsneKnnMax, kTsneThreads, kTsneLdsRow, kTsneRepTile, kTsneIBlock, kTsneAttRows, t ? t->K : 0, t ? t->nnz : 0,
-                               t ? t->max_row : 0, t ? t->att_grid : 0};
-        for (int k = 0; k < 10; k++) ints[k] = v[k];
+        ints[kKnnInfoLimit] = kTsneKnnMax; ints[kKnnInfoThreads] = kTsneThreads; ints[kKnnInfoLdsRow] = kTsneLdsRow;
+        ints[kKnnInfoRepTile] = kTsneRepTile; ints[kKnnInfoIBlock] = kTsneIBlock; ints[kKnnInfoAttRows] = kTsneAttRows;
+        ints[kKnnInfoK] = t ? t->K : 0; ints[kKnnInfoNnz] = t ? t->nnz : 0; ints[kKnnInfoLongest] = t ? t->max_row : 0;
+        ints[kKnnInfoAttGrid] = t ? t->att_grid : 0;
     }
     if (times_ms)
-        for (int k = 0; k < 5; k++) times_ms[k] = t ? t->knn_ms[k] : (k == 0 ? tl_knn_search_ms : 0.0);
+        for (int k = 0; k < kTsneKnnTimeSlots; k++) times_ms[k] = t ? t->knn_ms[k] : (k == kKnnTimeSearch ? tl_knn_search_ms : 0.0);
     return VBNMF_OK;
 }
 
@@ -431,11 +453,8 @@ void vbnmf_tsne_destroy(vbnmf_tsne *t)
     dev_free(t->xt); dev_free(t->beta); dev_free(t->sum_p); dev_free(t->inv_s); dev_free(t->trips); dev_free(t->state);
     dev_free(t->sums); dev_free(t->cost_i); dev_free(t->costs);
     dev_free(t->nb_idx); dev_free(t->nb_dist); dev_free(t->pcond); dev_free(t->indptr); dev_free(t->indices); dev_free(t->values);
-    if (t->ev4) (void)hipEventDestroy(t->ev4);
-    if (t->ev0) (void)hipEventDestroy(t->ev0);
-    if (t->ev1) (void)hipEventDestroy(t->ev1);
-    if (t->ev2) (void)hipEventDestroy(t->ev2);
-    if (t->ev3) (void)hipEventDestroy(t->ev3);
+    for (hipEvent_t e : t->ev)
+        if (e) (void)hipEventDestroy(e);
     if (t->stream) (void)hipStreamDestroy(t->stream);
     if (cur >= 0) (void)hipSetDevice(cur);
     delete t;
@@ -537,40 +556,37 @@ int vbnmf_tsne_run(vbnmf_tsne *t, int32_t first_iter, int32_t n_iter, double exa
     int32_t count = 0;
     for (int32_t it = first_iter; it <= last; it++) count += due(it) ? 1 : 0;
     if (int rc = tsne_costs_reserve(t, count)) return rc;
-    HIPCHECK(hipEventRecord(t->ev0, t->stream));
+    HIPCHECK(hipEventRecord(t->ev[kEvBegin], t->stream));
     int32_t slot = 0;
     for (int32_t it = first_iter; it <= last; it++) {
         // the cost of the Y that iteration it - 1 left is formed by this iteration's force launch
         const int cost = it > first_iter && due(it - 1) ? 1 : 0;
         const double e = it <= stop_lying_iter ? exaggeration : 1.0, m = it <= mom_switch_iter ? momentum : final_momentum;
-        if (it == last) HIPCHECK(hipEventRecord(t->ev2, t->stream));            // the last iteration's two launches, each by itself
-        if (int rc = tsne_launch_force(t, cost, it == last ? t->ev4 : nullptr)) return rc;      // (ev4: a neighbour handle's, between its two launches)
-        if (it == last) HIPCHECK(hipEventRecord(t->ev3, t->stream));
+        if (it == last) HIPCHECK(hipEventRecord(t->ev[kEvLast], t->stream));    // the last iteration's two launches, each by itself
+        if (int rc = tsne_launch_force(t, cost, it == last ? t->ev[kEvLastMid] : nullptr)) return rc;
+        if (it == last) HIPCHECK(hipEventRecord(t->ev[kEvLastForce], t->stream));
         if (int rc = tsne_launch_update(t, 1, cost, e, m, eta, min_gain, t->costs + slot)) return rc;
-        if (it == last) HIPCHECK(hipEventRecord(t->ev1, t->stream));
+        if (it == last) HIPCHECK(hipEventRecord(t->ev[kEvEnd], t->stream));
         if (cost) cost_iters[slot++] = it - 1;
     }
     if (int rc = tsne_launch_force(t, 1)) return rc;
     if (int rc = tsne_launch_update(t, 0, 1, 1.0, 0.0, 0.0, 0.0, t->costs + slot)) return rc;
     cost_iters[slot++] = last;
     HIPCHECK(hipStreamSynchronize(t->stream));
-    float ms = 0.0f;
-    HIPCHECK(hipEventElapsedTime(&ms, t->ev0, t->ev1));                         // the iterations, without the closing cost evaluation
-    t->times_ms[3] = ms;
-    HIPCHECK(hipEventElapsedTime(&ms, t->ev2, t->ev3));
-    t->times_ms[5] = ms;
-    HIPCHECK(hipEventElapsedTime(&ms, t->ev3, t->ev1));
-    t->times_ms[6] = ms;
+    int rc;
+    if ((rc = tsne_elapsed(t, kEvBegin, kEvEnd, &t->times_ms[kTimeLoop])) ||       // the iterations, without the closing cost evaluation
+        (rc = tsne_elapsed(t, kEvLast, kEvLastForce, &t->times_ms[kTimeLastForce])) ||
+        (rc = tsne_elapsed(t, kEvLastForce, kEvEnd, &t->times_ms[kTimeLastUpdate])))
+        return rc;
     if (t->K > 0) {
-        t->knn_ms[4] = ms;
-        HIPCHECK(hipEventElapsedTime(&ms, t->ev2, t->ev4));
-        t->knn_ms[2] = ms;
-        HIPCHECK(hipEventElapsedTime(&ms, t->ev4, t->ev3));
-        t->knn_ms[3] = ms;
+        t->knn_ms[kKnnTimeUpdate] = t->times_ms[kTimeLastUpdate];
+        if ((rc = tsne_elapsed(t, kEvLast, kEvLastMid, &t->knn_ms[kKnnTimeAttract])) ||
+            (rc = tsne_elapsed(t, kEvLastMid, kEvLastForce, &t->knn_ms[kKnnTimeRepulse])))
+            return rc;
     }
     const auto t0 = host_clock::now();
     HIPCHECK(hipMemcpy(itercosts, t->costs, (size_t)slot * sizeof(double), hipMemcpyDeviceToHost));
-    t->times_ms[4] = ms_since(t0);
+    t->times_ms[kTimeReadBack] = ms_since(t0);
     *n_costs = slot;
     return VBNMF_OK;
 }
@@ -578,11 +594,12 @@ int vbnmf_tsne_run(vbnmf_tsne *t, int32_t first_iter, int32_t n_iter, double exa
 int vbnmf_tsne_info(vbnmf_tsne *t, int32_t *ints, double *times_ms)
 {
     if (ints) {
-        const int32_t v[8] = {kTsneWave, kTsneThreads, kTsneIBlock, kTsneJTile, kTsneLdsRow, t ? t->aff_grid : 0, t ? t->force_grid : 0, kTsneUpdThreads};
-        for (int k = 0; k < 8; k++) ints[k] = v[k];
+        ints[kInfoWave] = kTsneWave; ints[kInfoThreads] = kTsneThreads; ints[kInfoIBlock] = kTsneIBlock; ints[kInfoJTile] = kTsneJTile;
+        ints[kInfoLdsRow] = kTsneLdsRow; ints[kInfoAffGrid] = t ? t->aff_grid : 0; ints[kInfoForceGrid] = t ? t->force_grid : 0;
+        ints[kInfoUpdThreads] = kTsneUpdThreads;
     }
     if (times_ms)
-        for (int k = 0; k < 7; k++) times_ms[k] = t ? t->times_ms[k] : (k < 3 ? tl_tsne_create_ms[k] : 0.0);
+        for (int k = 0; k < kTsneTimeSlots; k++) times_ms[k] = t ? t->times_ms[k] : (k < kTsneCreateTimes ? tl_tsne_create_ms[k] : 0.0);
     return VBNMF_OK;
 }
 

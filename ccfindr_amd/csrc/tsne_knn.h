@@ -1,14 +1,15 @@
 // tsne_knn.h -- gfx950 kernels of the neighbour-limited t-SNE map (included once, by tsne.hip, after tsne.h).
 //
 //   N_i = the K indices j != i with the smallest (D_ij, j), in that order (ties in distance go to the lower index) -> k_tsne_knn
-//   the bisection of tsne.h line for line, but over N_i only; p_{j|i} = exp(-beta_i D_ij) * (1 / S_i)                -> k_tsne_knn
+//   tsne.h's bisection (tsne_bisect), but over N_i only; p_{j|i} = exp(-beta_i D_ij) * (1 / S_i)                    -> k_tsne_knn
 //   P on the pattern {(i, j): j in N_i or i in N_j}, rows with ascending j, (p_{j|i} + p_{i|j}) * 1/(2n)             -> host, tsne.hip
 //   A_i = sum over the stored row of P_ij w_ij (y_i - y_j), and the three cost sums                                   -> k_tsne_attract
 //   R_i = sum_{j != i} w_ij^2 (y_i - y_j), z_i = sum_{j != i} w_ij over ALL j, exactly                                 -> k_tsne_repulse
 //   Z, dY, gains, uY, Y, the cost: k_tsne_update of tsne.h, untouched (the same sums[8][n])
 //
 // The rules of tsne.h hold: fp64, wave64, no floating-point atomics, every sum in a fixed tree, every loop bounded by n, d, K,
-// a tile or kTsneMaxTrips, every index formed from values the host checked.  The integer counters in LDS (a histogram, a
+// a tile or kTsneMaxTrips, every index formed from values the host checked.  What a kernel here does as a kernel of tsne.h does
+// is that header's function: tsne_distance_row, tsne_bisect, tsne_pair_w, tsne_lane_point, tsne_merge_waves.  The integer counters in LDS (a histogram, a
 // fill count) are added to in any order; nothing that is written out depends on the order in which those additions land.
 #pragma once
 #include "tsne.h"
@@ -35,8 +36,8 @@ struct TsneKnnArgs {
     double *pcond;                 // [n][K] p_{j|i} of the K neighbours, in the list's order
 };
 
-// One workgroup per point i, in grid strides; the row D_i. as in k_tsne_affinity (LDS up to kTsneLdsRow distances, else the
-// workgroup's row of `scratch`; thread t writes and reads the entries j = t, t + 256, .. only).
+// One workgroup per point i, in grid strides; the row D_i. by tsne_distance_row (LDS up to kTsneLdsRow distances, else the
+// workgroup's row of `scratch`).
 // Selection: the K-th smallest of the n - 1 composite keys (bits of D_ij, j) -- the bit pattern of a non-negative double
 // orders as the double does, and the keys are distinct -- by a radix select from the top: 8 passes over the bytes of D, then,
 // only if the tie at the K-th distance is cut, 4 over the bytes of j.  A pass counts the candidates (the keys that match the
@@ -44,8 +45,8 @@ struct TsneKnnArgs {
 // the waves' totals) finds the one bin in which the count crosses what is still to take.  The counts are sums of integers:
 // they do not depend on the order of the atomic additions.  Then every key <= the K-th is put into LDS at a slot an atomic
 // counter hands out -- exactly K of them, in an order that does depend on timing -- and a bitonic sort by (D, j) puts them
-// into the one order they have.  Bisection: thread q adds the terms q, q + 256, .. of the sorted list in ascending order, a
-// wave its 64 lanes in the xor butterfly, the waves are added in wave order: k_tsne_affinity's tree over K terms.
+// into the one order they have.  Bisection: tsne_bisect over the sorted list, so thread q adds the terms q, q + 256, .. in
+// ascending order: k_tsne_affinity's tree over K terms.
 __global__ __launch_bounds__(kTsneThreads) void k_tsne_knn(const TsneKnnArgs A)
 {
     __shared__ double s_row[kTsneLdsRow];
@@ -59,23 +60,13 @@ __global__ __launch_bounds__(kTsneThreads) void k_tsne_knn(const TsneKnnArgs A)
     __shared__ double s_red[2 * kTsneWaves];
     __shared__ double s_ctl[2];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int n = A.n, d = A.d, K = A.K;
+    const int n = A.n, K = A.K;
     double *row = n <= kTsneLdsRow ? s_row : A.scratch + (int64_t)blockIdx.x * n;
     int P2 = 1;
     while (P2 < K) P2 <<= 1;                                                   // <= kTsneKnnMax: the host checked K
 
     for (int i = blockIdx.x; i < n; i += gridDim.x) {
-        __syncthreads();                                                       // the last point's reads of the shared arrays are done
-        if (t < d) s_xi[t] = A.xt[(int64_t)t * n + i];
-        __syncthreads();
-        for (int j = t; j < n; j += kTsneThreads) {
-            double D = 0.0;
-            for (int k = 0; k < d; k++) {
-                const double df = s_xi[k] - A.xt[(int64_t)k * n + j];
-                D += df * df;
-            }
-            row[j] = D;
-        }
+        tsne_distance_row(A.xt, n, A.d, i, s_xi, row);
         // ---- the K-th smallest (D, j)
         unsigned long long pk = 0ull, mk = 0ull;                               // the digits of D chosen so far and their mask
         unsigned int pj = 0u, mj = 0u;                                         // ... of j
@@ -149,53 +140,16 @@ __global__ __launch_bounds__(kTsneThreads) void k_tsne_knn(const TsneKnnArgs A)
             A.dist[(int64_t)i * K + q] = __longlong_as_double((long long)s_key[q]);
         }
         if (!A.affinity) continue;                                             // (uniform)
-        // ---- the bisection of k_tsne_affinity over the K distances
-        double beta = 1.0, lo = -DBL_MAX, hi = DBL_MAX, S = 0.0;               // lo, hi, trips: thread 0's
-        int trips = 0, state = 0;                                              // 0 bisecting, 1 converged, 2 out of trips
-        for (;;) {
-            double sp = 0.0, sdp = 0.0;
-            for (int q = t; q < K; q += kTsneThreads) {
-                const double D = __longlong_as_double((long long)s_key[q]);
-                const double p = exp(-beta * D);
-                sp += p;
-                sdp += D * p;
-            }
-            sp = tsne_wave_sum(sp);
-            sdp = tsne_wave_sum(sdp);
-            __syncthreads();                                                   // s_red and s_ctl are free
-            if (lane == 0) { s_red[wave] = sp; s_red[kTsneWaves + wave] = sdp; }
-            __syncthreads();
-            sp = s_red[0]; sdp = s_red[kTsneWaves];
-#pragma unroll
-            for (int w = 1; w < kTsneWaves; w++) { sp += s_red[w]; sdp += s_red[kTsneWaves + w]; }
-            S = sp + DBL_MIN;
-            if (state == 2) break;
-            if (t == 0) {
-                const double H = beta * sdp / S + log(S);
-                const double delta = H - A.log_u;
-                trips++;
-                if (fabs(delta) < 1e-5) state = 1;
-                else {
-                    if (delta > 0.0) { lo = beta; beta = hi == DBL_MAX ? beta * 2.0 : (beta + hi) / 2.0; }
-                    else { hi = beta; beta = lo == -DBL_MAX ? beta / 2.0 : (beta + lo) / 2.0; }
-                    if (trips == kTsneMaxTrips) state = 2;
-                }
-                s_ctl[0] = beta;
-                s_ctl[1] = (double)state;
-            }
-            __syncthreads();
-            beta = s_ctl[0];
-            state = (int)s_ctl[1];
-            if (state == 1) break;
-        }
-        const double inv = 1.0 / S;
-        for (int q = t; q < K; q += kTsneThreads)
-            A.pcond[(int64_t)i * K + q] = exp(-beta * __longlong_as_double((long long)s_key[q])) * inv;
+        // ---- the bisection over the K sorted distances, none left out
+        const auto dist = [](int q) { return __longlong_as_double((long long)s_key[q]); };
+        const TsneBisection b = tsne_bisect(K, -1, dist, A.log_u, s_red, s_ctl);
+        const double inv = 1.0 / b.S;
+        for (int q = t; q < K; q += kTsneThreads) A.pcond[(int64_t)i * K + q] = exp(-b.beta * dist(q)) * inv;
         if (t == 0) {
-            A.beta[i] = beta;
-            A.sum_p[i] = S;
+            A.beta[i] = b.beta;
+            A.sum_p[i] = b.S;
             A.inv_s[i] = inv;
-            A.trips[i] = trips;
+            A.trips[i] = b.trips;
         }
     }
 }
@@ -225,7 +179,7 @@ __global__ __launch_bounds__(kTsneThreads) void k_tsne_attract(const TsneAttArgs
             const int j = A.indices[q];
             const double P = A.values[q];
             const double d0 = yi0 - A.y0[j], d1 = yi1 - A.y1[j];
-            const double w = 1.0 / (1.0 + d0 * d0 + d1 * d1);
+            const double w = tsne_pair_w(d0, d1);
             const double pw = P * w;
             a0 += pw * d0;
             a1 += pw * d1;
@@ -259,17 +213,15 @@ struct TsneRepArgs {
 
 // The R, z half of k_tsne_force: a workgroup owns the kTsneIBlock points i = blockIdx.x * 64 + lane and streams all j through
 // LDS in tiles of kTsneRepTile pairs (y_j0, y_j1).  Wave w takes the entries w * 256 .. w * 256 + 255 of every tile, adds its
-// terms in ascending j, and lane i of wave 0 adds the four partial sums as (w0 + w1) + (w2 + w3).  The division is IEEE.
+// terms in ascending j, and tsne_merge_waves joins the four partial sums.
 __global__ __launch_bounds__(kTsneThreads) void k_tsne_repulse(const TsneRepArgs A)
 {
     __shared__ __attribute__((aligned(16))) double s_y[2 * kTsneRepTile];
     constexpr int kShare = kTsneRepTile / kTsneWaves;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int n = A.n;
-    const int i = blockIdx.x * kTsneIBlock + lane;
-    const bool valid = i < n;
-    const int ii = valid ? i : n - 1;                                          // a lane past the end loads the last point and writes nothing
-    const double yi0 = A.y0[ii], yi1 = A.y1[ii];
+    const TsneLanePoint pt = tsne_lane_point(n, lane);
+    const double yi0 = A.y0[pt.ii], yi1 = A.y1[pt.ii];
     double r0 = 0.0, r1 = 0.0, z = 0.0;
 
     for (int j0 = 0; j0 < n; j0 += kTsneRepTile) {
@@ -286,8 +238,8 @@ __global__ __launch_bounds__(kTsneThreads) void k_tsne_repulse(const TsneRepArgs
 #pragma unroll 4
         for (int q = 0; q < cnt; q++) {
             const double d0 = yi0 - T[2 * q], d1 = yi1 - T[2 * q + 1];
-            const double w = 1.0 / (1.0 + d0 * d0 + d1 * d1);
-            if (valid && jw + q != i) {
+            const double w = tsne_pair_w(d0, d1);
+            if (pt.valid && jw + q != pt.i) {
                 const double ww = w * w;
                 r0 += ww * d0;
                 r1 += ww * d1;
@@ -295,20 +247,8 @@ __global__ __launch_bounds__(kTsneThreads) void k_tsne_repulse(const TsneRepArgs
             }
         }
     }
-    __syncthreads();                                                           // the tile is free: the waves' partial sums go there
-    double *s_part = s_y;                                                      // [kTsneWaves][3][64]
-    s_part[(wave * 3 + 0) * kTsneWave + lane] = r0;
-    s_part[(wave * 3 + 1) * kTsneWave + lane] = r1;
-    s_part[(wave * 3 + 2) * kTsneWave + lane] = z;
-    __syncthreads();
-    if (wave == 0 && valid) {
-#pragma unroll
-        for (int s = 0; s < 3; s++) {
-            const double p0 = s_part[(0 * 3 + s) * kTsneWave + lane], p1 = s_part[(1 * 3 + s) * kTsneWave + lane];
-            const double p2 = s_part[(2 * 3 + s) * kTsneWave + lane], p3 = s_part[(3 * 3 + s) * kTsneWave + lane];
-            A.sums[(int64_t)(2 + s) * n + i] = (p0 + p1) + (p2 + p3);
-        }
-    }
+    const double mine[3] = {r0, r1, z};
+    tsne_merge_waves(mine, s_y, A.sums, 2, n, pt, lane, wave);                 // s_part [kTsneWaves][3][64]
 }
 
 }  // namespace vbnmf

@@ -35,6 +35,10 @@ def _i32p(a):
     return a.ctypes.data_as(N.c_int32_p)
 
 
+def _i64p(a):
+    return a.ctypes.data_as(N.c_int64_p)
+
+
 def _pairs(a, n, what):
     if a is None:
         return None
@@ -44,18 +48,17 @@ def _pairs(a, n, what):
     return a
 
 
-def tsne_info(handle=None):
-    """Constants of the kernels (``vbnmf_tsne_info``), with the grids and ``times_ms`` of ``handle`` (a ``TSNE``) if given."""
-    ints = np.zeros(8, dtype=np.int32)
-    times = np.zeros(len(_TIMES), dtype=np.float64)
-    N.check(N.load().vbnmf_tsne_info(handle._h if handle is not None else None, _i32p(ints), N.dptr(times)))
-    out = {k: int(v) for k, v in zip(_INFO, ints)}
-    out["times_ms"] = dict(zip(_TIMES, (float(v) for v in times)))
+def _info(call, handle, names, ints, intp, time_names):
+    times = np.zeros(len(time_names), dtype=np.float64)
+    N.check(call(handle._h if handle is not None else None, intp(ints), N.dptr(times)))
+    out = {k: int(v) for k, v in zip(names, ints)}
+    out["times_ms"] = dict(zip(time_names, (float(v) for v in times)))
     return out
 
 
-def _i64p(a):
-    return a.ctypes.data_as(N.c_int64_p)
+def tsne_info(handle=None):
+    """Constants of the kernels (``vbnmf_tsne_info``), with the grids and ``times_ms`` of ``handle`` (a ``TSNE``) if given."""
+    return _info(N.load().vbnmf_tsne_info, handle, _INFO, np.zeros(len(_INFO), dtype=np.int32), _i32p, _TIMES)
 
 
 def _neighbors_arg(neighbors):
@@ -77,12 +80,7 @@ def tsne_knn_info(handle=None):
     """Constants of the neighbour kernels (``vbnmf_tsne_knn_info``), with K, nnz, the longest row, the attraction grid and
     ``times_ms`` of ``handle`` (a ``TSNE`` with neighbours) if given; without one ``times_ms["search"]`` is the calling thread's
     last search."""
-    ints = np.zeros(len(_KNN_INFO), dtype=np.int64)
-    times = np.zeros(len(_KNN_TIMES), dtype=np.float64)
-    N.check(N.load().vbnmf_tsne_knn_info(handle._h if handle is not None else None, _i64p(ints), N.dptr(times)))
-    out = {k: int(v) for k, v in zip(_KNN_INFO, ints)}
-    out["times_ms"] = dict(zip(_KNN_TIMES, (float(v) for v in times)))
-    return out
+    return _info(N.load().vbnmf_tsne_knn_info, handle, _KNN_INFO, np.zeros(len(_KNN_INFO), dtype=np.int64), _i64p, _KNN_TIMES)
 
 
 def knn(x, k, device=None):
@@ -116,13 +114,10 @@ class TSNE:
         k = _neighbors_arg(neighbors)
         h = ctypes.c_void_p()
         dev = 0 if device is None else int(device)
-        if k is None:
-            N.check(N.load().vbnmf_tsne_create(dev, self.n, self.d, N.dptr(x), float(perplexity), 1 if normalize else 0, ctypes.byref(h)))
-            self._h = h
-        else:
-            N.check(N.load().vbnmf_tsne_create_knn(dev, self.n, self.d, N.dptr(x), float(perplexity), 1 if normalize else 0, k,
-                                                   ctypes.byref(h)))
-            self._h = h
+        args = (dev, self.n, self.d, N.dptr(x), float(perplexity), 1 if normalize else 0)
+        N.check(N.load().vbnmf_tsne_create(*args, ctypes.byref(h)) if k is None else N.load().vbnmf_tsne_create_knn(*args, k, ctypes.byref(h)))
+        self._h = h
+        if k is not None:
             self.neighbors = tsne_knn_info(self)["neighbors"]
         self.beta = np.zeros(self.n)
         self.sum_p = np.zeros(self.n)

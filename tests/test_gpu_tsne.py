@@ -39,8 +39,7 @@ def _handle(c):
     return C.TSNE(c["X"], perplexity=c["u"], normalize=c["normalize"])
 
 
-def _f(v):
-    return mp.mpf(float(v))
+_f = T._f
 
 
 # ---- 1. affinities -----------------------------------------------------------------------------------------------------------
@@ -179,10 +178,7 @@ def test_loop_is_reproducible_and_costs_are_those_of_forces():
 
 
 # ---- 5. end to end -----------------------------------------------------------------------------------------------------------
-def _nn_same(Y, cid):
-    d2 = ((Y[:, None, :] - Y[None, :, :]) ** 2).sum(axis=2)
-    np.fill_diagonal(d2, np.inf)
-    return int((cid[d2.argmin(axis=1)] == cid).sum())
+_nn_same = T.nn_same
 
 
 def test_three_clusters_end_to_end():

@@ -27,8 +27,7 @@ CASES = [pytest.param(c, id=c[0]) for c in HANDLES]
 FORCE_CASES = CASES + [pytest.param("hub", id="hub")]
 
 
-def _f(v):
-    return mp.mpf(float(v))
+_f = T._f
 
 
 def _case(c):
@@ -286,10 +285,7 @@ def test_loop_is_reproducible_and_costs_are_those_of_forces():
 
 
 # ---- 7. end to end -----------------------------------------------------------------------------------------------------------
-def _nn_same(Y, cid):
-    d2 = ((Y[:, None, :] - Y[None, :, :]) ** 2).sum(axis=2)
-    np.fill_diagonal(d2, np.inf)
-    return int((cid[d2.argmin(axis=1)] == cid).sum())
+_nn_same = T.nn_same
 
 
 def test_three_clusters_end_to_end():

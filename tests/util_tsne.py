@@ -42,25 +42,18 @@ def sq_dist(X):
     return D
 
 
-def affinities(X, u, D=None):
-    """The bisection of every row -> beta, S, trips, flagged (rows where another summation order may branch otherwise).
-    A row that uses up its trips keeps the beta of the last update and S is evaluated once more at it."""
-    n = len(X)
-    D = sq_dist(X) if D is None else D
+def bisection(n, u, sums):
+    """The bisection of every row -> beta, S, trips, flagged (rows where another summation order may branch otherwise);
+    sums(rows, beta) -> S and sum D exp(-beta D) of those rows.  A row that uses up its trips keeps the beta of the last update
+    and S is evaluated once more at it."""
     beta, lo, hi = np.ones(n), np.full(n, -DBL_MAX), np.full(n, DBL_MAX)
     S, trips, flagged = np.zeros(n), np.zeros(n, dtype=np.int32), np.zeros(n, dtype=bool)
     act = np.arange(n)
     lnu = math.log(u)
-
-    def sums(rows):
-        p = np.exp(-beta[rows, None] * D[rows])
-        p[np.arange(len(rows)), rows] = 0.0
-        return p.sum(axis=1) + DBL_MIN, (D[rows] * p).sum(axis=1)
-
     for _ in range(MAX_TRIPS):
         if not len(act):
             break
-        s, sdp = sums(act)
+        s, sdp = sums(act, beta)
         H = beta[act] * sdp / s + np.log(s)
         delta = H - lnu
         S[act] = s
@@ -77,8 +70,20 @@ def affinities(X, u, D=None):
         beta[r] = np.where(lo[r] == -DBL_MAX, beta[r] / 2.0, (beta[r] + lo[r]) / 2.0)
         act = act[~conv]
     if len(act):
-        S[act] = sums(act)[0]
+        S[act] = sums(act, beta)[0]
     return beta, S, trips, flagged
+
+
+def affinities(X, u, D=None):
+    """The bisection over all j != i of every row (the entry i is zeroed, not left out: numpy's sum then rounds as it does)."""
+    D = sq_dist(X) if D is None else D
+
+    def sums(rows, beta):
+        p = np.exp(-beta[rows, None] * D[rows])
+        p[np.arange(len(rows)), rows] = 0.0
+        return p.sum(axis=1) + DBL_MIN, (D[rows] * p).sum(axis=1)
+
+    return bisection(len(D), u, sums)
 
 
 def joint_p(D, beta, S):
@@ -185,18 +190,24 @@ def force_depth(n):
     return 8 * (-(-n // 32)) + 2
 
 
-def mp_point(X, beta, S, Y, i, e=1.0, Z=None):
-    """Point i in 50 digits from the doubles X, beta, S, Y -> dict A (2), R (2), z, and cost if Z (50 digits) is given."""
-    n, d = X.shape
+def mp_point(X, beta, S, Y, i, e=1.0, Z=None, idx=None):
+    """Point i in 50 digits from the doubles X, beta, S, Y -> dict A (2), R (2), z, and cost if Z (50 digits) is given.
+    idx: the neighbour lists (util_tsne_knn); a half p_{j|i} that is not listed is exactly 0.  None: every pair is listed."""
+    n = len(X)
     D = mp_dist_row(X, i)
+    mine = None if idx is None else set(int(j) for j in idx[i])
     bi, si = _f(beta[i]), _f(S[i])
     yi = [_f(Y[i, 0]), _f(Y[i, 1])]
     tA, tR, tz, tc = [[], []], [[], []], [], []
-    lnZ = mp.log(Z) if Z is not None else None
     for j in range(n):
         if j == i:
             continue
-        P = (mp.exp(-bi * D[j]) / si + mp.exp(-_f(beta[j]) * D[j]) / _f(S[j])) / (2 * n)
+        P = mp.mpf(0)                                # (0 + a is exact)
+        if idx is None or j in mine:
+            P += mp.exp(-bi * D[j]) / si
+        if idx is None or i in idx[j]:
+            P += mp.exp(-_f(beta[j]) * D[j]) / _f(S[j])
+        P /= 2 * n
         dy = [yi[0] - _f(Y[j, 0]), yi[1] - _f(Y[j, 1])]
         w = 1 / (1 + dy[0] ** 2 + dy[1] ** 2)
         tz.append(w)
@@ -211,36 +222,46 @@ def mp_point(X, beta, S, Y, i, e=1.0, Z=None):
     return out
 
 
-def force_bounds(D, d, beta, S, Y, e=1.0):
-    """The derivation above for every point at once (the bounds themselves need no more than fp64) -> absolute bounds A, R
-    (n x 2), z, cost (n) for a device result against 50 digits, and the sums of absolute terms they are a share of."""
+def p_bounds(D, d, beta, S, M=None, subnormal=0.0):
+    """-> P and dP of the comment above, n x n.  M[i, j]: p_{j|i} is formed (None: for every j != i); `subnormal` is added to
+    dP where either half is (util_tsne_knn.SUBNORMAL; the dense kernel's P has no such term)."""
     n = len(D)
-    dep = force_depth(n)
-    pc = np.exp(-beta[:, None] * D) / S[:, None]
-    np.fill_diagonal(pc, 0.0)
+    M = ~np.eye(n, dtype=bool) if M is None else M
+    pc = np.where(M, np.exp(-beta[:, None] * D) / S[:, None], 0.0)
     P = (pc + pc.T) / (2.0 * n)
     bp = beta[:, None] * pc
-    dP = 7 * U * P + (d + 3) * U * D * (bp + bp.T) / (2.0 * n)
+    return P, 7 * U * P + (d + 3) * U * D * (bp + bp.T) / (2.0 * n) + np.where(M | M.T, subnormal, 0.0)
+
+
+def force_bounds(D, d, beta, S, Y, e=1.0, M=None, depA=None, depR=None, subnormal=0.0):
+    """The derivation above for every point at once (the bounds themselves need no more than fp64) -> absolute bounds A, R
+    (n x 2), z, cost (n) for a device result against 50 digits, the sums of absolute terms they are a share of, and the P they
+    were formed from.  depA, depR: the summation depths of A with the cost sums (a number or one per row) and of R with z;
+    None: force_depth(n), the dense kernel's for both.  M, subnormal: as for p_bounds."""
+    n = len(D)
+    depA = force_depth(n) if depA is None else depA
+    depR = force_depth(n) if depR is None else depR
+    P, dP = p_bounds(D, d, beta, S, M, subnormal)
     dy = Y[:, None, :] - Y[None, :, :]
     w = 1.0 / (1.0 + dy[:, :, 0] ** 2 + dy[:, :, 1] ** 2)
     np.fill_diagonal(w, 0.0)
-    out = {"A": np.zeros((n, 2)), "R": np.zeros((n, 2)), "abs_A": np.zeros((n, 2)), "abs_R": np.zeros((n, 2))}
+    out = {"A": np.zeros((n, 2)), "R": np.zeros((n, 2)), "abs_A": np.zeros((n, 2)), "abs_R": np.zeros((n, 2)), "P": P}
     for c in range(2):
         tA, tR = np.abs(e * P * w * dy[:, :, c]), np.abs(w * w * dy[:, :, c])
         out["abs_A"][:, c], out["abs_R"][:, c] = tA.sum(1), tR.sum(1)
-        out["A"][:, c] = (np.abs(e * w * dy[:, :, c]) * dP + 10 * U * tA).sum(1) + (dep + 1) * U * tA.sum(1)
-        out["R"][:, c] = (15 + dep + 1) * U * tR.sum(1)
+        out["A"][:, c] = (np.abs(e * w * dy[:, :, c]) * dP + 10 * U * tA).sum(1) + (depA + 1) * U * tA.sum(1)
+        out["R"][:, c] = (15 + depR + 1) * U * tR.sum(1)
     z = w.sum(1)
-    out["z"], out["abs_z"] = (6 + dep + 1) * U * z, z
+    out["z"], out["abs_z"] = (6 + depR + 1) * U * z, z
     lnZ = abs(math.log(z.sum()))
-    rZ = (6 + dep + (-(-n // 1024)) + 6 + 15) * U
+    rZ = (6 + depR + (-(-n // 1024)) + 6 + 15) * U
     with np.errstate(divide="ignore", invalid="ignore"):
         lp = np.where(P > 0, np.abs(np.log(np.where(P > 0, P, 1.0))), 0.0)
         lw = np.where(w > 0, np.abs(np.log(np.where(w > 0, w, 1.0))), 0.0)
     pos = P > 0
     ec = np.where(pos, dP * (lp + 1 + lw + lnZ) + U * (3 * P * lp + 6 * P + 3 * P * lw) + P * (rZ + 3 * U * lnZ), 0.0)
     sc = np.where(pos, P * lp + P * lw + P * lnZ, 0.0).sum(1)
-    out["cost"], out["abs_cost"] = ec.sum(1) + (dep + 4) * U * sc, sc
+    out["cost"], out["abs_cost"] = ec.sum(1) + (depA + 4) * U * sc, sc
     return out
 
 
@@ -342,3 +363,10 @@ SPECIAL = {                                  # name -> arguments of case()
 E2E = dict(n=300, d=3, k=3, seed=11)
 E2E_FINAL = (0.28726339468839934, 0.2740588050049169, 0.28419602357038803, 0.2830980237485424, 0.30152232496421605)
 E2E_NN_SAME = 300
+
+
+def nn_same(Y, cid):
+    """The points whose nearest neighbour in Y has their own cluster."""
+    d2 = ((Y[:, None, :] - Y[None, :, :]) ** 2).sum(axis=2)
+    np.fill_diagonal(d2, np.inf)
+    return int((cid[d2.argmin(axis=1)] == cid).sum())

@@ -34,39 +34,12 @@ def knn_lists(D, K):
 
 
 def affinities(dist, u):
-    """util_tsne.affinities line for line, over the K listed distances of every row -> beta, S, trips, flagged."""
-    n = len(dist)
-    beta, lo, hi = np.ones(n), np.full(n, -DBL_MAX), np.full(n, DBL_MAX)
-    S, trips, flagged = np.zeros(n), np.zeros(n, dtype=np.int32), np.zeros(n, dtype=bool)
-    act = np.arange(n)
-    lnu = math.log(u)
-
-    def sums(rows):
+    """util_tsne.bisection over the K listed distances of every row -> beta, S, trips, flagged."""
+    def sums(rows, beta):
         p = np.exp(-beta[rows, None] * dist[rows])
         return p.sum(axis=1) + DBL_MIN, (dist[rows] * p).sum(axis=1)
 
-    for _ in range(MAX_TRIPS):
-        if not len(act):
-            break
-        s, sdp = sums(act)
-        H = beta[act] * sdp / s + np.log(s)
-        delta = H - lnu
-        S[act] = s
-        trips[act] += 1
-        flagged[act] |= (np.abs(np.abs(delta) - TOL) < FLAG) | (np.abs(delta) < FLAG)
-        conv = np.abs(delta) < TOL
-        up = ~conv & (delta > 0)
-        dn = ~conv & ~(delta > 0)
-        r = act[up]
-        lo[r] = beta[r]
-        beta[r] = np.where(hi[r] == DBL_MAX, beta[r] * 2.0, (beta[r] + hi[r]) / 2.0)
-        r = act[dn]
-        hi[r] = beta[r]
-        beta[r] = np.where(lo[r] == -DBL_MAX, beta[r] / 2.0, (beta[r] + lo[r]) / 2.0)
-        act = act[~conv]
-    if len(act):
-        S[act] = sums(act)[0]
-    return beta, S, trips, flagged
+    return T.bisection(len(dist), u, sums)
 
 
 def cond_p(dist, beta, S):
@@ -108,16 +81,14 @@ def run(P, Y, n_iter, **kw):
 
 
 # ---- 50 digits ---------------------------------------------------------------------------------------------------------------
-def _f(v):
-    return mp.mpf(float(v))
+_f = T._f
 
 
 # Affinity sums over a list.  The terms are util_tsne's: p_j = exp(-beta D_ij) is off by 2u (exp) and by the exponent's
 # (d + 3) beta D_ij u, relative.  The tree of k_tsne_knn: a thread adds the ceil(K / 256) terms q, q + 256, .. of the sorted
 # list, then 6 butterfly levels, 3 additions of wave values and the DBL_MIN: depth = ceil(K / 256) + 6 + 3 + 1, each addition
-# costing u of the (positive) partial sum.  K_S = 2 + depth + 1 (second-order terms), as util_tsne.k_aff with K for n.
-def k_aff(K):
-    return 2 + (-(-K // 256) + 6 + 3 + 1) + 1
+# costing u of the (positive) partial sum.  K_S = 2 + depth + 1 (second-order terms): util_tsne.k_aff with K for n.
+k_aff = T.k_aff
 
 
 def mp_row(X, i, nbrs, beta, u):
@@ -165,68 +136,15 @@ def masks(idx):
 
 def mp_point(X, beta, S, idx, Y, i, e=1.0, Z=None):
     """Point i in 50 digits from the doubles X, beta, S, Y and the lists -> dict A (2), R (2), z, and cost if Z is given."""
-    n = len(X)
-    D = T.mp_dist_row(X, i)
-    mine = set(int(j) for j in idx[i])
-    bi, si = _f(beta[i]), _f(S[i])
-    yi = [_f(Y[i, 0]), _f(Y[i, 1])]
-    tA, tR, tz, tc = [[], []], [[], []], [], []
-    for j in range(n):
-        if j == i:
-            continue
-        P = mp.mpf(0)
-        if j in mine:
-            P += mp.exp(-bi * D[j]) / si
-        if i in idx[j]:
-            P += mp.exp(-_f(beta[j]) * D[j]) / _f(S[j])
-        P /= 2 * n
-        dy = [yi[0] - _f(Y[j, 0]), yi[1] - _f(Y[j, 1])]
-        w = 1 / (1 + dy[0] ** 2 + dy[1] ** 2)
-        tz.append(w)
-        for c in range(2):
-            tA[c].append(_f(e) * P * w * dy[c])
-            tR[c].append(w * w * dy[c])
-        if Z is not None and P > 0:
-            tc.append(P * mp.log(P * Z / w))
-    out = {"A": [mp.fsum(tA[0]), mp.fsum(tA[1])], "R": [mp.fsum(tR[0]), mp.fsum(tR[1])], "z": mp.fsum(tz)}
-    if Z is not None:
-        out["cost"] = mp.fsum(tc)
-    return out
+    return T.mp_point(X, beta, S, Y, i, e, Z, idx)
 
 
 def force_bounds(D, d, beta, S, idx, Y, e=1.0, tile=1024):
-    """util_tsne.force_bounds with the depths above -> absolute bounds A, R (n x 2), z, cost (n) and the sums of absolute
-    terms they are a share of; also the dense P the bounds were formed from."""
-    n = len(D)
+    """util_tsne.force_bounds with the depths above and SUBNORMAL -> absolute bounds A, R (n x 2), z, cost (n), the sums of
+    absolute terms they are a share of, and the dense P the bounds were formed from."""
     M = masks(idx)
-    row_len = (M | M.T).sum(1)
-    depA = (-(-row_len // 64) + 6).astype(np.float64)
-    depR = repulse_depth(n, tile)
-    pc = np.where(M, np.exp(-beta[:, None] * D) / S[:, None], 0.0)
-    P = (pc + pc.T) / (2.0 * n)
-    bp = beta[:, None] * pc
-    dP = 7 * U * P + (d + 3) * U * D * (bp + bp.T) / (2.0 * n) + np.where(M | M.T, SUBNORMAL, 0.0)
-    dy = Y[:, None, :] - Y[None, :, :]
-    w = 1.0 / (1.0 + dy[:, :, 0] ** 2 + dy[:, :, 1] ** 2)
-    np.fill_diagonal(w, 0.0)
-    out = {"A": np.zeros((n, 2)), "R": np.zeros((n, 2)), "abs_A": np.zeros((n, 2)), "abs_R": np.zeros((n, 2)), "P": P}
-    for c in range(2):
-        tA, tR = np.abs(e * P * w * dy[:, :, c]), np.abs(w * w * dy[:, :, c])
-        out["abs_A"][:, c], out["abs_R"][:, c] = tA.sum(1), tR.sum(1)
-        out["A"][:, c] = (np.abs(e * w * dy[:, :, c]) * dP + 10 * U * tA).sum(1) + (depA + 1) * U * tA.sum(1)
-        out["R"][:, c] = (15 + depR + 1) * U * tR.sum(1)
-    z = w.sum(1)
-    out["z"], out["abs_z"] = (6 + depR + 1) * U * z, z
-    lnZ = abs(math.log(z.sum()))
-    rZ = (6 + depR + (-(-n // 1024)) + 6 + 15) * U
-    with np.errstate(divide="ignore", invalid="ignore"):
-        lp = np.where(P > 0, np.abs(np.log(np.where(P > 0, P, 1.0))), 0.0)
-        lw = np.where(w > 0, np.abs(np.log(np.where(w > 0, w, 1.0))), 0.0)
-    pos = P > 0
-    ec = np.where(pos, dP * (lp + 1 + lw + lnZ) + U * (3 * P * lp + 6 * P + 3 * P * lw) + P * (rZ + 3 * U * lnZ), 0.0)
-    sc = np.where(pos, P * lp + P * lw + P * lnZ, 0.0).sum(1)
-    out["cost"], out["abs_cost"] = ec.sum(1) + (depA + 4) * U * sc, sc
-    return out
+    depA = attract_depth((M | M.T).sum(1)).astype(np.float64)
+    return T.force_bounds(D, d, beta, S, Y, e, M, depA, repulse_depth(len(D), tile), SUBNORMAL)
 
 
 # A stored value against 50 digits (from the doubles beta and S): dP of the comment above, with SUBNORMAL.
@@ -235,12 +153,7 @@ def force_bounds(D, d, beta, S, idx, Y, e=1.0, tile=1024):
 # the mean over i of the second part is sum_ij (d + 3) u D_ij beta_i p_{j|i} / n: the second term of sum dP again.  So
 # |sum P - 1| <= sum dP (the values) + (k_aff(K) u + sum dP) (the S_i) + DBL_MIN mean(1 / S) + u (fsum's one rounding).
 def p_bounds(D, d, beta, S, idx):
-    n = len(D)
-    M = masks(idx)
-    pc = np.where(M, np.exp(-beta[:, None] * D) / S[:, None], 0.0)
-    P = (pc + pc.T) / (2.0 * n)
-    bp = beta[:, None] * pc
-    return P, 7 * U * P + (d + 3) * U * D * (bp + bp.T) / (2.0 * n) + np.where(M | M.T, SUBNORMAL, 0.0)
+    return T.p_bounds(D, d, beta, S, masks(idx), SUBNORMAL)
 
 
 def sum_p_bound(dP, K, S):
