@@ -12,8 +12,8 @@ IDLE = 0xFFFFFFFF
 LDS_KB = {3: 96, 10: 160}
 
 
-def set_geometry(monkeypatch, r, merge=None):
-    monkeypatch.setenv("VBNMF_MAX_LEN", "16")
+def set_geometry(monkeypatch, r, merge=None, max_len=16):
+    monkeypatch.setenv("VBNMF_MAX_LEN", str(int(max_len)))
     monkeypatch.setenv("VBNMF_EQUAL_BLOCKS", "1")
     monkeypatch.setenv("VBNMF_LDS_KB", str(LDS_KB.get(r, 160)))
     if merge is None:
