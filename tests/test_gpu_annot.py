@@ -11,6 +11,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import util_annot as U  # noqa: E402
+from util_annot import compare, make_perms, make_sets, make_table  # noqa: E402  (the builders are shared with test_gpu_annot_grid.py)
 
 import ccfindr_amd as C  # noqa: E402
 from ccfindr_amd import annotate as A  # noqa: E402
@@ -20,63 +21,6 @@ pytestmark = pytest.mark.gpu
 
 INFO = A.gsea_info()
 W, G, CAP = INFO["wave_width"], INFO["workgroup_size"], INFO["max_set_hits"]
-
-
-def make_table(n, r, seed, na_clusters=(), all_prefixed=False):
-    """A meta table of n rows: every cluster lists the same n genes in its own order, weights decreasing with ties.  The clusters
-    in ``na_clusters`` end in NA rows (gene '', weight NaN), as a column shorter than the table does.  A tenth of the genes are
-    named IG* (all of them with ``all_prefixed``)."""
-    rng = np.random.default_rng(seed)
-    names = np.array([("IG%d" % i) if (all_prefixed or i % 10 == 3) else ("g%d" % i) for i in range(n)])
-    gene = np.empty((n, r), dtype=names.dtype)
-    w = np.empty((n, r))
-    for k in range(r):
-        gene[:, k] = names[rng.permutation(n)]
-        w[:, k] = np.sort(np.round(rng.gamma(0.8, 1.0, size=n), 1) + 0.1)[::-1]        # ties, and no zero
-        if k in na_clusters and n > 1:
-            cut = n - int(rng.integers(1, max(2, n // 3 + 1)))
-            gene[cut:, k] = ""
-            w[cut:, k] = np.nan
-    return C.MetaTable(gene=gene.astype(str), w=w, cv=np.full((n, r), 0.1)), names
-
-
-def make_sets(names, seed, sizes):
-    rng = np.random.default_rng(seed)
-    gset = {"none": ["absent1", "absent2"], "every": list(names)}
-    for t in sizes:
-        if 0 < t <= len(names):
-            gset["size%d" % t] = list(rng.choice(names, size=t, replace=False))
-    if len(names) >= 4:
-        gset["prefix"] = ["IG", str(names[0]), str(names[1])]                            # IG* rows by prefix: hits AND misses
-    return gset
-
-
-def make_perms(n, nperm, seed):
-    rng = np.random.default_rng(seed)
-    perms = np.array([rng.permutation(n) for _ in range(nperm)], dtype=np.int32).reshape(nperm, n)
-    perms[0] = np.arange(n)                                                              # the identity: exact ties meet the strict <
-    if nperm > 2:
-        perms[2] = perms[1]                                                              # and one permutation twice
-    return perms
-
-
-def compare(meta, gset, p, perms, label):
-    out = C.assign_celltype(meta, meta.rank, gset, p=p, p_value=True, perms=perms, grp_prefix=("IG",), return_null=True)
-    tb = A.gsea_tables(meta, gset, p=p, grp_prefix=("IG",))
-    es, exceed, null = U.assign_dense(meta.gene, meta.w, tb["wp"].T, gset, perms, ("IG",))
-    nan = int(np.isnan(es).sum())
-    print(f"{label}: N={meta.gene.shape[0]} r={meta.rank} sets={len(gset)} p={p} nperm={len(perms)}: {nan} of {es.size} scores NaN, "
-          f"largest set {int(np.diff(tb['hit_ptr']).max())} hits, exceed in [{exceed.min()}, {exceed.max()}]")
-    assert U.bits_equal(out["ES"], es), (label, out["ES"], es)
-    assert U.bits_equal(out["null_es"], null), label
-    assert out["exceed"].dtype == np.int64 and np.array_equal(out["exceed"], exceed), (label, out["exceed"], exceed)
-    with np.errstate(invalid="ignore"):
-        want_p = np.where(np.isnan(es), np.nan, exceed / float(len(perms)))
-    assert U.bits_equal(out["pvalue"], want_p)
-    assert np.array_equal(null[0], es, equal_nan=True) and np.all(exceed[~np.isnan(es)] <= len(perms) - 1)
-    # the observed scores alone: the same bits
-    assert U.bits_equal(C.assign_celltype(meta, meta.rank, gset, p=p, grp_prefix=("IG",)), es)
-    return out, es
 
 
 SMALL = [1, 2, W - 1, W, W + 1, G - 1, G + 1]

@@ -59,13 +59,19 @@ def _check_affinities(c, a, h):
     assert 1 <= h.trips.min() and h.trips.max() <= T.MAX_TRIPS
 
 
-@pytest.mark.parametrize("kw", CASES)
+FULL_ROW = T.full_lds_row(ROW)
+
+
+@pytest.mark.parametrize("kw", CASES + [pytest.param(T.shape_kw(FULL_ROW), id="n%d-d%d" % FULL_ROW[:2])])
 def test_affinities(kw):
     c, a = _case(kw)
     with _handle(c) as h:
         _check_affinities(c, a, h)
         info = h.info()
     assert info["force_grid"] == -(-c["n"] // IB) and 1 <= info["affinity_grid"] <= c["n"]
+    if c["n"] == ROW:
+        # fewer workgroups than points: a workgroup takes its second point's distances into the LDS row of its first
+        assert info["affinity_grid"] < c["n"], info["affinity_grid"]
 
 
 def test_affinities_row_past_the_lds_capacity():

@@ -66,7 +66,8 @@ def test_special_inputs_do_what_they_are_for():
 
 def test_committed_seeds_flag_no_row():
     cases, big = _all_cases()
-    for name, kw in cases + [("lds_row + 1", dict(n=big[0], d=big[1]))]:
+    full = T.full_lds_row(_info()["lds_row_capacity"])
+    for name, kw in cases + [("lds_row + 1", dict(n=big[0], d=big[1])), ("lds_row", T.shape_kw(full))]:
         _, a = _aff(kw)
         assert not a["flagged"].any(), (name, kw)
 

